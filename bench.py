@@ -1,6 +1,6 @@
 """Benchmark of the walk-training hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c5] [--full] [--dump-outputs DIR]
 
 One "step" = one full iteration of the reference's training loop (train.py:48-110) over one batch of synthetic z:
 sample z -> style MLP -> StyleGAN2 synthesis (original) -> ResNet-50 regressor -> linear W+ walk -> synthesis (edited)
@@ -13,9 +13,13 @@ sample z -> style MLP -> StyleGAN2 synthesis (original) -> ResNet-50 regressor -
   dataset/attributes_scene.txt, 5 attributes, train_multi_attr.py clamp flow), batch 8 per GPU, every contraction on the 16-bit
   matrix cores (3-term bf16 split, fp32 accumulation: fp32-class results), forward+backward replayed from ONE hipGraph.
 
-The line carries `step_ms` (one HIP event per timed step on the main stream: per-step times, median / min / max), `sensors`
-(shader clock and socket power before / during / after the timed region), `config5` (the c5 workload on the 16-bit path, hipGraph, with its
-own roofline) and `reg_only` (--no_content_loss --no_gan_loss: the one loss configuration SURVEY 8d calls jointly reachable) beside the headline.
+A plain run sets up, warms up, times exactly K steps and prints the headline line: `value` (images/s), `ms_per_step`, `step_ms` (one HIP
+event per timed step on the main stream: per-step times, median / min / max), the allocator and the workload.  --full adds everything else
+beside the headline: `sensors` (shader clock and socket power before / during / after the timed region), `roofline` (a per-launch event
+pass), `config5` (the c5 workload on the 16-bit path, hipGraph, with its own roofline), `reg_only` (--no_content_loss --no_gan_loss: the one
+loss configuration SURVEY 8d calls jointly reachable), `batch_sweep`, `allreduce_us` and `cpu_baseline`.
+--dump-outputs DIR: after the timed steps, what the last one computed as DIR/<name>.npy (dump_outputs); with the same arguments every run
+feeds the timed steps the same inputs and state (Workload.save_state), so two builds can be compared output for output.
 
 N > 1: one rank process per GPU (RCCL over xGMI).  `python bench.py --gpus N` starts the ranks itself; under
 torch.distributed.run (WORLD_SIZE set) it is one of them.  Weak scaling: the per-GPU batch is fixed; ranks draw identical z /
@@ -40,6 +44,7 @@ HBM_PEAK_GBS = 8000.0               # /opt/skills/guides/MI355X_MICROARCH.md (sp
 NOISE_STRENGTH = 0.05               # per-layer NoiseInjection weights of the benchmarked generator ("pretrained-like": non-zero)
 SCENE_ATTRS = ['dirty', 'daylight', 'night', 'sunrisesunset', 'dawndusk']
 C5_PRECISION = 'f16'                # [r5] config 5's 16-bit path: IEEE fp16 h8 maps (BASELINE configs[4]: "fp16 MFMA"); 'bf16' = rounds 3-4 (--precision bf16)
+DUMP_SAMPLE = 1 << 20               # --dump-outputs: an output with more elements (the images: 25M each) is written as this many of them
 
 
 def cpu_model():
@@ -207,6 +212,37 @@ def step_stats(ms):
                 min_ms=round(srt[0], 2), max_ms=round(srt[-1], 2))
 
 
+def sample_index(n, k, seed=0):
+    """k distinct, sorted flat positions of [0, n): one seeded position in each of k equal strata."""
+    stride = n // k
+    return np.arange(k, dtype=np.int64) * stride + np.random.RandomState(seed).randint(0, stride, k)
+
+
+def dump_outputs(out_dir, result, walk):
+    """What a caller of the timed step receives from its last call — the dict of selfcheck.run_step / capture.CapturedStep (images x0 / x1,
+    regressor predictions a0, eps, loss, the loss terms as terms_<name>, the walk gradient `grad`) and the walk after that step's Adam update
+    (walk_<parameter>) — as out_dir/<name>.npy: float64 stays float64, everything else becomes float32.  An output of more than DUMP_SAMPLE
+    elements is written flat, as its elements at sample_index(numel, DUMP_SAMPLE): at most 4 MB per array, about 9 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def add(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                add('%s_%s' % (name, k), x)
+        elif torch.is_tensor(v):
+            arrays[name] = v.detach()
+    for k, v in result.items():
+        add(k, v)
+    for k, p in walk.named_parameters():
+        add('walk_' + k.replace('.', '_'), p)
+    for name, t in sorted(arrays.items()):
+        if t.numel() > DUMP_SAMPLE:
+            t = t.reshape(-1)[torch.from_numpy(sample_index(t.numel(), DUMP_SAMPLE)).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def call_bytes(q):
     """Algorithmic HBM bytes of a conv call: input (+ its gradient mask) read once, output written once, every fused epilogue
     operand (residual, its mask, output mask, accumulate, res_sub) read once; weights / per-sample vectors are noise."""
@@ -313,6 +349,7 @@ class Workload:
         self.use_graph = use_graph
         conv.PRECISION = precision
         np.random.seed(1234)
+        torch.manual_seed(1234)                              # the generator's per-layer noise draws
         self.g = selfcheck.build_graph(resolution, self.attrs, batch * world, lr=1e-4, transform='scene' if self.c5 else 'face')
         if world > 1:
             dist.broadcast_parameters(self.g.walk.parameters())
@@ -349,6 +386,24 @@ class Workload:
             return selfcheck.run_step(self.g, zs, self.draw_alpha(), clamp=self.clamp, **flags)
         return one_step
 
+    def save_state(self):
+        """What a training step changes and a later one reads: the walk, Adam's moments and step counts, the fp16 loss scale and its flags,
+        the numpy RNG of the alpha draws and the CUDA RNG of the noise draws (the networks are fixed)."""
+        g = self.g
+        ts = list(g.walk.parameters()) + [v for st in g.optimizers.state.values() for v in st.values() if torch.is_tensor(v)]
+        if g.loss_scaler is not None:
+            ts += [g.loss_scaler.scale, g.loss_scaler.state]
+        return ts, [t.detach().clone() for t in ts], np.random.get_state(), torch.cuda.get_rng_state()
+
+    def restore_state(self, saved):
+        """Back to save_state's snapshot, in place (a captured hipGraph holds the walk's address)."""
+        ts, copies, np_state, cuda_rng = saved
+        with torch.no_grad():
+            for t, c in zip(ts, copies):
+                t.copy_(c)
+        np.random.set_state(np_state)
+        torch.cuda.set_rng_state(cuda_rng)
+
     def release(self):
         import gc
         self.captured = {}
@@ -365,11 +420,12 @@ class Workload:
                    self.batch, 'hipGraph-replayed' if graph else 'eager'))
 
 
-def warm_up(one_step, count, seconds, dev=None):
+def warm_up(one_step, count, seconds, dev=None, workload=None):
     """`count` untimed steps, then more until about `seconds` of wall time have passed (clocks, power state, allocator pools, lazily packed
     weights settle on a time scale, not a step count).  Every rank runs the SAME number of steps (a step holds the walk-gradient all-reduce: a
     per-rank time test would leave ranks in different collectives): the extra steps are computed once from the slowest rank's time for the
-    counted ones.  Returns the number of steps run."""
+    counted ones.  `workload`: its training state after the counted steps is restored after the extra ones, so that what follows starts from
+    the same state however many extra steps the clock asked for.  Returns the number of steps run."""
     import math
     from latent2im_amd import capture, dist
     t0 = time.perf_counter()
@@ -384,9 +440,12 @@ def warm_up(one_step, count, seconds, dev=None):
     if elapsed < seconds:
         per_step = max(elapsed / n if n > 1 else elapsed, 1e-3)    # (the very first step carries the lazy weight packing)
         extra = min(int(math.ceil((seconds - elapsed) / per_step)), 200)
+        saved = workload.save_state() if workload is not None else None
         for _ in range(extra):
             one_step(n)
             n += 1
+        if saved is not None:
+            workload.restore_state(saved)
         torch.cuda.synchronize()
     return n
 
@@ -475,7 +534,7 @@ def main():
                          "matrix cores (fp32-class results)")
     ap.add_argument('--hip_graph', type=int, default=None, help='1: replay forward+backward from one hipGraph (c5 default), 0: eager launches')
     ap.add_argument('--no_config5', action='store_true', help='skip the `config5` block (c5 workload, 16-bit path, hipGraph) of a c3 run')
-    ap.add_argument('--config5_steps', type=int, default=20, help='timed steps of the config5 block (20: one host hiccup of 20 ms moves the figure by 3 %, not 6)')
+    ap.add_argument('--config5_steps', type=int, default=20, help='timed steps of the config5 block (20: one host hiccup of 20 ms moves the figure by 3 %%, not 6)')
     ap.add_argument('--no_reg_only', action='store_true', help='skip the `reg_only` figures')
     ap.add_argument('--no_allreduce_rehearsal', action='store_true', help='N = 1: do not build the one-rank RCCL group for `allreduce_us` (profiler runs)')
     ap.add_argument('--direct_3x3', action='store_true', help='run 3x3 stride-1 layers on the direct implicit-GEMM kernel instead of Winograd')
@@ -487,6 +546,11 @@ def main():
                     "headline, reported as `batch_sweep`; 'none' = off")
     ap.add_argument('--sweep_steps', type=int, default=3)
     ap.add_argument('--rank_timeout_s', type=float, default=3600.0, help='--gpus N without a launcher: give up on the rank processes after this long')
+    ap.add_argument('--full', action='store_true', help='measure everything beside the headline as well: sensors, the per-launch event pass '
+                    '(roofline), reg_only, the batch sweep, config5, the all-reduce, the CPU baseline (the --no_* / --sweep / --cpu_baseline_s '
+                    'options above trim it)')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0; images as a fixed, seeded sample)')
     a = ap.parse_args()
 
     from latent2im_amd import constants, conv, dist, selfcheck, synth
@@ -516,31 +580,34 @@ def main():
     assert torch.cuda.is_available(), 'bench.py needs the MI355X'
     dev = torch.device('cuda', torch.cuda.current_device())
     sens_idx = local
+    no_sensors = a.no_sensors or not a.full
     none = dict(sclk_mhz=None, power_w=None, source='off (--no_sensors)')
-    s0 = none if a.no_sensors else gpu_sensors(sens_idx)
+    s0 = none if no_sensors else gpu_sensors(sens_idx)
     gpu_sensors.cheap = bool(s0['source'] and s0['source'].startswith('sysfs'))
     wl = Workload(a.config, precision, a.resolution, a.batch, a.attrs.split(',') if a.attrs else None, world, a.steps + a.warmup, use_graph)
     global_b = wl.global_b
     one_step = wl.stepper(reg_only=a.reg_only)
 
     # ---- the headline: W (+ time-based) warm-up steps, then EXACTLY K timed steps
-    warm_run = warm_up(one_step, a.warmup, a.warmup_s, dev)
+    warm_run = warm_up(one_step, a.warmup, a.warmup_s, dev, workload=wl)
     mem0 = torch.cuda.memory_stats()
-    sens_before = none if a.no_sensors else gpu_sensors(sens_idx)       # (the device idles for the synchronisation in front of it: expect idle clocks)
+    sens_before = none if no_sensors else gpu_sensors(sens_idx)       # (the device idles for the synchronisation in front of it: expect idle clocks)
     if a.no_gc:
         import gc
         gc.collect()
         gc.disable()
-    elapsed, step_ms, r, sens_mid = timed_steps(one_step, a.warmup, a.steps, a.max_ahead, None if a.no_sensors else sens_idx)
+    elapsed, step_ms, r, sens_mid = timed_steps(one_step, a.warmup, a.steps, a.max_ahead, None if no_sensors else sens_idx)
     if a.no_gc:
         gc.enable()
-    sens_after = none if a.no_sensors else gpu_sensors(sens_idx)
+    if a.dump_outputs and rk == 0:
+        dump_outputs(a.dump_outputs, r, wl.g.walk)
+    sens_after = none if no_sensors else gpu_sensors(sens_idx)
     mem1 = torch.cuda.memory_stats()
     per_rank_ms = [round(t / a.steps * 1e3, 3) for t in dist.gather_floats(elapsed)]
     elapsed = dist.max_over_ranks(elapsed, dev)
     loss_value = float(r['loss'])
     wgrad = next(iter(wl.g.walk.parameters()))
-    allreduce_us = dist.time_allreduce(wgrad.detach())
+    allreduce_us = dist.time_allreduce(wgrad.detach()) if a.full else None
     allreduce_note = ('median of 100 synchronised all-reduces of a walk-gradient-shaped tensor (%d bytes) over the %s process group'
                       % (wgrad.numel() * 4, torch.distributed.get_backend())) if allreduce_us is not None else None
     alloc = dict(reserved_GB_before=round(mem0['reserved_bytes.all.current'] / 1e9, 2), reserved_GB_after=round(mem1['reserved_bytes.all.current'] / 1e9, 2),
@@ -550,13 +617,13 @@ def main():
     # ---- roofline of the conv kernels (every rank repeats the steps: the walk-gradient all-reduce is inside a step; rank 0 reports)
     prof, t_events, ev_steps = None, None, None
     n_ev = min(a.event_steps, a.steps)
-    if not a.no_kernel_events:
+    if a.full and not a.no_kernel_events:
         prof, t_events, ev_steps = event_pass(wl, wl.stepper(reg_only=a.reg_only, graph=False), a.warmup, n_ev)
     dist.barrier()
 
     # ---- reg-only loss (train.py:174-176 --no_content_loss --no_gan_loss) on the same graph
     reg = None
-    if not a.no_reg_only and not a.reg_only:
+    if a.full and not a.no_reg_only and not a.reg_only:
         reg = {precision: dict(quick_rate(wl.stepper(reg_only=True), 5, global_b, dev, a.max_ahead),
                                workload=wl.describe(True, a.noise_strength, use_graph))}
         if not a.no_kernel_events:                           # [r5] the reg-only loss is the configuration SURVEY 8(d) calls jointly reachable: its own roofline
@@ -565,7 +632,7 @@ def main():
 
     # ---- batch sweep (the BASELINE metric is quoted over a batch sweep): the same eager step at other per-GPU batches, every rank
     sweep = None
-    if a.sweep and a.sweep not in ('0', 'none', 'off'):
+    if a.full and a.sweep and a.sweep not in ('0', 'none', 'off'):
         import gc
         wl.captured = {}
         gc.collect()
@@ -594,7 +661,7 @@ def main():
 
     # ---- config 5 (BASELINE configs[4] per-GPU shape) beside the headline: scene attributes, clamp flow, 16-bit path, hipGraph-replayed
     cfg5 = None
-    if not c5 and not a.no_config5 and a.resolution == 1024:
+    if a.full and not c5 and not a.no_config5 and a.resolution == 1024:
         wkey3, desc3 = wl.key(a.reg_only), wl.describe(a.reg_only, a.noise_strength, use_graph)
         wl.release()
         w5 = Workload('c5', C5_PRECISION, a.resolution, a.batch, None, world, a.config5_steps + 2, True)
@@ -623,7 +690,7 @@ def main():
     else:
         wkey3, desc3 = wl.key(a.reg_only), wl.describe(a.reg_only, a.noise_strength, use_graph)
 
-    if world == 1 and allreduce_us is None and not a.no_allreduce_rehearsal:
+    if a.full and world == 1 and allreduce_us is None and not a.no_allreduce_rehearsal:
         allreduce_us, allreduce_note = one_rank_allreduce_us(wgrad)
     if rk != 0:
         dist.shutdown()
@@ -660,7 +727,10 @@ def main():
                roofline=roof, config5=cfg5, reg_only=reg, batch_sweep=sweep, loss_scale=ls_main,
                ranks_seen=ranks, per_rank_ms_per_step=per_rank_ms, allreduce_us=None if allreduce_us is None else round(allreduce_us, 1),
                allreduce_note=allreduce_note)
-    if world == 1 and a.cpu_baseline_s > 0:
+    if not a.full:                                       # the plain run's line: the headline and what its timed steps recorded
+        for k in ('sensors', 'roofline', 'config5', 'reg_only', 'batch_sweep', 'allreduce_us', 'allreduce_note'):
+            del out[k]
+    elif world == 1 and a.cpu_baseline_s > 0:
         out['cpu_baseline'] = cpu_baseline(a.resolution, len(wkey3[2]), a.cpu_baseline_s, full_loss=not a.reg_only, clamp=c5)
     else:
         out['cpu_baseline'] = None
