@@ -1,4 +1,5 @@
-"""Drop-in for the attribute-preservation half of the reference's ``eval.py``:
+"""Drop-in for the reference's ``eval.py`` (attribute preservation; identity preservation when a facenet checkpoint is given by
+``--facenet_ckpt`` / constants.facenet_path, see ``--identity``):
 
 python eval.py models_celeba/stylegan_v2_real_face_linear_lr0.0001_l2_w/opt.yml --gpu 0 --noise_seed 0 --num_samples 10 \
     --num_panels 10 --attrPath ./dataset/attributes_celeba.txt --target_attrList Smiling \

@@ -436,10 +436,29 @@ int l2i_adam_guarded_f32(float* p, const float* g, float* m, float* v, float* st
 int l2i_reg_bce_f32(double* loss, float* preds, float* g_feat, const float* feat, const float* fc_w, const float* fc_b, const int64_t* cols,
                     const void* target, int target_f64, int B, int F, int K, float eps, void* stream);
 
+/* [ABI 8] The identity-preservation half of eval.py (csrc/l2i_face.hip; eval.py:170-209, latent2im_amd/facenet.py).
+ * l2i_face_resize_f32: the generator's image -> the face network's input, bit-identical to the reference's clip_ims followed by PIL's
+ *   Image.resize((OW, OH)) (bicubic a = -0.5, antialiased): x [planes, H, W] fp32 in [-1, 1] is quantised with clip_ims' float32 arithmetic
+ *   (np.uint8(np.clip(((x + 1) / 2.0) * 255, 0, 255))), resized horizontally to a uint8 intermediate, then vertically; y [planes, OH, OW] fp32
+ *   holds the resulting 0..255 bytes.  Each pass is PIL's fixed-point form: acc = 2^21 + sum_t q[first + t] * coef[o * k + t] (int32),
+ *   clip(acc >> 22, 0, 255).  xbounds [OW, 2] / ybounds [OH, 2] = (first input pixel, tap count) and xcoef [OW, xk] / ycoef [OH, yk] int32 are
+ *   PIL's tables of the axis (22-bit coefficients normalised in double; latent2im_amd/facenet.py:resize_tables), device pointers.  Equal sizes
+ *   give identity tables: the image is a copy.  Built for inputs <= 4096 and outputs <= 256 pixels a side with <= 256 taps, where the input
+ *   rows 16 output rows read fit 48 KiB of LDS as bytes (square inputs up to ~2048 onto 160); other shapes return L2I_E_UNSUPPORTED.
+ * l2i_face_head_f32: InceptionResnetV1's head for the whole batch: emb[b, :] = F.normalize(w_t^T mean_hw(feat[b]) + bias) (eps 1e-12), feat
+ *   [B, C, HW], w_t [C][E] = last_linear.weight^T with last_bn's eval-mode scale folded into its columns, bias [E] = last_bn's folded shift;
+ *   emb [B, E] fp32.  npairs > 0: B == 2 * npairs, rows p and p + npairs are an (edited, original) pair and dist[p] (float64) =
+ *   scipy.spatial.distance.cosine of the two embeddings taken as float64 vectors (1 - uv / sqrt(uu vv), float64 sums, clipped to [0, 2]);
+ *   npairs = 0: dist is not touched (may be NULL).  Built for C <= 2048 and E <= 512; other shapes return L2I_E_UNSUPPORTED. */
+int l2i_face_resize_f32(float* y, const float* x, int64_t planes, int H, int W, int OH, int OW, const int32_t* xbounds, const int32_t* xcoef,
+                        int xk, const int32_t* ybounds, const int32_t* ycoef, int yk, void* stream);
+int l2i_face_head_f32(float* emb, double* dist, const float* feat, const float* w_t, const float* bias, int B, int C, int HW, int E, int npairs,
+                      void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
- * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
-#define L2I_ABI_VERSION 7
+ * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
+#define L2I_ABI_VERSION 8
 int l2i_abi_version(void);
 int l2i_sizeof_conv_params(void);       /* sizeof(struct l2i_conv_params) of THIS build */
 

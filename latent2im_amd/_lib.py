@@ -111,6 +111,8 @@ _SIGNATURES = {
     'l2i_modulate_planes_multi_h8': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     'l2i_segmented_matvec_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     'l2i_reg_bce_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    'l2i_face_resize_f32': (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
+    'l2i_face_head_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_nonfinite_flag_f32': (c_i, [c_p, c_l, c_p, c_p]),
     'l2i_adam_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
@@ -122,7 +124,7 @@ _SIGNATURES = {
 for _n in [k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i_cast_f32_to_h8', 'l2i_cast_h8_to_f32')]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
-ABI_VERSION = 7          # L2I_ABI_VERSION of include/l2i.h this binding mirrors
+ABI_VERSION = 8          # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -16,11 +16,14 @@ reg_json = None
 reg_path = '/path/003_dict.model'
 g_path = '/path/550000.pt'
 vgg_path = ''
+# eval.py's face network (facenet_pytorch InceptionResnetV1; the reference downloads its vggface2 weights): that plain state_dict file.  eval
+# --identity auto runs the identity half only when it exists; --facenet_ckpt overrides it
+facenet_path = ''
 # BASELINE config 1 (graphs/pggan): the in-repo PGGAN-256 generator checkpoint ({'G': state_dict}, transform_base.py:578-590) and its resolution
 pg_path = '/path/280000_dict.model'
 PG_RESOLUTION = 256
 
-SYNTH_SEED_G, SYNTH_SEED_D, SYNTH_SEED_R, SYNTH_SEED_V = 100, 200, 300, 400
+SYNTH_SEED_G, SYNTH_SEED_D, SYNTH_SEED_R, SYNTH_SEED_V, SYNTH_SEED_F = 100, 200, 300, 400, 600
 # per-layer NoiseInjection weights of the synthetic generator: 0 like a fresh reference Generator (networks.py:279; parity tests), > 0
 # like a trained one (bench.py: the per-layer N(0,1) draw of networks.py:281-286 is then inside the timed region)
 SYNTH_NOISE_STRENGTH = 0.0

@@ -1,0 +1,195 @@
+// l2i_face.hip — the identity-preservation half of eval.py on the device (gfx950).  Entry points l2i_face_resize_f32, l2i_face_head_f32.
+//
+// Reference: eval.py:170-198 — every bucket entry's edited and original image is quantised (clip_ims: np.uint8(np.clip(((x + 1) / 2.0) * 255,
+// 0, 255)) in float32), resized by PIL's Image.resize((160, 160)) (bicubic, antialiased), handed to facenet_pytorch's InceptionResnetV1 as
+// raw 0..255 floats and compared by scipy's cosine distance.  Here the whole batch stays on the device:
+//   * l2i_face_resize_f32: quantisation + PIL's two separable fixed-point passes (Resample.c: 22-bit coefficients, int32 accumulation from
+//     2^21, >> 22 and clip to 0..255 after EACH pass, i.e. a uint8 intermediate).  The coefficient / bound tables are PIL's, computed by the
+//     caller in double (latent2im_amd/facenet.py:resize_tables); the kernel does integer MACs only, so the result is PIL's bit for bit.  One
+//     block makes FR_ROWS output rows of one plane: the horizontal pass of the input rows those rows read goes to LDS (uint8), then the
+//     vertical pass reads LDS.
+//   * l2i_face_head_f32: the network's head (avgpool_1a, last_linear with last_bn folded in by the caller, F.normalize) for the whole batch,
+//     and optionally the cosine distance of every (edited, original) pair in float64.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include "l2i.h"
+#include "l2i_internal.h"
+
+namespace l2i_face {
+
+constexpr int FR_ROWS = 16;            // output rows per block
+constexpr int FR_LDS = 48 * 1024;      // bytes of uint8 intermediate rows per block
+constexpr int FR_THREADS = 256;
+
+// clip_ims in float32 with numpy's operation order (x + 1, / 2, * 255; / 2 is exact), np.clip, then the truncating uint8 cast
+__device__ __forceinline__ int quant8(float v) {
+    float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.0f), 0.5f), 255.0f);
+    t = fminf(fmaxf(t, 0.0f), 255.0f);          // (NaN -> 0)
+    return (int)t;
+}
+
+// Resample.c clip8: the 22-bit fixed-point sum back to a byte
+__device__ __forceinline__ int clip8(int acc) {
+    if (acc >= (1 << 30)) return 255;
+    if (acc <= 0) return 0;
+    return acc >> 22;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void face_resize_kernel(float* __restrict__ y, const float* __restrict__ x, int tiles, int H, int W, int OH,
+                                                                 int OW, const int32_t* __restrict__ xb, const int32_t* __restrict__ xc, int xk,
+                                                                 const int32_t* __restrict__ yb, const int32_t* __restrict__ yc, int yk) {
+    __shared__ uint8_t mid[FR_LDS];
+    const int64_t plane = blockIdx.x / tiles;
+    const int tile = blockIdx.x - (int)(plane * tiles);
+    const int oy0 = tile * FR_ROWS, oy1 = min(oy0 + FR_ROWS, OH);
+    const int r0 = yb[2 * oy0];
+    const int r1 = yb[2 * (oy1 - 1)] + yb[2 * (oy1 - 1) + 1];            // bounds are non-decreasing in the output index
+    const int nrows = min(r1 - r0, FR_LDS / OW);                         // (the host bounds the span; never write past the buffer)
+    const float* xp = x + plane * (int64_t)H * W;
+    for (int i = threadIdx.x; i < nrows * OW; i += FR_THREADS) {
+        const int r = i / OW, ox = i - r * OW;
+        const int iy = r0 + r;
+        const int xmin = xb[2 * ox], n = min(xb[2 * ox + 1], xk);
+        const int32_t* k = xc + (int64_t)ox * xk;
+        int acc = 1 << 21;
+        if (iy >= 0 && iy < H) {
+            const float* row = xp + (int64_t)iy * W;
+            for (int t = 0; t < n; ++t) {
+                const int xi = xmin + t;
+                if (xi >= 0 && xi < W) acc += quant8(row[xi]) * k[t];
+            }
+        }
+        mid[i] = (uint8_t)clip8(acc);
+    }
+    __syncthreads();
+    float* yp = y + plane * (int64_t)OH * OW;
+    for (int i = threadIdx.x; i < (oy1 - oy0) * OW; i += FR_THREADS) {
+        const int oy = oy0 + i / OW, ox = i - (i / OW) * OW;
+        const int ymin = yb[2 * oy] - r0, n = min(yb[2 * oy + 1], yk);
+        const int32_t* k = yc + (int64_t)oy * yk;
+        int acc = 1 << 21;
+        for (int t = 0; t < n; ++t) {
+            const int r = ymin + t;
+            if (r >= 0 && r < nrows) acc += (int)mid[r * OW + ox] * k[t];
+        }
+        yp[(int64_t)oy * OW + ox] = (float)clip8(acc);
+    }
+}
+
+constexpr int HEAD_THREADS = 256;
+constexpr int HEAD_MAXC = 2048;
+constexpr int HEAD_MAXE = 2 * HEAD_THREADS;
+
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {             // fixed order: deterministic
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Block j makes samples s[0], s[1]: (j, j + npairs) when pairs are asked for, else (2j, 2j + 1).
+__global__ __launch_bounds__(HEAD_THREADS) void face_head_kernel(float* __restrict__ emb, double* __restrict__ dist, const float* __restrict__ feat,
+                                                                 const float* __restrict__ w_t, const float* __restrict__ bias, int B, int C, int HW,
+                                                                 int E, int npairs) {
+    __shared__ float pooled[2][HEAD_MAXC];
+    __shared__ float redf[4];
+    __shared__ double redd[4];
+    const int tid = threadIdx.x;
+    int s[2];
+    if (npairs > 0) {
+        s[0] = blockIdx.x;
+        s[1] = blockIdx.x + npairs;
+    } else {
+        s[0] = 2 * blockIdx.x;
+        s[1] = 2 * blockIdx.x + 1 < B ? 2 * blockIdx.x + 1 : -1;
+    }
+    const float inv_hw = 1.0f / (float)HW;
+    for (int j = 0; j < 2; ++j) {                                  // avgpool_1a
+        if (s[j] < 0) {
+            for (int c = tid; c < C; c += HEAD_THREADS) pooled[j][c] = 0.f;
+            continue;
+        }
+        const float* f = feat + (int64_t)s[j] * C * HW;
+        for (int c = tid; c < C; c += HEAD_THREADS) {
+            float a = 0.f;
+            for (int p = 0; p < HW; ++p) a += f[(int64_t)c * HW + p];
+            pooled[j][c] = a * inv_hw;
+        }
+    }
+    __syncthreads();
+    float z[2][2] = {{0.f, 0.f}, {0.f, 0.f}};                      // [sample][output tid, tid + 256]
+    const int e0 = tid, e1 = tid + HEAD_THREADS;
+    for (int c = 0; c < C; ++c) {                                  // last_linear (+ folded last_bn scale): w_t is [C][E], coalesced in e
+        const float w0 = e0 < E ? w_t[(int64_t)c * E + e0] : 0.f;
+        const float w1 = e1 < E ? w_t[(int64_t)c * E + e1] : 0.f;
+        const float p0 = pooled[0][c], p1 = pooled[1][c];
+        z[0][0] += p0 * w0;
+        z[0][1] += p0 * w1;
+        z[1][0] += p1 * w0;
+        z[1][1] += p1 * w1;
+    }
+    for (int j = 0; j < 2; ++j) {
+        z[j][0] = e0 < E ? z[j][0] + bias[e0] : 0.f;
+        z[j][1] = e1 < E ? z[j][1] + bias[e1] : 0.f;
+    }
+    for (int j = 0; j < 2; ++j) {                                  // F.normalize(p=2, eps=1e-12)
+        const float ss = block_sum(z[j][0] * z[j][0] + z[j][1] * z[j][1], redf);
+        const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+        z[j][0] = z[j][0] / nrm;
+        z[j][1] = z[j][1] / nrm;
+        if (s[j] >= 0) {
+            if (e0 < E) emb[(int64_t)s[j] * E + e0] = z[j][0];
+            if (e1 < E) emb[(int64_t)s[j] * E + e1] = z[j][1];
+        }
+    }
+    if (npairs > 0) {                                              // scipy.spatial.distance.cosine on the float64 embeddings
+        const double a0 = z[0][0], a1 = z[0][1], b0 = z[1][0], b1 = z[1][1];
+        const double uv = block_sum(a0 * b0 + a1 * b1, redd);
+        const double uu = block_sum(a0 * a0 + a1 * a1, redd);
+        const double vv = block_sum(b0 * b0 + b1 * b1, redd);
+        if (tid == 0) {
+            double d = 1.0 - uv / sqrt(uu * vv);
+            dist[blockIdx.x] = d < 0.0 ? 0.0 : (d > 2.0 ? 2.0 : d);
+        }
+    }
+}
+
+}  // namespace l2i_face
+
+extern "C" int l2i_face_resize_f32(float* y, const float* x, int64_t planes, int H, int W, int OH, int OW, const int32_t* xbounds,
+                                   const int32_t* xcoef, int xk, const int32_t* ybounds, const int32_t* ycoef, int yk, void* stream) {
+    using namespace l2i_face;
+    if (!y || !x || !xbounds || !xcoef || !ybounds || !ycoef || planes < 1 || H < 1 || W < 1 || OH < 1 || OW < 1)
+        return l2i_set_error(L2I_E_ARG, "l2i_face_resize_f32: null pointer or empty shape");
+    if (H > 4096 || W > 4096 || OH > 256 || OW > 256 || xk < 1 || yk < 1 || xk > 256 || yk > 256)
+        return l2i_set_error(L2I_E_UNSUPPORTED, "l2i_face_resize_f32: built for inputs <= 4096 and outputs <= 256 pixels a side, <= 256 taps");
+    // input rows one block's FR_ROWS output rows read: at most (FR_ROWS - 1) * H / OH between their first taps, plus one support
+    const int64_t span = ((int64_t)(FR_ROWS - 1) * H + OH - 1) / OH + yk + 1;
+    if (span * OW > FR_LDS)
+        return l2i_set_error(L2I_E_UNSUPPORTED, "l2i_face_resize_f32: the uint8 rows of one block's vertical support exceed its LDS buffer");
+    const int tiles = (OH + FR_ROWS - 1) / FR_ROWS;
+    if (planes * tiles > 0x7FFFFFFF) return l2i_set_error(L2I_E_UNSUPPORTED, "l2i_face_resize_f32: too many planes");
+    hipLaunchKernelGGL(face_resize_kernel, dim3((unsigned)(planes * tiles)), dim3(FR_THREADS), 0, (hipStream_t)stream, y, x, tiles, H, W, OH, OW,
+                       xbounds, xcoef, xk, ybounds, ycoef, yk);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}
+
+extern "C" int l2i_face_head_f32(float* emb, double* dist, const float* feat, const float* w_t, const float* bias, int B, int C, int HW, int E,
+                                 int npairs, void* stream) {
+    using namespace l2i_face;
+    if (!emb || !feat || !w_t || !bias || B < 1 || C < 1 || HW < 1 || E < 1 || npairs < 0)
+        return l2i_set_error(L2I_E_ARG, "l2i_face_head_f32: null pointer or empty shape");
+    if (npairs > 0 && (B != 2 * npairs || !dist))
+        return l2i_set_error(L2I_E_ARG, "l2i_face_head_f32: pairs need B == 2 * npairs and a dist buffer");
+    if (C > HEAD_MAXC || E > HEAD_MAXE)
+        return l2i_set_error(L2I_E_UNSUPPORTED, "l2i_face_head_f32: built for C <= 2048 pooled channels and E <= 512 embedding features");
+    const int blocks = npairs > 0 ? npairs : (B + 1) / 2;
+    hipLaunchKernelGGL(face_head_kernel, dim3(blocks), dim3(HEAD_THREADS), 0, (hipStream_t)stream, emb, dist, feat, w_t, bias, B, C, HW, E, npairs);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}

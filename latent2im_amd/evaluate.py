@@ -1,19 +1,25 @@
-"""Evaluation driver: attribute preservation of a trained walk (reference eval.py:21-239).
+"""Evaluation driver: attribute and identity preservation of a trained walk (reference eval.py:21-239).
 
 For every batch and every target attribute the batch is edited at ``num_panels`` alphas, every sample is bucketed by how
-far the target attribute moved (|d| <= 0.3 / 0.6 / 1, graph.attribute_change_bucket) and the metric is the mean absolute
-change of the 39 OTHER regressor outputs per bucket.  The identity-preservation half of the reference (facenet
-InceptionResnetV1 cosine similarity, eval.py:27-31,170-189) needs a third-party network that is not part of this path and
-is not built.
+far the target attribute moved (|d| <= 0.3 / 0.6 / 1, graph.attribute_change_bucket) and the attribute metric is the mean
+absolute change of the 39 OTHER regressor outputs per bucket.
 
-Reference quirk kept: eval.py:203-209 sit OUTSIDE the batch loop, so only the buckets of the LAST batch / LAST target
-attribute enter the printed metric; ``all_batches=True`` accumulates every batch instead."""
+The identity metric (eval.py:27-32,170-209; ``--identity {auto,on,off}``) embeds every bucket entry's edited and original
+image with the face network (latent2im_amd/facenet.py: facenet_pytorch's InceptionResnetV1 restated on the HIP kernels, its
+checkpoint at constants.facenet_path / ``--facenet_ckpt``) and prints, per non-empty bucket, 1 - the mean cosine distance.
+``auto`` (the default) runs it only when the face checkpoint exists; ``on`` also accepts synthetic weights where the run's
+opt.yml allows them.  Its input is the reference's: clip_ims, PIL's bicubic resize to 160^2, raw 0..255 values (no
+fixed_image_standardization), made on the device bit for bit (l2i_face_resize_f32).
+
+Reference quirks kept: eval.py:203-209 sit OUTSIDE the batch loop, so only the buckets of the LAST batch / LAST target
+attribute enter the printed attribute metric (``all_batches=True`` accumulates every batch instead); the identity distances
+(``sim``) are never reset, so every batch and every target attribute enters the identity metric."""
 import os
 from collections import OrderedDict
 
 import numpy as np
 
-from . import constants, dist, hostutil
+from . import constants, dist, facenet, hostutil
 from .vis import VisOptions
 
 
@@ -31,8 +37,8 @@ def attribute_preservation(multi_attrs, original_attrs, index_):
     return results, results_avg
 
 
-def main(argv=None, all_batches=False):
-    from . import graph as graph_mod
+def eval_options():
+    """eval.py's parser: VisOptions + the reference's options + ``--identity`` / ``--facenet_ckpt``."""
     v = VisOptions()
     v.initialize()
     v.parser.add_argument('--num_samples', type=int, default=10)
@@ -43,6 +49,16 @@ def main(argv=None, all_batches=False):
     v.parser.add_argument('--target_attrList', type=str, default=None)
     v.parser.add_argument('--trainEmbed', action='store_true')
     v.parser.add_argument('--updateGAN', action='store_true')
+    v.parser.add_argument('--identity', choices=('auto', 'on', 'off'), default='auto',
+                          help='identity preservation (facenet cosine similarity): auto = when the face checkpoint exists')
+    v.parser.add_argument('--facenet_ckpt', type=str, default=None,
+                          help='facenet_pytorch InceptionResnetV1 state_dict (vggface2); default constants.facenet_path')
+    return v
+
+
+def main(argv=None, all_batches=False):
+    from . import graph as graph_mod
+    v = eval_options()
     opt, conf = v.parse(argv)
     dist.select_gpu(opt.gpu)                         # before the first torch.cuda call (vis_w.py / eval.py set CUDA_VISIBLE_DEVICES)
     dist.init_from_env()
@@ -54,7 +70,13 @@ def main(argv=None, all_batches=False):
         constants.BATCH_SIZE = conf.batch_size
     output_dir = opt.output_dir if opt.output_dir else os.path.join(conf.output_dir, 'images')
     os.makedirs(output_dir, exist_ok=True)
+    face_path = constants.facenet_path if opt.facenet_ckpt is None else opt.facenet_ckpt
+    want_identity = facenet.identity_mode(opt.identity, face_path)        # (decided before the graph is built: `on` without weights raises)
     g = graph_mod.find_model_using_name(conf.model, conf.transform)(**hostutil.set_graph_kwargs(conf))
+    face_net = None
+    if want_identity:
+        face_net, face_src = facenet.load(face_path, device=g.device)
+        print('Load face recognition model', face_src)
     g.load_multi_models(opt.save_path_w, None, trainEmbed=opt.trainEmbed, updateGAN=opt.updateGAN)
     graph_inputs = hostutil.graph_input(g, opt.num_samples, seed=opt.noise_seed)
     epochs = opt.save_path_w.split('/')[-1].split('_')[2]
@@ -75,6 +97,7 @@ def main(argv=None, all_batches=False):
     print('target_attrList: ', target_attrList)
 
     multi_attrs, original_attrs = [[], [], []], [[], [], []]
+    sim = [[], [], []]
     multi_attr = org_attr = None
     index_ = None
     bs = constants.BATCH_SIZE
@@ -86,9 +109,16 @@ def main(argv=None, all_batches=False):
                                    min_alpha=opt.min_alpha, wgt=True)
         for t in target_attrList:
             index_ = attrTable[t]
-            multi_attr, org_attr, _, _ = g.vis_multi_image_batch_alphas_compute_multi_attr(
-                batch, new_filename + '_attr_%s' % t, alphas_to_graph=ag, alphas_to_target=at, layers=layers, batch_start=s.start,
-                wgt=False, wmask=False, trainEmbed=opt.trainEmbed, computeL2=False, index_=index_)
+            if face_net is None:
+                multi_attr, org_attr, _, _ = g.vis_multi_image_batch_alphas_compute_multi_attr(
+                    batch, new_filename + '_attr_%s' % t, alphas_to_graph=ag, alphas_to_target=at, layers=layers, batch_start=s.start,
+                    wgt=False, wmask=False, trainEmbed=opt.trainEmbed, computeL2=False, index_=index_)
+            else:
+                multi_attr, org_attr, _, _, dists = g.vis_multi_image_batch_alphas_compute_multi_attr_identity(
+                    batch, new_filename + '_attr_%s' % t, alphas_to_graph=ag, alphas_to_target=at, layers=layers, batch_start=s.start,
+                    face_net=face_net, wgt=False, wmask=False, trainEmbed=opt.trainEmbed, computeL2=False, index_=index_)
+                for k in range(3):
+                    sim[k] += dists[k]
             if all_batches:
                 for k in range(3):
                     multi_attrs[k] += multi_attr[k]
@@ -97,6 +127,11 @@ def main(argv=None, all_batches=False):
         for k in range(3):
             multi_attrs[k] += multi_attr[k]
             original_attrs[k] += org_attr[k]
+    out = {}
+    if face_net is not None:
+        identity, identity_avg = facenet.identity_preservation(sim)
+        print('[IDENTITY PRESERVATION] Results on 3 epsilon segments', ['%.4f' % i for i in identity_avg])
+        out = dict(identity=identity, identity_avg=identity_avg, identity_bucket_sizes=[len(d) for d in sim])
     results, results_avg = attribute_preservation(multi_attrs, original_attrs, index_)
     print('[ATTRIBUTE PRESERVATION] Results on 3 epsilon segments', ['%.4f' % i for i in results_avg])
-    return dict(results=results, results_avg=results_avg, bucket_sizes=[len(m) for m in multi_attrs], index_=index_)
+    return dict(results=results, results_avg=results_avg, bucket_sizes=[len(m) for m in multi_attrs], index_=index_, **out)

@@ -517,8 +517,21 @@ class TransformGraph:
         buckets by how far the TARGET attribute moved: |d| <= 0.3, <= 0.6, <= 1 (samples that moved further are dropped).
         Returns (multi_attr, attri_org, imgs, orgs): four lists of three lists (edited attrs [40], original attrs [40],
         uint8 edited image [3,R,R], uint8 original image)."""
+        return self._compute_multi_attr(graph_inputs, alphas_to_graph, alphas_to_target, layers, name, trainEmbed, given_w, index_)[:4]
+
+    def vis_multi_image_batch_alphas_compute_multi_attr_identity(self, graph_inputs, filename, alphas_to_graph, alphas_to_target,
+                                                                 batch_start, face_net, layers=None, name=None, wgt=False, wmask=False,
+                                                                 trainEmbed=False, computeL2=False, given_w=None, index_=None):
+        """Both halves of eval.py from one generator pass per alpha: what vis_multi_image_batch_alphas_compute_multi_attr returns, plus
+        ``dists`` (three lists, one per bucket, in the order of the other lists): the float64 cosine distance between the face embeddings of
+        each bucket entry's edited and original image (eval.py:170-189).  ``face_net`` (facenet.InceptionResnetV1) embeds the whole batch
+        on the device, from the generator's output: resize, network and distance never see a host copy of the images."""
+        return self._compute_multi_attr(graph_inputs, alphas_to_graph, alphas_to_target, layers, name, trainEmbed, given_w, index_,
+                                        face_net=face_net)
+
+    def _compute_multi_attr(self, graph_inputs, alphas_to_graph, alphas_to_target, layers, name, trainEmbed, given_w, index_, face_net=None):
         zs_batch = graph_inputs['z']
-        multi_attr, attri_org, imgs, orgs = [[], [], []], [[], [], []], [[], [], []], [[], [], []]
+        multi_attr, attri_org, imgs, orgs, dists = [[], [], []], [[], [], []], [[], [], []], [[], [], []], [[], [], []]
         index_list = [index_] if type(index_) == int else index_
         with torch.no_grad():
             for ag1, at1 in zip(alphas_to_graph, alphas_to_target):
@@ -527,6 +540,7 @@ class TransformGraph:
                                                                   index_=index_)
                 pred_attr = self.regressor(best_im_out).detach().cpu().numpy()       # [N, 40]
                 org = self.regressor(out_zs).detach().cpu().numpy()
+                face_d = face_net.pair_distances(best_im_out, out_zs)[0].cpu().numpy() if face_net is not None else None
                 best_im_out = self.clip_ims(best_im_out.detach().cpu().numpy())
                 out_zs = self.clip_ims(out_zs.cpu().numpy())
                 bucket = attribute_change_bucket(pred_attr[:, index_list[0]], org[:, index_list[0]])
@@ -537,7 +551,9 @@ class TransformGraph:
                         attri_org[k].append(org[i])
                         imgs[k].append(best_im_out[i])
                         orgs[k].append(out_zs[i])
-        return multi_attr, attri_org, imgs, orgs
+                        if face_d is not None:
+                            dists[k].append(float(face_d[i]))
+        return multi_attr, attri_org, imgs, orgs, dists
 
     def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7):
         raise NotImplementedError('Subclass should implement vis_image_batch')

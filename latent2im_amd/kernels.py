@@ -217,3 +217,32 @@ def segmented_matvec(out, inp, w, segs, block_seg, nblocks, B, in2=None, bias=No
                                             _lib.stream_ptr()), 'l2i_segmented_matvec_f32')
     return out
 
+
+
+def face_resize(x, xbounds, xcoef, ybounds, ycoef):
+    """l2i_face_resize_f32: x [B, C, H, W] fp32 in [-1, 1] -> clip_ims + PIL's resize to [B, C, OH, OW] (fp32 bytes 0..255).  The int32
+    tables [O, 2] / [O, k] of each axis are PIL's (facenet.resize_tables), on the device."""
+    lib = _lib.load()
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    oh, ow = ybounds.shape[0], xbounds.shape[0]
+    assert xcoef.shape[0] == ow and ycoef.shape[0] == oh and all(t.dtype == torch.int32 and t.is_contiguous() for t in (xbounds, xcoef, ybounds, ycoef))
+    y = torch.empty(b, c, oh, ow, device=x.device, dtype=torch.float32)
+    _lib.check(lib.l2i_face_resize_f32(_lib.fptr(y), _lib.fptr(x), b * c, h, w, oh, ow, _lib.ptr(xbounds), _lib.ptr(xcoef), xcoef.shape[1],
+                                       _lib.ptr(ybounds), _lib.ptr(ycoef), ycoef.shape[1], _lib.stream_ptr()), 'l2i_face_resize_f32')
+    return y
+
+
+def face_head(feat, w_t, bias, npairs=0):
+    """l2i_face_head_f32: feat [B, C, h, w] -> (unit embeddings [B, E], float64 cosine distances [npairs] of rows (p, p + npairs), or None).
+    w_t [C, E] / bias [E]: last_linear with last_bn folded in (facenet.InceptionResnetV1)."""
+    lib = _lib.load()
+    feat = feat.contiguous()
+    b, c = feat.shape[:2]
+    e = w_t.shape[1]
+    assert w_t.shape[0] == c and bias.numel() == e
+    emb = torch.empty(b, e, device=feat.device, dtype=torch.float32)
+    dist = torch.empty(npairs, device=feat.device, dtype=torch.float64) if npairs else None
+    _lib.check(lib.l2i_face_head_f32(_lib.fptr(emb), _lib.ptr(dist), _lib.fptr(feat), _lib.fptr(w_t), _lib.fptr(bias), b, c,
+                                     feat[0, 0].numel(), e, int(npairs), _lib.stream_ptr()), 'l2i_face_head_f32')
+    return emb, dist
