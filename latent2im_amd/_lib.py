@@ -121,7 +121,8 @@ _SIGNATURES = {
 }
 
 # [r5] every h8 entry point exists twice: bf16 elements (the name as is) and IEEE fp16 elements (suffix _f16), same signatures
-for _n in [k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i_cast_f32_to_h8', 'l2i_cast_h8_to_f32')]:
+_F16_TWINS = frozenset(k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i_cast_f32_to_h8', 'l2i_cast_h8_to_f32'))
+for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
 ABI_VERSION = 8          # L2I_ABI_VERSION of include/l2i.h this binding mirrors
@@ -198,6 +199,17 @@ def load():
 def check(rc, what):
     if rc != 0:
         raise L2IError('%s failed (%d): %s' % (what, rc, load().l2i_last_error().decode()))
+
+
+def call(name, *args, dtype=None, stream=None):
+    """Enqueue entry point ``name`` with ``args`` on the current stream, or on ``stream``: for h8 maps of ``dtype`` float16 its IEEE fp16 twin.
+    Returns the name of the entry it called; raises L2IError naming it when it fails."""
+    if dtype is torch.float16 and name in _F16_TWINS:
+        name += '_f16'
+    rc = getattr(_lib or load(), name)(*args, stream_ptr() if stream is None else stream)
+    if rc:
+        check(rc, name)
+    return name
 
 
 def stream_ptr():

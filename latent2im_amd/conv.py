@@ -122,6 +122,14 @@ def pack_weight_wino4(w):
     return torch.cat([a, b], dim=2).float().contiguous()
 
 
+def _bf16x3_planes(self):
+    """(hi, lo) bf16 planes of ``self.w_src`` on the device of ``self.w``, built on first use (Launch, FusedTransposed)."""
+    if self.w16 is None and self.w_src is not None:
+        hi, lo = pack_weight_bf16x3(self.w_src)
+        self.w16 = (hi.to(self.w.device), lo.to(self.w.device))
+    return self.w16
+
+
 class Launch:
     """One call of the kernel: a stride-1/2 correlation writing every (oy_step, ox_step)-th output pixel."""
     __slots__ = ('w', 'cin', 'cout', 'kh', 'kw', 'stride', 'pad_y', 'pad_x', 'step', 'off_y', 'off_x', 'w16', 'w_src', 'wino', 'w4', 'wino4')
@@ -140,11 +148,7 @@ class Launch:
         self.wino4 = None                                      # F(4x4,3x3) pack, built on first use
         self.w_src = torch.as_tensor(w_oihw, dtype=torch.float32) if (self.cin % 8 == 0 and self.kh <= 3 and self.kw <= 3) else None
 
-    def bf16x3_planes(self):
-        if self.w16 is None and self.w_src is not None:
-            hi, lo = pack_weight_bf16x3(self.w_src)
-            self.w16 = (hi.to(self.w.device), lo.to(self.w.device))
-        return self.w16
+    bf16x3_planes = _bf16x3_planes
 
     def wino_pack(self):
         if self.wino is None and self.w_src is not None and self.kh == 3 and self.kw == 3:
@@ -250,11 +254,7 @@ class FusedTransposed:
         self.w_src = w if (self.k == 3 and pad in (0, 1) and self.cin % 16 == 0) else None
         self.w16 = None
 
-    def bf16x3_planes(self):
-        if self.w16 is None and self.w_src is not None:
-            hi, lo = pack_weight_bf16x3(self.w_src)
-            self.w16 = (hi.to(self.w.device), lo.to(self.w.device))
-        return self.w16
+    bf16x3_planes = _bf16x3_planes
 
     def to(self, device):
         self.w = self.w.to(device)
@@ -280,39 +280,116 @@ class SmallTransposed:
         return self
 
 
+def _flags(p):
+    """Epilogue part of a shape key: the operands the launch has (out_scale, noise, bias, residual, res_mask, out_mask, accumulate, res_sub as
+    d n b r m o a s) and its activation."""
+    return ''.join(c for c, v in zip('dnbrmoas', (p.out_scale, p.noise, p.bias, p.residual, p.res_mask, p.out_mask, p.accumulate, p.res_sub)) if v) + str(p.act)
+
+
+def _conv_meta(p, family, in_px=False, in_flags=True):
+    """(FLOPs, shape key, family) of a one-conv launch, read back from its struct.  ``family`` None: the one l2i_conv2d_family picks; ``in_px``:
+    the FLOPs count input pixels (the h8 transposed conv); ``in_flags``: the key records in_mask / in_scale (the h8 convs record neither)."""
+    npx = p.H * p.W if in_px else p.OH * p.OW
+    key = (p.B, p.Cin, p.Cout, p.KH, p.KW, p.stride, p.H, p.W, p.OH, p.OW, p.oy_step, in_flags and bool(p.in_mask), in_flags and bool(p.in_scale), _flags(p))
+    return 2.0 * p.B * p.Cout * p.Cin * p.KH * p.KW * npx, key, family or FAMILIES[_lib.load().l2i_conv2d_family(p)]
+
+
+def _transposed_meta(p, family):
+    """(FLOPs, shape key, family) of a one-launch stride-2 transposed conv (FusedTransposed, SmallTransposed): FLOPs over the input pixels, the
+    full output size in the key."""
+    return (2.0 * p.B * p.Cout * p.Cin * p.KH * p.KW * p.H * p.W,
+            (p.B, p.Cin, p.Cout, p.KH, p.KW, 2, p.H, p.W, p.OHf, p.OWf, 2, bool(p.in_mask), bool(p.in_scale)), family)
+
+
+def _launch(name, args, dtype, meta, *meta_args):
+    """Enqueue entry point ``name`` (its fp16 twin for ``dtype`` float16) with ``args`` on the current stream.  When PROFILE is a list the launch
+    is bracketed by timing events and PROFILE gets (start, end, algorithmic FLOPs, shape key, entry point, kernel family), where
+    ``meta(*meta_args)`` returns (FLOPs, shape key, family) after the launch; it is only called then.  (A closure instead of ``meta_args``
+    would cost every launch about 0.7 us of host time.)"""
+    if PROFILE is None:
+        _lib.call(name, *args, dtype=dtype)
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    name = _lib.call(name, *args, dtype=dtype)
+    e1.record()
+    flop, key, family = meta(*meta_args)
+    PROFILE.append((e0, e1, flop, key, name, family))
+
+
+def _map_ptr(t):
+    """Pointer of a map: 16-bit h8 [B, C/8, H, W, 8] (5-D) or fp32 NCHW."""
+    return None if t is None else (_lib.ptr(t) if t.dim() == 5 else _lib.fptr(t))
+
+
+def _like(t, ref):
+    """Pointer of a map that has the shape of ``ref`` (and, h8, its element type)."""
+    if t is None:
+        return None
+    assert t.shape == ref.shape and (t.dim() == 4 or t.dtype == ref.dtype), (t.shape, t.dtype, ref.shape, ref.dtype)
+    return _map_ptr(t)
+
+
+def _fuse_sq(p, y, sq):
+    """sq = (reference like y, [SQ_SLOTS] zeroed accumulator, [fused flag]): the epilogue also sums (y - ref)^2."""
+    assert sq[1].numel() == _lib.SQ_SLOTS
+    p.sq_ref, p.sq_out = _like(sq[0], y), _lib.fptr(sq[1])
+    sq[2][0] = True
+
+
+def _conv_params(x, w, y, B, cin, H, W, cout, kh, kw, stride, pad_y, pad_x, OH, OW, OHf, OWf, step=1, off_y=0, off_x=0, in_scale=None, in_mask=None,
+                 mask=(0.0, 0.0), out_scale=None, noise=None, noise_w=0.0, bias=None, residual=None, res_mask=None, out_mask=None, act=ACT_NONE, slope=0.0,
+                 gain=1.0, out_gain=1.0, accumulate=False, res_sub=None, res_coef=1.0, res_coef_dev=None, sq=None):      # (epilogue in run_launch's order)
+    """The l2i_conv_params of a conv launch with the fields every launcher shares.  x / y: fp32 NCHW or 16-bit h8 maps; ``w``: an fp32 pack
+    [Cin][KH*KW][CoutP] (l2i.h: w) or 16-bit planes [..][CoutP][8] (w_hi); y is the full [.., OHf, OWf] output, of which the launch writes
+    OH x OW pixels, every ``step``-th from (off_y, off_x).  in_mask has the shape of x; residual, res_mask, out_mask, res_sub and sq[0] that
+    of y; the residual term is res_coef * res_coef_dev[0] * (residual - res_sub).  A field left at its default stays zero (the gains one)."""
+    p = ConvParams()
+    p.x = _lib.ptr(x) if x.dim() == 5 else _lib.fptr(x)                # (_map_ptr inline: this runs on every launch)
+    p.y = _lib.ptr(y) if y.dim() == 5 else _lib.fptr(y)
+    if w.dtype == torch.float32:
+        p.w, p.CoutP = _lib.fptr(w), w.shape[-1]
+    else:
+        p.w_hi, p.CoutP = _lib.ptr(w), w.shape[-2]
+    p.B, p.Cin, p.H, p.W, p.Cout = B, cin, H, W, cout
+    p.KH, p.KW, p.stride, p.pad_y, p.pad_x = kh, kw, stride, pad_y, pad_x
+    p.OH, p.OW, p.OHf, p.OWf = OH, OW, OHf, OWf
+    p.oy_step = p.ox_step = step
+    if off_y or off_x:
+        p.oy_off, p.ox_off = off_y, off_x
+    p.mask_pos, p.mask_neg = mask
+    if in_scale is not None or in_mask is not None:
+        p.in_scale, p.in_mask = _lib.fptr(in_scale), _like(in_mask, x)
+    if out_scale is not None or noise is not None or bias is not None:
+        p.out_scale, p.noise, p.bias = _lib.fptr(out_scale), _lib.fptr(noise), _lib.fptr(bias)
+    if noise_w:
+        p.noise_w = float(noise_w)
+    if residual is not None or res_mask is not None or out_mask is not None:
+        p.residual, p.res_mask, p.out_mask = _like(residual, y), _like(res_mask, y), _like(out_mask, y)
+    if res_sub is not None:
+        assert residual is not None
+        p.res_sub, p.res_coef, p.res_coef_dev = _like(res_sub, y), float(res_coef), _lib.fptr(res_coef_dev)
+    p.act, p.act_slope, p.act_gain, p.out_gain = act, slope, gain, out_gain
+    p.accumulate = int(accumulate)
+    if sq is not None:
+        _fuse_sq(p, y, sq)
+    return p
+
+
 def run_small_transposed(F, x, y, in_mask=None, mask=(1.0, 0.0), out_gain=1.0):
-    lib = _lib.load()
     h8 = x.dim() == 5                                      # [r5] 16-bit h8 gradient (and mask) in: l2i_conv_params::in_h8
     if h8:
         B, cg, H, W, _ = x.shape
         cin = cg * 8
-        assert x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous() and (in_mask is None or (in_mask.dtype == x.dtype and in_mask.is_contiguous()))
+        assert x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous()
     else:
         B, cin, H, W = x.shape
-    assert cin == F.cin and y.shape[0] == B and y.shape[1] == F.cout
-    p = ConvParams()
-    p.x, p.w, p.y = (_lib.ptr(x) if h8 else _lib.fptr(x)), _lib.fptr(F.w), _lib.fptr(y)
+    assert cin == F.cin and y.shape[0] == B and y.shape[1] == F.cout and y.dtype == torch.float32
+    OHf, OWf = y.shape[2], y.shape[3]
+    p = _conv_params(x, F.w, y, B, cin, H, W, F.cout, F.k, F.k, 2, F.pad, F.pad, (OHf + 1) // 2, (OWf + 1) // 2, OHf, OWf, 2, in_mask=in_mask, mask=mask,
+                     out_gain=out_gain)
     p.in_h8 = 0 if not h8 else (2 if x.dtype == torch.float16 else 1)
-    p.B, p.Cin, p.H, p.W, p.Cout, p.CoutP = B, cin, H, W, F.cout, 4
-    p.KH = p.KW = F.k
-    p.stride, p.pad_y, p.pad_x = 2, F.pad, F.pad
-    p.OHf, p.OWf = y.shape[2], y.shape[3]
-    p.OH, p.OW = (p.OHf + 1) // 2, (p.OWf + 1) // 2
-    p.oy_step = p.ox_step = 2
-    p.in_mask = _lib.ptr(in_mask) if h8 else _lib.fptr(in_mask)
-    p.mask_pos, p.mask_neg = mask
-    p.act_gain, p.out_gain = 1.0, out_gain
-    if in_mask is not None:
-        assert in_mask.shape == x.shape
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(lib.l2i_conv_transpose2d_f32(p, _lib.stream_ptr()), 'l2i_conv_transpose2d_f32')
-        e1.record()
-        PROFILE.append((e0, e1, 2.0 * B * F.cout * cin * F.k * F.k * H * W,
-                        (B, cin, F.cout, F.k, F.k, 2, H, W, int(p.OHf), int(p.OWf), 2, in_mask is not None, False), 'l2i_conv_transpose2d_f32', 'direct_small_valu'))
-        return y
-    _lib.check(lib.l2i_conv_transpose2d_f32(p, _lib.stream_ptr()), 'l2i_conv_transpose2d_f32')
+    _launch('l2i_conv_transpose2d_f32', (p,), None, _transposed_meta, p, 'direct_small_valu')
     return y
 
 
@@ -333,42 +410,22 @@ def _split_k(p, px, cin, y):
 
 
 def run_fused_transposed(F, x, y, in_scale=None, in_mask=None, mask=(1.0, 0.0), out_scale=None, out_gain=1.0, tile_hint=0):
-    lib = _lib.load()
     B, cin, H, W = x.shape
     assert cin == F.cin and y.shape[0] == B and y.shape[1] == F.cout
-    p = ConvParams()
-    p.x, p.w, p.y = _lib.fptr(x), _lib.fptr(F.w), _lib.fptr(y)
-    p.B, p.Cin, p.H, p.W, p.Cout, p.CoutP = B, cin, H, W, F.cout, F.w.shape[2]
-    p.KH = p.KW = F.k
-    p.stride, p.pad_y, p.pad_x = 2, F.pad, F.pad
-    p.OHf, p.OWf = y.shape[2], y.shape[3]
-    p.OH, p.OW = (p.OHf + 1) // 2, (p.OWf + 1) // 2
-    p.oy_step = p.ox_step = 2
-    p.in_scale, p.in_mask = _lib.fptr(in_scale), _lib.fptr(in_mask)
-    p.mask_pos, p.mask_neg = mask
-    p.out_scale = _lib.fptr(out_scale)
-    p.act_gain, p.out_gain = 1.0, out_gain
+    OHf, OWf = y.shape[2], y.shape[3]
+    p = _conv_params(x, F.w, y, B, cin, H, W, F.cout, F.k, F.k, 2, F.pad, F.pad, (OHf + 1) // 2, (OWf + 1) // 2, OHf, OWf, 2, in_scale=in_scale,
+                     in_mask=in_mask, mask=mask, out_scale=out_scale, out_gain=out_gain)
     p.tile_hint = tile_hint
-    if in_mask is not None:
-        assert in_mask.shape == x.shape
-    entry, name, family = lib.l2i_conv_transpose2d_f32, 'l2i_conv_transpose2d_f32', 'transposed_f32'
+    name, family = 'l2i_conv_transpose2d_f32', 'transposed_f32'
     nat_h, nat_w = (H - 1) * 2 - 2 * F.pad + F.k, (W - 1) * 2 - 2 * F.pad + F.k
     if (PRECISION == 'bf16x3' and tile_hint == 0 and F.w_src is not None and W % 4 == 0 and W >= 32 and x.data_ptr() % 16 == 0
-            and (in_mask is None or in_mask.data_ptr() % 16 == 0) and 0 <= p.OHf - nat_h <= 8 and 0 <= p.OWf - nat_w <= 8):
+            and (in_mask is None or in_mask.data_ptr() % 16 == 0) and 0 <= OHf - nat_h <= 8 and 0 <= OWf - nat_w <= 8):
         planes = F.bf16x3_planes()
         p.w_hi, p.w_lo = _lib.ptr(planes[0]), _lib.ptr(planes[1])
-        entry, name, family = lib.l2i_conv_transpose2d_bf16x3_f32, 'l2i_conv_transpose2d_bf16x3_f32', 'transposed_bf16x3'
+        name, family = 'l2i_conv_transpose2d_bf16x3_f32', 'transposed_bf16x3'
     else:
         _split_k(p, B * H * W, cin, y)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(entry(p, _lib.stream_ptr()), name)
-        e1.record()
-        PROFILE.append((e0, e1, 2.0 * B * F.cout * cin * F.k * F.k * H * W,
-                        (B, cin, F.cout, F.k, F.k, 2, H, W, int(p.OHf), int(p.OWf), 2, in_mask is not None, in_scale is not None), name, family))
-        return y
-    _lib.check(entry(p, _lib.stream_ptr()), name)
+    _launch(name, (p,), None, _transposed_meta, p, family)
     return y
 
 
@@ -377,8 +434,8 @@ def run_launch(L, x, y, out_hw=None, in_scale=None, in_mask=None, mask=(1.0, 0.0
                out_gain=1.0, accumulate=False, tile_hint=0, res_sub=None, res_coef=1.0, res_coef_dev=None, sq=None, pool=None, _defer=None):
     """Enqueue one kernel call on the current stream.  ``_defer`` (a list): a plain 1x1 stride-1 launch appends its struct instead (``launch_pair_f32``).  ``y`` is the full output tensor [B, Cout, OHf, OWf].  ``pool`` ([r5]) = (pooled [B, Cout, OHf/2, OWf/2]
     fp32, arg-max bytes of the same shape, [fused flag]): where the launch takes the position-split F(4x4) kernel it also writes MaxPool2d(2, 2) of y
-    (l2i.h: pool_out / pool_idx) and sets the flag; otherwise the caller runs the pool kernel."""
-    lib = _lib.load()
+    (l2i.h: pool_out / pool_idx) and sets the flag; otherwise the caller runs the pool kernel.  ``sq`` (see _fuse_sq): where the chosen kernel's
+    epilogue can, it sums (y - ref)^2 and sets the flag."""
     B, cin, H, W = x.shape
     assert cin == L.cin, (cin, L.cin)
     assert y.shape[0] == B and y.shape[1] == L.cout, (y.shape, B, L.cout)
@@ -390,45 +447,24 @@ def run_launch(L, x, y, out_hw=None, in_scale=None, in_mask=None, mask=(1.0, 0.0
         OW = (OWf - L.off_x + L.step - 1) // L.step
     if OH <= 0 or OW <= 0:
         return
-    p = ConvParams()
-    p.x, p.w, p.y = _lib.fptr(x), _lib.fptr(L.w), _lib.fptr(y)
-    p.B, p.Cin, p.H, p.W, p.Cout, p.CoutP = B, cin, H, W, L.cout, L.w.shape[2]
-    p.KH, p.KW, p.stride, p.pad_y, p.pad_x = L.kh, L.kw, L.stride, L.pad_y, L.pad_x
-    p.OH, p.OW, p.OHf, p.OWf = OH, OW, OHf, OWf
-    p.oy_step = p.ox_step = L.step
-    p.oy_off, p.ox_off = L.off_y, L.off_x
-    p.in_scale, p.in_mask = _lib.fptr(in_scale), _lib.fptr(in_mask)
-    p.mask_pos, p.mask_neg = mask
-    p.out_scale, p.noise, p.noise_w, p.bias = _lib.fptr(out_scale), _lib.fptr(noise), float(noise_w), _lib.fptr(bias)
-    p.residual, p.res_mask, p.out_mask = _lib.fptr(residual), _lib.fptr(res_mask), _lib.fptr(out_mask)
-    if res_sub is not None:                      # residual term = res_coef * res_coef_dev[0] * (residual - res_sub)
-        assert residual is not None and res_sub.shape == residual.shape
-        p.res_sub, p.res_coef, p.res_coef_dev = _lib.fptr(res_sub), float(res_coef), _lib.fptr(res_coef_dev)
-    p.act, p.act_slope, p.act_gain, p.out_gain = act, slope, gain, out_gain
-    p.accumulate, p.tile_hint = int(accumulate), tile_hint
-    if in_mask is not None:
-        assert in_mask.shape == x.shape
-    if residual is not None:
-        assert residual.shape == y.shape
-    if out_mask is not None:
-        assert out_mask.shape == y.shape
-    entry, name = lib.l2i_conv2d_f32, 'l2i_conv2d_f32'
+    p = _conv_params(x, L.w, y, B, cin, H, W, L.cout, L.kh, L.kw, L.stride, L.pad_y, L.pad_x, OH, OW, OHf, OWf, L.step, L.off_y, L.off_x,
+                     in_scale, in_mask, mask, out_scale, noise, noise_w, bias, residual, res_mask, out_mask, act, slope, gain, out_gain, accumulate,
+                     res_sub, res_coef, res_coef_dev)                # (positional: ~20 keyword arguments would add ~1 us per launch)
+    p.tile_hint = tile_hint
     if _defer is not None:
         assert L.kh == 1 and L.kw == 1 and L.stride == 1 and L.step == 1
-        _defer.append((p, (x, y, L.w, bias, residual)))
+        _defer.append((p, x.dtype, (x, y, L.w, bias, residual)))
         return
+    name, family, fuse_sq = 'l2i_conv2d_f32', None, False          # family None: the one l2i_conv2d_family picks for the struct
     if (L.w4 is not None and tile_hint == 0 and out_scale is None and noise is None and bias is None and residual is None and out_mask is None
             and act == ACT_NONE):                          # the launch takes the direct VALU kernel (l2i_conv2d_family): hand it the dense pack
         p.w, p.CoutP = _lib.fptr(L.w4), 4
     if PRECISION == 'bf16x3' and tile_hint == 0 and _bf16x3_eligible(L, x, in_mask, OW):
         planes = L.bf16x3_planes()
         p.w_hi, p.w_lo = _lib.ptr(planes[0]), _lib.ptr(planes[1])
-        entry, name = lib.l2i_conv2d_bf16x3_f32, 'l2i_conv2d_bf16x3_f32'
-        if (sq is not None and L.step == 1 and OWf % 4 == 0 and OW % 4 == 0 and sq[0].data_ptr() % 16 == 0
-                and _wino_aligned(y, residual, res_mask, out_mask, noise, res_sub)):      # the vectorised epilogue (l2i_epilogue_vec_ok) sums (y - ref)^2 too
-            assert sq[0].shape == y.shape and sq[1].numel() == _lib.SQ_SLOTS
-            p.sq_ref, p.sq_out = _lib.fptr(sq[0]), _lib.fptr(sq[1])
-            sq[2][0] = True
+        name, family = 'l2i_conv2d_bf16x3_f32', 'implicit_gemm_bf16x3'
+        fuse_sq = (L.step == 1 and OWf % 4 == 0 and OW % 4 == 0
+                   and _wino_aligned(y, residual, res_mask, out_mask, noise, res_sub))      # the vectorised epilogue (l2i_epilogue_vec_ok) sums (y - ref)^2 too
     elif (USE_WINOGRAD and L.kh == 3 and L.kw == 3 and L.stride == 1 and L.step == 1 and L.w_src is not None and L.cout > 4 and OW >= 32
           and OW % 4 == 0 and tile_hint == 0 and _wino_aligned(y, residual, res_mask, out_mask, noise, res_sub)):
         relu_in = in_mask is not None and in_mask.data_ptr() == x.data_ptr() and tuple(mask) == (1.0, 0.0)
@@ -442,35 +478,18 @@ def run_launch(L, x, y, out_hw=None, in_scale=None, in_mask=None, mask=(1.0, 0.0
                 assert tuple(pool[0].shape) == (B, L.cout, OHf // 2, OWf // 2) and pool[1].shape == pool[0].shape and pool[1].dtype == torch.uint8
                 p.pool_out, p.pool_idx = _lib.fptr(pool[0]), _lib.ptr(pool[1])
                 pool[2][0] = True
-            entry, name = lib.l2i_conv2d_wino4_f32, 'l2i_conv2d_wino4_f32'
+            name, family = 'l2i_conv2d_wino4_f32', 'winograd4_f32'
         else:
             p.w = _lib.fptr(L.wino_pack())
-            entry, name = lib.l2i_conv2d_wino_f32, 'l2i_conv2d_wino_f32'
-        if sq is not None and sq[0].data_ptr() % 16 == 0:    # sq = (reference like y, [SQ_SLOTS] zeroed accumulator, [fused flag]): sum (y - ref)^2 in the epilogue
-            assert sq[0].shape == y.shape and sq[1].numel() == _lib.SQ_SLOTS
-            p.sq_ref, p.sq_out = _lib.fptr(sq[0]), _lib.fptr(sq[1])
-            sq[2][0] = True
+            name, family = 'l2i_conv2d_wino_f32', 'winograd_f32'
+        fuse_sq = True
     elif L.kh * L.kw > 1 and L.cout > 4:
         _split_k(p, B * OH * OW, cin, y)                  # small maps of the generic kernel (the Winograd / split-precision kernels take maps >= 32 wide)
-    if (sq is not None and name == 'l2i_conv2d_f32' and tile_hint == 0 and sq[0].data_ptr() % 16 == 0 and p.ksplit <= 1
-            and lib.l2i_conv2d_family(p) == 2):           # L2I_FAMILY_CIN3: the <= 3-input-channel kernel sums (y - ref)^2 in its epilogue too
-        assert sq[0].shape == y.shape and sq[1].numel() == _lib.SQ_SLOTS
-        p.sq_ref, p.sq_out = _lib.fptr(sq[0]), _lib.fptr(sq[1])
-        sq[2][0] = True
-    if PROFILE is not None:
-        family = {'l2i_conv2d_wino_f32': 'winograd_f32', 'l2i_conv2d_wino4_f32': 'winograd4_f32', 'l2i_conv2d_bf16x3_f32': 'implicit_gemm_bf16x3'}.get(name)
-        if family is None:
-            family = FAMILIES[lib.l2i_conv2d_family(p)]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(entry(p, _lib.stream_ptr()), name)
-        e1.record()
-        PROFILE.append((e0, e1, 2.0 * B * L.cout * cin * L.kh * L.kw * OH * OW,
-                        (B, cin, L.cout, L.kh, L.kw, L.stride, H, W, OH, OW, L.step, in_mask is not None, in_scale is not None,
-                         ''.join(c for c, t in zip('dnbrmoas', (out_scale, noise, bias, residual, res_mask, out_mask, accumulate or None, res_sub)) if t is not None) + str(act)),
-                        name, family))
-        return
-    _lib.check(entry(p, _lib.stream_ptr()), name)
+    if (sq is not None and sq[0].data_ptr() % 16 == 0
+            and (fuse_sq or (family is None and tile_hint == 0 and p.ksplit <= 1
+                             and _lib.load().l2i_conv2d_family(p) == 2))):      # L2I_FAMILY_CIN3: the <= 3-input-channel kernel sums (y - ref)^2 too
+        _fuse_sq(p, y, sq)
+    _launch(name, (p,), None, _conv_meta, p, family)
 
 
 def _bf16x3_eligible(L, x, in_mask, OW):
@@ -499,6 +518,12 @@ def run_plan(plan, x, y, accumulate=False, **kw):
     return y
 
 
+def _weight_f32(weight, keep_cuda=False):
+    """A conv weight (numpy array or tensor) as an fp32 tensor on the host; ``keep_cuda``: a CUDA weight stays where it lives."""
+    w = torch.as_tensor(weight if torch.is_tensor(weight) else np.asarray(weight), dtype=torch.float32)
+    return w if keep_cuda and w.is_cuda else w.cpu()
+
+
 class FrozenConv2d:
     """A convolution (or stride-2 transposed convolution) with constant weights: forward plan + input-gradient plan.
 
@@ -506,9 +531,7 @@ class FrozenConv2d:
     y[co, 2i+k-pad] += x[ci, i] * weight[co, ci, k]  (F.conv_transpose2d(x, weight.transpose(0,1), stride=2))."""
 
     def __init__(self, weight, stride=1, padding=0, transposed=False, device='cuda'):
-        w = torch.as_tensor(np.asarray(weight) if not torch.is_tensor(weight) else weight, dtype=torch.float32)
-        if not (torch.is_tensor(weight) and weight.is_cuda):        # frozen nets: numpy / CPU weights, packed once on the host
-            w = w.cpu()                                             # (a CUDA weight — a net that is being trained — is packed where it lives)
+        w = _weight_f32(weight, keep_cuda=True)      # frozen nets: numpy / CPU weights, packed once on the host (a net that is being trained: where it lives)
         self.cout, self.cin, self.k, _ = w.shape
         self.stride, self.padding, self.transposed = stride, padding, transposed
         wt = w.transpose(0, 1).contiguous()                       # [Cin, Cout, K, K]: roles swapped for the gradient
@@ -633,7 +656,7 @@ class ImgConvH8:
     land on the fp32 image through the generic kernels: H8Conv.dgrad(out_f32=True), FrozenConv2d.dgrad_h8in)."""
 
     def __init__(self, weight, stride=1, padding=0, device='cuda'):
-        w = torch.as_tensor(np.asarray(weight) if not torch.is_tensor(weight) else weight, dtype=torch.float32).cpu()
+        w = _weight_f32(weight)
         self.cout, self.cin, self.k, _ = w.shape
         assert (self.k, stride) in ((1, 1), (3, 1), (7, 2)) and self.cout % 8 == 0, (self.k, stride, self.cout)
         self.stride, self.padding = stride, padding
@@ -644,35 +667,13 @@ class ImgConvH8:
         return (h + 2 * self.padding - self.k) // self.stride + 1, (w + 2 * self.padding - self.k) // self.stride + 1
 
     def forward(self, x, bias=None, act=ACT_NONE, slope=0.2, gain=1.0, out_gain=1.0, sq=None):
-        lib = _lib.load()
         B, cin, H, W = x.shape
         assert cin == self.cin and x.dtype == torch.float32
         oh, ow = self.out_hw(H, W)
         y = torch.empty(B, self.cout // 8, oh, ow, 8, device=x.device, dtype=self.dtype)
-        p = ConvParams()
-        p.x, p.w_hi, p.y = _lib.fptr(x), _lib.ptr(self.planes), _lib.ptr(y)
-        p.B, p.Cin, p.H, p.W, p.Cout, p.CoutP = B, cin, H, W, self.cout, self.planes.shape[-2]
-        p.KH = p.KW = self.k
-        p.stride, p.pad_y, p.pad_x = self.stride, self.padding, self.padding
-        p.OH, p.OW, p.OHf, p.OWf = oh, ow, oh, ow
-        p.oy_step = p.ox_step = 1
-        p.bias = _lib.fptr(bias)
-        p.act, p.act_slope, p.act_gain, p.out_gain = act, slope, gain, out_gain
-        if sq is not None:                                            # (reference like y, [SQ_SLOTS] zeroed accumulator, [fused flag])
-            assert sq[0].shape == y.shape and sq[0].dtype == y.dtype and sq[1].numel() == _lib.SQ_SLOTS
-            p.sq_ref, p.sq_out = _lib.ptr(sq[0]), _lib.fptr(sq[1])
-            sq[2][0] = True
-        name = 'l2i_conv_img_h8' + ('_f16' if self.dtype == torch.float16 else '')
-        entry = getattr(lib, name)
-        if PROFILE is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _lib.check(entry(p, _lib.stream_ptr()), name)
-            e1.record()
-            PROFILE.append((e0, e1, 2.0 * B * self.cout * cin * self.k * self.k * oh * ow,
-                            (B, cin, self.cout, self.k, self.k, self.stride, H, W, oh, ow, 1, False, False, ('b' if bias is not None else '') + str(act)), name, 'conv_h8'))
-            return y
-        _lib.check(entry(p, _lib.stream_ptr()), name)
+        p = _conv_params(x, self.planes, y, B, cin, H, W, self.cout, self.k, self.k, self.stride, self.padding, self.padding, oh, ow, oh, ow, bias=bias,
+                         act=act, slope=slope, gain=gain, out_gain=out_gain, sq=sq)
+        _launch('l2i_conv_img_h8', (p,), self.dtype, _conv_meta, p, 'conv_h8')
         return y
 
 
@@ -682,7 +683,7 @@ class H8Conv:
     l2i_conv2d_h8 / l2i_conv_transpose2d_h8; no weight gradients (the walk is the only trainable tensor)."""
 
     def __init__(self, weight, stride=1, padding=0, transposed=False, device='cuda', cin_pad=32):
-        w = torch.as_tensor(np.asarray(weight) if not torch.is_tensor(weight) else weight, dtype=torch.float32).cpu()
+        w = _weight_f32(weight)
         self.cout, self.cin, self.k, _ = w.shape
         self.stride, self.padding, self.transposed, self.device = stride, padding, transposed, device
         assert cin_pad == 32 or (cin_pad == 16 and self.k == 3 and stride == 1 and not transposed), 'a 16-channel chunk exists for 3x3 stride-1 layers only'
@@ -725,17 +726,13 @@ class H8Conv:
             return run_h8(pl, gy, out, self.coutp_in, self.cin, self.k, 2, self.padding, transposed=True, w_bstride=w_bstride, **kw)
         return run_h8(pl, gy, out, self.coutp_in, self.cin, self.k, 1, self.k - 1 - self.padding, transposed=False, w_bstride=w_bstride, **kw)
 
-
-def _h8_dgrad_compact(self, gy, planes=None, **kw):
-    """Input-gradient of a STRIDED 1x1 conv without the zero insertion: the 1x1 stride-1 conv of gy with the transposed weights, on the
-    compact (output-resolution) map; the caller scatters it into every second pixel (kernels16.add_zero_insert)."""
-    assert self.k == 1 and self.stride == 2 and not self.transposed
-    B, _, oh, ow, _ = gy.shape
-    out = torch.empty(B, (self.cin + 7) // 8, oh, ow, 8, device=gy.device, dtype=gy.dtype)
-    return run_h8(planes if planes is not None else self.bwd_planes, gy, out, self.coutp_in, self.cin, 1, 1, 0, **kw)
-
-
-H8Conv.dgrad_compact = _h8_dgrad_compact
+    def dgrad_compact(self, gy, planes=None, **kw):
+        """Input-gradient of a STRIDED 1x1 conv without the zero insertion: the 1x1 stride-1 conv of gy with the transposed weights, on the
+        compact (output-resolution) map; the caller scatters it into every second pixel (kernels16.add_zero_insert)."""
+        assert self.k == 1 and self.stride == 2 and not self.transposed
+        B, _, oh, ow, _ = gy.shape
+        out = torch.empty(B, (self.cin + 7) // 8, oh, ow, 8, device=gy.device, dtype=gy.dtype)
+        return run_h8(planes if planes is not None else self.bwd_planes, gy, out, self.coutp_in, self.cin, 1, 1, 0, **kw)
 
 
 def run_h8(planes, x, y, cin, cout, k, stride, pad, transposed=False, w_bstride=0, out_f32=False, out_scale=None, noise=None, noise_w=0.0, bias=None,
@@ -743,85 +740,50 @@ def run_h8(planes, x, y, cin, cout, k, stride, pad, transposed=False, w_bstride=
            res_coef_dev=None, sq=None, relu_in=False, rgb=None, mask_out=None, mask_bits=False, _defer=None):
     """Enqueue l2i_conv2d_h8 / l2i_conv_transpose2d_h8 on the current stream.  x: h8 bf16 with ``cin`` (multiple of 32) channels.
     ``_defer``: a list — the filled parameter struct is appended to it instead of being launched (``launch_pair_h8`` launches two of them as one kernel)."""
-    lib = _lib.load()
     B, cg, H, W, _ = x.shape
     assert x.dtype in (torch.bfloat16, torch.float16) and cg * 8 == cin and cin % 16 == 0, (x.dtype, x.shape, cin)
-    f16 = x.dtype == torch.float16
-    coutp = planes.shape[-2]
-    assert planes.shape[-5] == cin // 16 and planes.shape[-4] == k * k and coutp >= cout, (planes.shape, cin, k, cout)
+    assert planes.shape[-5] == cin // 16 and planes.shape[-4] == k * k and planes.shape[-2] >= cout, (planes.shape, cin, k, cout)
     if out_f32:
         assert y.dtype == torch.float32 and y.shape[1] == cout
-        OHf, OWf = y.shape[2], y.shape[3]
     else:
         assert y.dtype == x.dtype and y.shape[1] * 8 >= cout and cout % 8 == 0, (y.dtype, y.shape, cout)
-        OHf, OWf = y.shape[2], y.shape[3]
-    p = ConvParams()
-    p.x, p.w_hi, p.y = _lib.ptr(x), _lib.ptr(planes), _lib.ptr(y)
-    p.B, p.Cin, p.H, p.W, p.Cout, p.CoutP = B, cin, H, W, cout, coutp
-    p.KH = p.KW = k
-    p.stride, p.pad_y, p.pad_x = stride, pad, pad
-    p.OHf, p.OWf = OHf, OWf
+    OHf, OWf = y.shape[2], y.shape[3]
     if transposed:
-        p.OH, p.OW = (OHf + 1) // 2, (OWf + 1) // 2
-        p.oy_step = p.ox_step = 2
+        OH, OW, step = (OHf + 1) // 2, (OWf + 1) // 2, 2
     else:
-        p.OH, p.OW = min(OHf, (H + 2 * pad - k) // stride + 1), min(OWf, (W + 2 * pad - k) // stride + 1)
-        p.oy_step = p.ox_step = 1
-    p.out_scale, p.noise, p.noise_w, p.bias = _lib.fptr(out_scale), _lib.fptr(noise), float(noise_w), _lib.fptr(bias)
-    for t in (residual, res_sub) + (() if mask_bits else (res_mask, out_mask)):
-        assert t is None or (t.shape == y.shape and t.dtype == y.dtype)
+        OH, OW, step = min(OHf, (H + 2 * pad - k) // stride + 1), min(OWf, (W + 2 * pad - k) // stride + 1), 1
+    p = _conv_params(x, planes, y, B, cin, H, W, cout, k, k, stride, pad, pad, OH, OW, OHf, OWf, step, 0, 0, None, None,
+                     mask, out_scale, noise, noise_w, bias, residual, None if mask_bits else res_mask, None if mask_bits else out_mask, act, slope, gain,
+                     out_gain, accumulate, res_sub, res_coef, res_coef_dev, sq)       # (positional, as in run_launch; mask: of the OUTPUT mask here)
     if mask_bits or mask_out is not None:             # [r6] sign planes (l2i.h: mask_out / mask_bits): one byte per 16-byte pixel slot, [B, Cout/8, OHf, OWf] uint8
         assert not out_f32
         for t in (mask_out,) + ((res_mask, out_mask) if mask_bits else ()):
             assert t is None or (t.dtype == torch.uint8 and tuple(t.shape) == tuple(y.shape[:4]) and t.is_contiguous()), (None if t is None else (t.dtype, t.shape), y.shape)
         p.mask_out, p.mask_bits = _lib.ptr(mask_out), int(bool(mask_bits))
-    p.residual, p.res_mask, p.out_mask = _lib.ptr(residual), _lib.ptr(res_mask), _lib.ptr(out_mask)
-    p.mask_pos, p.mask_neg = mask                                 # of the OUTPUT mask here: * (out_mask > 0 ? mask[0] : mask[1])
+        if mask_bits:
+            p.res_mask, p.out_mask = _lib.ptr(res_mask), _lib.ptr(out_mask)
     if relu_in:                                                   # ReLU-on-load (VGG-19 reads pre-ReLU taps): in_mask == x, mask (1, 0)
         assert out_mask is None
         p.in_mask, p.mask_pos, p.mask_neg = p.x, 1.0, 0.0
-    if res_sub is not None:
-        p.res_sub, p.res_coef, p.res_coef_dev = _lib.ptr(res_sub), float(res_coef), _lib.fptr(res_coef_dev)
-    p.act, p.act_slope, p.act_gain, p.out_gain = act, slope, gain, out_gain
-    p.accumulate = int(accumulate)
     p.w_bstride, p.out_f32 = int(w_bstride), int(out_f32)
-    if sq is not None:                                            # (reference like y, [SQ_SLOTS] zeroed accumulator, [fused flag])
-        assert sq[0].shape == y.shape and sq[0].dtype == y.dtype and sq[1].numel() == _lib.SQ_SLOTS
-        p.sq_ref, p.sq_out = _lib.ptr(sq[0]), _lib.fptr(sq[1])
-        sq[2][0] = True
     if rgb is not None:                                           # [r5] (wmod [B, 3, Cout], bias [3], out [B, 3, OHf, OWf]) fp32: ToRGB of the output in the epilogue (l2i.h: rgb_w)
         assert not transposed and not out_f32 and cout in (32, 64) and tuple(rgb[0].shape) == (B, 3, cout) and tuple(rgb[2].shape) == (B, 3, OHf, OWf)
         p.rgb_w, p.rgb_bias, p.rgb_out = _lib.fptr(rgb[0]), _lib.fptr(rgb[1]), _lib.fptr(rgb[2])
-    name = ('l2i_conv_transpose2d_h8' if transposed else 'l2i_conv2d_h8') + ('_f16' if f16 else '')
     if _defer is not None:
         assert not transposed
-        _defer.append((p, f16, (planes, x, y, residual, res_mask, out_mask, mask_out, bias), ''.join(c for c, t in zip('brmo', (bias, residual, res_mask, out_mask)) if t is not None) + str(act)))
+        _defer.append((p, x.dtype, (planes, x, y, residual, res_mask, out_mask, mask_out, bias)))
         return y
-    entry = getattr(lib, name)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(entry(p, _lib.stream_ptr()), name)
-        e1.record()
-        npx = H * W if transposed else int(p.OH) * int(p.OW)
-        PROFILE.append((e0, e1, 2.0 * B * cout * cin * k * k * npx, (B, cin, cout, k, k, stride, H, W, int(p.OH), int(p.OW), 2 if transposed else 1, False, False,
-                                                                     ''.join(c for c, t in zip('dnbrmoas', (out_scale, noise, bias, residual, res_mask, out_mask, accumulate or None, res_sub)) if t is not None) + str(act)),
-                        name, 'transposed_h8' if transposed else 'conv_h8'))
-        return y
-    _lib.check(entry(p, _lib.stream_ptr()), name)
+    _launch('l2i_conv_transpose2d_h8' if transposed else 'l2i_conv2d_h8', (p,), x.dtype, _conv_meta, p, 'transposed_h8' if transposed else 'conv_h8',
+            transposed, False)
     return y
 
 
-PAIR_VARIANT = int(_os.environ.get('L2I_H8_PAIR_TILE', '-1'))      # -1: by map size (launch_pair_h8); 0 / 1: l2i_conv1x1_pair_h8's variant argument
-
-
-PAIR_MAX_COUT2 = int(_os.environ.get('L2I_H8_PAIR_MAXC', '256'))     # (A/B: 128 leaves the 256-channel shapes — one block per CU — to separate launches)
 PAIR_SHAPES = ((64, 64), (128, 128), (256, 256), (64, 128), (128, 256))          # (input channels of the first conv, output channels of the second) l2i_conv1x1_pair_h8 is built for
 
 
 def pair_h8_shapes_ok(cin1, cout1, cout2, npix):
     """Does l2i_conv1x1_pair_h8 take two chained 1x1 stride-1 convs cin1 -> cout1 -> cout2 on maps of ``npix`` pixels (include/l2i.h lists the conditions)?"""
-    return (cin1, cout2) in PAIR_SHAPES and cout2 <= PAIR_MAX_COUT2 and cout1 % 32 == 0 and npix % 128 == 0
+    return (cin1, cout2) in PAIR_SHAPES and cout1 % 32 == 0 and npix % 128 == 0
 
 
 CHAIN3_SHAPES = ((64, 64), (128, 128), (64, 128))        # (channels of the 3x3 conv, output channels of the last conv) l2i_conv_chain3_h8 is built for
@@ -829,34 +791,29 @@ CHAIN3_SHAPES = ((64, 64), (128, 128), (64, 128))        # (channels of the 3x3 
 
 def chain3_h8_shapes_ok(c, cout1, cout2, h, w):
     """Does l2i_conv_chain3_h8 take 3x3 (c -> c) -> 1x1 (c -> cout1) -> 1x1 (cout1 -> cout2) on h x w maps?"""
-    return (c, cout2) in CHAIN3_SHAPES and cout2 <= PAIR_MAX_COUT2 and cout1 % 32 == 0 and w % 32 == 0 and h % 4 == 0
+    return (c, cout2) in CHAIN3_SHAPES and cout1 % 32 == 0 and w % 32 == 0 and h % 4 == 0
+
+
+def _pair_meta(p1, p2, family, fl=None, chain3=False):
+    """(FLOPs, shape key, family) of a launch of two chained 1x1 convs (p1 -> p2), with a 3x3 conv on p1's input in front for ``chain3``;
+    ``fl``: the key's epilogue flags (default: those of both structs)."""
+    B, c1, c2, c3, H, W = p1.B, p1.Cin, p1.Cout, p2.Cout, p1.H, p1.W
+    fl = fl or _flags(p1) + '+' + _flags(p2)
+    return 2.0 * B * H * W * (c1 * c2 + c2 * c3 + (9 * c1 * c1 if chain3 else 0)), (B, c1, c2, 1, 1, 1, H, W, H, W, 1, False, False, fl, c3), family
 
 
 def launch_pair_h8(deferred, variant=None):
     """``deferred``: the structs ``run_h8(..., _defer=deferred)`` left — two (a 1x1 conv, then the 1x1 conv that reads its output: l2i_conv1x1_pair_h8) or three
     (a 3x3 stride-1 conv in front of them: l2i_conv_chain3_h8): ONE launch on the current stream.  Raises L2IError when the library refuses the chain (the caller
     checks ``pair_h8_shapes_ok`` / ``chain3_h8_shapes_ok`` first)."""
-    lib = _lib.load()
     head = deferred[0] if len(deferred) == 3 else None
-    (p1, f16, keep1, fl1), (p2, f16b, keep2, fl2) = deferred[-2:]
-    assert f16 == f16b and (head is None or head[1] == f16)
-    name = ('l2i_conv_chain3_h8' if head is not None else 'l2i_conv1x1_pair_h8') + ('_f16' if f16 else '')
-    entry = getattr(lib, name)
-    npix = int(p1.H) * int(p1.W)
+    (p1, dtype, _), (p2, dtype2, _) = deferred[-2:]
+    assert dtype == dtype2 and (head is None or head[1] == dtype)
     if variant is None:
-        variant = PAIR_VARIANT if PAIR_VARIANT >= 0 else (1 if int(p1.B) * npix < 256 * 1024 else 0)      # 128-pixel tiles below 1024 blocks of 256 pixels
-    args = ((head[0],) if head is not None else ()) + (p1, p2, int(variant), _lib.stream_ptr())
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(entry(*args), name)
-        e1.record()
-        B, c1, c2, c3 = int(p1.B), int(p1.Cin), int(p1.Cout), int(p2.Cout)
-        flop = 2.0 * B * npix * (c1 * c2 + c2 * c3 + (9 * c1 * c1 if head is not None else 0))
-        # (priced in the conv_h8 family: its launches are what this one replaces; bench.call_bytes knows the entry names)
-        PROFILE.append((e0, e1, flop, (B, c1, c2, 1, 1, 1, int(p1.H), int(p1.W), int(p1.H), int(p1.W), 1, False, False, fl1 + '+' + fl2, c3), name, 'conv_h8'))
-        return
-    _lib.check(entry(*args), name)
+        variant = 1 if p1.B * p1.H * p1.W < 256 * 1024 else 0      # 128-pixel tiles below 1024 blocks of 256 pixels
+    # (priced in the conv_h8 family: its launches are what this one replaces; bench.call_bytes knows the entry names)
+    _launch('l2i_conv_chain3_h8' if head is not None else 'l2i_conv1x1_pair_h8', ((head[0],) if head is not None else ()) + (p1, p2, int(variant)), dtype,
+            _pair_meta, p1, p2, 'conv_h8', None, head is not None)
 
 
 PAIR_F32_SHAPES = ((64, 64), (64, 128), (128, 128))       # (input channels of the first conv, output channels of the second) l2i_conv1x1_pair_f32 is built for
@@ -869,15 +826,5 @@ def pair_f32_shapes_ok(cin1, cout1, cout2, npix):
 def launch_pair_f32(deferred):
     """``deferred``: the two structs ``run_launch(..., _defer=deferred)`` left (a 1x1 conv with bias / residual / ReLU, then the 1x1 conv that reads its output):
     ONE launch of l2i_conv1x1_pair_f32 on the current stream."""
-    lib = _lib.load()
-    (p1, keep1), (p2, keep2) = deferred
-    name = 'l2i_conv1x1_pair_f32'
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _lib.check(lib.l2i_conv1x1_pair_f32(p1, p2, _lib.stream_ptr()), name)
-        e1.record()
-        B, c1, c2, c3, npix = int(p1.B), int(p1.Cin), int(p1.Cout), int(p2.Cout), int(p1.H) * int(p1.W)
-        PROFILE.append((e0, e1, 2.0 * B * npix * (c1 * c2 + c2 * c3), (B, c1, c2, 1, 1, 1, int(p1.H), int(p1.W), int(p1.H), int(p1.W), 1, False, False, 'br1+b1', c3), name, 'gemm1x1_f32'))
-        return
-    _lib.check(lib.l2i_conv1x1_pair_f32(p1, p2, _lib.stream_ptr()), name)
+    (p1, _, _), (p2, _, _) = deferred
+    _launch('l2i_conv1x1_pair_f32', (p1, p2), None, _pair_meta, p1, p2, 'gemm1x1_f32', 'br1+b1')

@@ -233,8 +233,8 @@ class _RegBceFn(torch.autograd.Function):
         loss = torch.empty(1, dtype=torch.float64, device=feat.device)
         preds = torch.empty(B, K, dtype=torch.float32, device=feat.device)
         g = torch.empty_like(feat)
-        _lib.check(_lib.load().l2i_reg_bce_f32(_lib.ptr(loss), _lib.fptr(preds), _lib.fptr(g), _lib.fptr(feat), _lib.fptr(fc_w), _lib.fptr(fc_b), _lib.ptr(cols),
-                                              _lib.ptr(target), int(target.dtype == torch.float64), B, F, K, 1e-12, _lib.stream_ptr()), 'l2i_reg_bce_f32')
+        _lib.call('l2i_reg_bce_f32', _lib.ptr(loss), _lib.fptr(preds), _lib.fptr(g), _lib.fptr(feat), _lib.fptr(fc_w), _lib.fptr(fc_b), _lib.ptr(cols),
+                  _lib.ptr(target), int(target.dtype == torch.float64), B, F, K, 1e-12)
         ctx.save_for_backward(g)
         ctx.preds = preds
         return loss.reshape(())

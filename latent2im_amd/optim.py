@@ -81,7 +81,6 @@ class GuardedAdam(torch.optim.Adam):
                 todo.append((p, group, st))
         if not todo:
             return None
-        lib = _lib.load()
         state, scale = self._flags(todo[0][0].device)
         sc = self.scaler
         single = len(todo) == 1
@@ -89,13 +88,13 @@ class GuardedAdam(torch.optim.Adam):
         if not single:
             for p, _, _ in todo:
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                _lib.check(lib.l2i_nonfinite_flag_f32(_lib.fptr(g), g.numel(), _lib.ptr(state), stream), 'l2i_nonfinite_flag_f32')
+                _lib.call('l2i_nonfinite_flag_f32', _lib.fptr(g), g.numel(), _lib.ptr(state), stream=stream)
         for i, (p, group, st) in enumerate(todo):
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             b1, b2 = group['betas']
-            _lib.check(lib.l2i_adam_guarded_f32(_lib.fptr(p), _lib.fptr(g), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']),
-                                                p.numel(), float(group['lr']), float(b1), float(b2), float(group['eps']), 1 if single else 0,
-                                                _lib.ptr(state), _lib.ptr(scale), float(sc.GROWTH if sc else 2.0), float(sc.BACKOFF if sc else 0.5),
-                                                int(sc.growth_interval if sc else 0), float(sc.max_scale if sc else 1.0),
-                                                1 if i == len(todo) - 1 else 0, stream), 'l2i_adam_guarded_f32')
+            _lib.call('l2i_adam_guarded_f32', _lib.fptr(p), _lib.fptr(g), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']),
+                      p.numel(), float(group['lr']), float(b1), float(b2), float(group['eps']), 1 if single else 0,
+                      _lib.ptr(state), _lib.ptr(scale), float(sc.GROWTH if sc else 2.0), float(sc.BACKOFF if sc else 0.5),
+                      int(sc.growth_interval if sc else 0), float(sc.max_scale if sc else 1.0),
+                      1 if i == len(todo) - 1 else 0, stream=stream)
         return None

@@ -24,12 +24,10 @@ BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 
 def conv_wgrad(x, gy, k, stride, pad):
     """dW [Cout,Cin,k,k] of a correlation y = conv(x, W, stride, pad) given gy = dL/dy."""
-    lib = _lib.load()
     b, cin, h, w = x.shape
     _, cout, oh, ow = gy.shape
     dw = torch.zeros(cout, cin, k, k, device=x.device, dtype=torch.float32)
-    _lib.check(lib.l2i_conv2d_wgrad_f32(_lib.fptr(dw), _lib.fptr(x), _lib.fptr(gy), b, cin, h, w, cout, oh, ow, k, k, stride, pad, pad,
-                                        _lib.stream_ptr()), 'l2i_conv2d_wgrad_f32')
+    _lib.call('l2i_conv2d_wgrad_f32', _lib.fptr(dw), _lib.fptr(x), _lib.fptr(gy), b, cin, h, w, cout, oh, ow, k, k, stride, pad, pad)
     return dw
 
 
@@ -44,11 +42,10 @@ class _BN:
         self.name = name
 
     def forward(self, x, residual=None, relu=True):
-        lib = _lib.load()
         b, c, h, w = x.shape
         n = b * h * w
         s = torch.zeros(2, c, device=x.device, dtype=torch.float64)
-        _lib.check(lib.l2i_bn_stats_f32(_lib.ptr(s[0]), _lib.ptr(s[1]), _lib.fptr(x), b, c, h * w, _lib.stream_ptr()), 'l2i_bn_stats_f32')
+        _lib.call('l2i_bn_stats_f32', _lib.ptr(s[0]), _lib.ptr(s[1]), _lib.fptr(x), b, c, h * w)
         mean64 = s[0] / n
         var64 = (s[1] / n - mean64 * mean64).clamp_(min=0.0)                    # biased variance normalises (BatchNorm2d.forward)
         mean, invstd = mean64.float(), torch.rsqrt(var64 + BN_EPS).float()
@@ -59,27 +56,24 @@ class _BN:
         scale = (self.weight * invstd).contiguous()
         shift = (self.bias - mean * scale).contiguous()
         y = torch.empty_like(x)
-        _lib.check(lib.l2i_bn_apply_f32(_lib.fptr(y), _lib.fptr(x), _lib.fptr(scale), _lib.fptr(shift), _lib.fptr(residual), int(relu), b, c, h * w,
-                                        _lib.stream_ptr()), 'l2i_bn_apply_f32')
+        _lib.call('l2i_bn_apply_f32', _lib.fptr(y), _lib.fptr(x), _lib.fptr(scale), _lib.fptr(shift), _lib.fptr(residual), int(relu), b, c, h * w)
         return y, (x, mean.contiguous(), invstd.contiguous())
 
     def backward(self, gy, saved, out_mask=None, want_masked=False):
         """gy = dL/d(output of relu(bn(x) [+ residual])); out_mask = that output when a ReLU followed.  Returns (dx, d weight, d bias,
         masked gy or None)."""
-        lib = _lib.load()
         x, mean, invstd = saved
         b, c, h, w = x.shape
         n = b * h * w
         s = torch.zeros(2, c, device=x.device, dtype=torch.float64)
-        _lib.check(lib.l2i_bn_bwd_reduce_f32(_lib.ptr(s[0]), _lib.ptr(s[1]), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
-                                             _lib.fptr(invstd), b, c, h * w, _lib.stream_ptr()), 'l2i_bn_bwd_reduce_f32')
+        _lib.call('l2i_bn_bwd_reduce_f32', _lib.ptr(s[0]), _lib.ptr(s[1]), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
+                  _lib.fptr(invstd), b, c, h * w)
         d_bias, d_weight = s[0].float(), s[1].float()
         m_dy, m_dyxh = (s[0] / n).float().contiguous(), (s[1] / n).float().contiguous()
         dx = torch.empty_like(x)
         gm = torch.empty_like(x) if want_masked else None
-        _lib.check(lib.l2i_bn_bwd_apply_f32(_lib.fptr(dx), _lib.fptr(gm), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
-                                            _lib.fptr(invstd), _lib.fptr(self.weight), _lib.fptr(m_dy), _lib.fptr(m_dyxh), b, c, h * w,
-                                            _lib.stream_ptr()), 'l2i_bn_bwd_apply_f32')
+        _lib.call('l2i_bn_bwd_apply_f32', _lib.fptr(dx), _lib.fptr(gm), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
+                  _lib.fptr(invstd), _lib.fptr(self.weight), _lib.fptr(m_dy), _lib.fptr(m_dyxh), b, c, h * w)
         return dx, d_weight, d_bias, gm
 
     def tensors(self):
