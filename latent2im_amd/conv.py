@@ -25,16 +25,14 @@ def h8_dtype():
     """Element type of the 16-bit path's h8 tensors under the current PRECISION ([r5]: 'f16' = IEEE fp16, everything else bf16)."""
     return torch.float16 if PRECISION == 'f16' else torch.bfloat16
 
-USE_WINOGRAD = _os.environ.get('L2I_WINOGRAD', '1') != '0'    # 3x3 stride-1 layers on maps >= 32 wide take the F(2x2,3x3) fp32 kernel
+USE_WINOGRAD = True    # 3x3 stride-1 layers on maps >= 32 wide take the F(2x2,3x3) fp32 kernel
 # [r4] Winograd F(4x4,3x3) (csrc/l2i_wino4.hip: 1.78x fewer MFMAs than F(2x2), error ~1e-6..1e-5 of max|y| instead of 3e-7) for the unmasked 3x3
 # stride-1 launches on maps >= 32 wide ([r5]: 32 x 16-pixel tiles below 64): 'all' = every eligible launch on the [r5] position-split kernel, 'r4' = those >= 64 wide on the round-4
-# kernel (kept for A/B runs: the two are bit-identical), 'off' = F(2x2) everywhere.  The parity suite runs 'all' and 'off'.
-WINO4_MODES = ('all', 'tall', 'r4', 'off')        # 'tall' ([r5], A/B): the position-split kernel on 64 x 16-pixel tiles / eight waves where the map has >= 16 rows
-WINO4 = _os.environ.get('L2I_WINO4', 'all')
+# kernel (kept as the comparator of the bit-identity test: the two are bit-identical), 'off' = F(2x2) everywhere.  The parity suite runs 'all' and 'off'.
+WINO4_MODES = ('all', 'tall', 'r4', 'off')        # 'tall' ([r5], the bit-identity test): the position-split kernel on 64 x 16-pixel tiles / eight waves where the map has >= 16 rows
+WINO4 = 'all'
 WINO4_R4_MIN_W = 64      # narrowest map the 'r4' mode sends to the round-4 kernel (its tile is 64 wide; the bit-identity test lowers this)
-if WINO4 not in WINO4_MODES:
-    raise ValueError('L2I_WINO4 must be one of %s, got %r' % (WINO4_MODES, WINO4))
-SPLIT_K = _os.environ.get('L2I_SPLIT_K', '1') != '0'    # 4x4 .. 16x16 maps: cut Cin into ranges computed by separate blocks (l2i.h: ksplit / ws)
+SPLIT_K = True    # 4x4 .. 16x16 maps: cut Cin into ranges computed by separate blocks (l2i.h: ksplit / ws)
 _WS = {}            # split-K workspaces, one per (device, stream)
 USE_FUSED_TRANSPOSED = True     # False: issue stride-2 transposed convs as four per-parity launches
 PROFILE = None      # bench.py sets this to a list: every launch then appends (start_event, end_event, algorithmic_flops, shape, entry point, kernel family)

@@ -34,10 +34,6 @@
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef L2I_C16_AHEAD
-#define L2I_C16_AHEAD 0
-#endif
-
 namespace s16 {
 // K x K window, stride S, WN 32-pixel rows per wave (TH = 4 WN output rows per block, 32 columns).
 // TR != 0: stride-2 TRANSPOSED 3x3 conv (TR = 1: pad 0, TR = 2: pad 1), all four output parities from one staged tile: the tile is
@@ -202,16 +198,6 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
     // one pixel column (px of the 4-pixel vectors) of every item of the prefetched tile -> LDS stage: mask, style scale, split, two 16-byte stores.
     // The K > 1 pipeline spreads the four columns over the MFMA steps of the chunk's later phases (VALU in the shadow of the matrix pipe).
     auto commit_px = [&](int stage, int px) {
-#ifdef L2I_ABL_NOCOMMIT
-        return;
-#endif
-#ifdef L2I_ABL_LOADSONLY                                   // keep the loads alive, no VALU, no LDS stores
-#pragma unroll
-        for (int u = 0; u < G::NS; ++u)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) asm volatile("" ::"v"(xin[u][e]));
-        return;
-#endif
         if (G::GATHER && (px & 1)) return;                 // 1x1 stride 2 reads even columns only
         u32x4* ih = in_st + stage * IN_STAGE;
         u32x4* il = ih + IN_PLANE;
@@ -227,12 +213,8 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
             u32x4 hi, lo;
             split8b(v, hi, lo);
             const int s = lslot[u] + ((S == 2) ? ((G::GATHER ? 0 : (px & 1) * G::RPH) + (px >> 1)) : px);
-#ifdef L2I_ABL_NOSTORE
-            asm volatile("" ::"v"(hi), "v"(lo), "v"(s));
-#else
             ih[s] = hi;
             il[s] = lo;
-#endif
         }
     };
     auto commit = [&](int stage) {
@@ -294,7 +276,7 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
 #pragma unroll
             for (int n = 0; n < WN; ++n) ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[m], f.bh[n], ac[m][n], 0, 0, 0);
     };
-    // One phase: NSTEP MFMA steps; the fragments of step s+1 are read while step s is on the matrix pipe (two register sets), and
+    // One phase: NSTEP MFMA steps; the fragments of step s+1 are read into the same register set once step s's MFMAs are issued, and
     // `px_of(step)` >= 0 names the pixel column of the NEXT chunk's tile that is committed to `commit_stage` beside that step's MFMAs.
     auto mfma_phase = [&](int in_stage, int w_stage, auto ky_t, int commit_stage, auto px0_t, auto px1_t, auto px2_t) {
         constexpr int px0 = decltype(px0_t)::value, px1 = decltype(px1_t)::value, px2 = decltype(px2_t)::value;   // compile time: no branch in the MFMA stream
@@ -307,16 +289,14 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
         const u32x4* il = ih + IN_PLANE;
         const u32x4* wh = w_st + w_stage * W_STAGE + abase;
         const u32x4* wl = wh + WSLOTS;
-        constexpr bool AHEAD = (L2I_C16_AHEAD != 0);
-        Frag f[2];
-        load_frags(f[0], ih, il, wh, wl, 0);
+        Frag f;
+        load_frags(f, ih, il, wh, wl, 0);
 #pragma unroll
         for (int stp = 0; stp < NSTEP; ++stp) {
-            if (AHEAD && stp + 1 < NSTEP) load_frags(f[(stp + 1) & 1], ih, il, wh, wl, stp + 1);
             constexpr int pxs[3] = {px0, px1, px2};
             if constexpr (NSTEP == 3) { if (pxs[stp] >= 0) commit_px(commit_stage, pxs[stp]); }
-            mma(f[AHEAD ? (stp & 1) : 0], acc[TR ? py * 2 + ((stp + PADT) & 1) : 0]);
-            if (!AHEAD && stp + 1 < NSTEP) load_frags(f[0], ih, il, wh, wl, stp + 1);
+            mma(f, acc[TR ? py * 2 + ((stp + PADT) & 1) : 0]);
+            if (stp + 1 < NSTEP) load_frags(f, ih, il, wh, wl, stp + 1);
         }
     };
 
@@ -334,18 +314,10 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
         // the DMA of this phase's weights has landed; register loads issued after it (first phase of a chunk, K > 1) stay in flight
         if (K > 1 && ky == 1 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLOADS) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef L2I_ABL_NOBARRIER
         __syncthreads();
-#endif
-#ifndef L2I_ABL_NOLOADS
         if (ky == 0 && more) issue_scales((ch + 1) * G::CK);
-#endif
-#ifndef L2I_ABL_NODMA
         if (ph + 1 < nphases) dma_w(ky + 1 < K ? ch : ch + 1, ky + 1 < K ? ky + 1 : 0, (ph + 1) & 1);
-#endif
-#ifndef L2I_ABL_NOLOADS
         if (ky == 0 && more) issue_loads((ch + 1) * G::CK);
-#endif
     };
     for (int ch = 0; ch < L.nchunks; ++ch) {
         const bool more = ch + 1 < L.nchunks;

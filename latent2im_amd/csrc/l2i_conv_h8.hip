@@ -21,7 +21,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
@@ -149,9 +148,6 @@ struct H8Out {
             for (int e = 0; e < 8; ++e) v[e] += o[e];
         }
         const u32x4 out = {cvt_pk_bf16_h8(v[0], v[1]), cvt_pk_bf16_h8(v[2], v[3]), cvt_pk_bf16_h8(v[4], v[5]), cvt_pk_bf16_h8(v[6], v[7])};
-#ifdef L2I_H8_ABLATE_STORE                                 // timing ablation: the epilogue's arithmetic without its global store
-        if (out.x == 0x12345678u && out.y == 0x9abcdef0u)
-#endif
         reinterpret_cast<u32x4*>(p.y)[slot] = out;
         if (p.mask_out) p.mask_out[slot] = (uint8_t)h8_sign_byte(out);
         if (p.sq_ref) {                                            // ContentLoss value of a VGG tap on the ROUNDED output (what the next layer reads)
@@ -167,7 +163,7 @@ struct H8Out {
 // RELU_IN: pro(x) = max(x, 0) on the B fragments (VGG-19: a conv reads the PRE-ReLU tap of the layer below, which is what the ContentLoss
 // and the backward masks need in HBM): four v_pk_max_i16 per fragment — a negative bf16 is a negative int16, so the integer max with 0 is
 // the ReLU (and -0 -> +0) — beside the bf16 MFMAs, whose pipe the VALU does not share
-// Measured, not kept (round 3, tools/probes/h8_ablate*.sh): a "deep" variant for the low-Cin 3x3 layers — three tile stages requested two chunks ahead,
+// Measured, not kept (round 3, timing-ablation builds since removed): a "deep" variant for the low-Cin 3x3 layers — three tile stages requested two chunks ahead,
 // a chunk's whole 3x3 weight slice per stage with ONE barrier per chunk, tile DMA issued by waves 0-1 and weight DMA by waves 2-3 so that a wave's
 // in-order vmcnt never makes an L2-hit weight slice wait behind an HBM tile.  72 KB of LDS = two blocks per CU instead of four: 9-15 % SLOWER
 // on every layer (64 -> 64 @1024^2 0.94 against 0.83 ms).  The timing ablations say why nothing memory-side helps: with no DMA at all the launch
@@ -248,9 +244,6 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
         }
     }
     auto dma_in = [&](int chunk, int stage) {
-#ifdef L2I_H8_ABLATE_TILE                                  // timing ablation: no tile traffic (the MFMAs run on whatever the LDS holds)
-        return;
-#endif
         const unsigned soff = (unsigned)chunk * G::NH * plane_b;
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(in_st + stage * IN_STAGE);
 #pragma unroll
@@ -272,9 +265,6 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
         wvoff[t] = (unsigned)((((st * K * K + tap) * 2 + hf) * p.CoutP + m0 + i) * 16);
     }
     auto dma_w = [&](int chunk, int ky, int stage_slot) {       // stage_slot: first LDS slot of the phase's weights (relative to w_st)
-#ifdef L2I_H8_ABLATE_W                                     // timing ablation: no weight traffic
-        return;
-#endif
         const unsigned soff = (unsigned)((((size_t)chunk * G::KS * K * K + ky * K) * 2) * p.CoutP * 16);
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage_slot);
 #pragma unroll
@@ -321,18 +311,10 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
             for (int ks = 0; ks < G::KS; ++ks) {
                 bf16x8 af[WM], bf[WN];
 #pragma unroll
-#ifdef L2I_H8_ABLATE_LDSREAD                               // timing ablation: no fragment reads
-                for (int m = 0; m < WM; ++m) af[m] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)kx, (unsigned)ks, (unsigned)m, (unsigned)lane});
-#else
                 for (int m = 0; m < WM; ++m) af[m] = __builtin_bit_cast(bf16x8, wh[((kx * G::KS + ks) * 2) * BM + m * 32]);
-#endif
 #pragma unroll
                 for (int n = 0; n < WN; ++n) {
-#ifdef L2I_H8_ABLATE_LDSREAD
-                    u32x4 raw = u32x4{(unsigned)n, (unsigned)kx, (unsigned)j, 7u};
-#else
                     u32x4 raw = ih[ks * 2 * G::HSTRIDE + n * rstep_out * G::RP + coloff];
-#endif
                     if constexpr (RELU_IN) {
                         asm("v_pk_max_i16 %0, %0, 0" : "+v"(raw.x)); asm("v_pk_max_i16 %0, %0, 0" : "+v"(raw.y));
                         asm("v_pk_max_i16 %0, %0, 0" : "+v"(raw.z)); asm("v_pk_max_i16 %0, %0, 0" : "+v"(raw.w));
@@ -343,11 +325,7 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
                 for (int m = 0; m < WM; ++m)
 #pragma unroll
                     for (int n = 0; n < WN; ++n)
-#ifdef L2I_H8_ABLATE_MFMA                                  // timing ablation (tools/probes/h8_ablate.sh): fragments are read, no matrix work
-                        acc[TR ? py * 2 + ((kx + PADT) & 1) : 0][m][n][0] += __builtin_bit_cast(f32x4_, af[m])[0] * __builtin_bit_cast(f32x4_, bf[n])[0];
-#else
                         acc[TR ? py * 2 + ((kx + PADT) & 1) : 0][m][n] = H8_MFMA(af[m], bf[n], acc[TR ? py * 2 + ((kx + PADT) & 1) : 0][m][n], 0, 0, 0);
-#endif
             }
         }
     };
@@ -366,9 +344,7 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
         // weights of phase (ch, 1), stays in flight across that phase's barrier
         if (K > 1 && ky == 1 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::NPW) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef L2I_H8_ABLATE_BARRIER
         __syncthreads();
-#endif
         if (ph + 1 < nphases) dma_w(ky + 1 < K ? ch : ch + 1, ky + 1 < K ? ky + 1 : 0, ((ph + 1) & 1) * WSLOTS);
         if (ky == 0 && more) dma_in(ch + 1, (ch + 1) & 1);
     };
@@ -389,19 +365,6 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
         static_assert(!OUT32 || TR == 0, "fp32 NCHW output: correlations only");
         __syncthreads();                                   // the stages become the epilogue's transpose strips
         l2i_epilogue_32x32<WM, WN>(p, acc[0], reinterpret_cast<float*>(smem4), b, m0, oy0, ox0, L.vec_epi != 0);
-#ifdef L2I_H8_ABLATE_EPI                                   // timing ablation: no epilogue (one dword per lane keeps the accumulators alive)
-    } else if (true) {
-        float t = 0.f;
-#pragma unroll
-        for (int a = 0; a < NACC; ++a)
-#pragma unroll
-            for (int m = 0; m < WM; ++m)
-#pragma unroll
-                for (int n = 0; n < WN; ++n)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t += acc[a][m][n][r];
-        if (t == 12345.678f) reinterpret_cast<float*>(p.y)[tid] = t;
-#endif
     } else if (L.lean_epi) {
         // Lean epilogue (forward layers and plain gradient convs: per-channel vectors and the per-pixel noise only).  On the low-Cin layers the
         // general epilogue below was as many VALU instructions as the K loop was MFMA cycles (7 VALU per MFMA on 64 -> 64 @1024^2, SQ counters:
@@ -505,9 +468,6 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
                     const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
                     unsigned off;
                     const bool ok = pix(n, a, off);
-#ifdef L2I_H8_ABLATE_STORE
-                    if (out.x == 0x12345678u && out.y == 0x9abcdef0u)
-#endif
                     if (ok && gok) yq[off] = out;
                     if (!EXTRA && p.mask_out && ok && gok) p.mask_out[((size_t)b * cg_out + g0 + 4 * m + 2 * pr) * plane + off] = (uint8_t)h8_sign_byte(out);
                     if (EXTRA && p.sq_ref && ok && gok) {          // [r5] ContentLoss value of a VGG tap on the ROUNDED output, as in the general epilogue
@@ -598,10 +558,9 @@ static int launch_h8(const l2i_conv_params& p, hipStream_t st) {
     L.total = (int)total;
     L.nchunks = p.Cin / G::CK;
     L.vec_epi = (OUT32 && l2i_epilogue_vec_ok(p)) ? 1 : 0;
-    static const int lean_env = getenv("L2I_H8_LEAN") ? atoi(getenv("L2I_H8_LEAN")) : 1;
     // identity / ReLU / leaky ReLU as max(g * gpos, g * gneg) needs 0 <= gneg <= gpos
     const bool gains_ok = p.out_gain > 0.f && (p.act != L2I_ACT_LRELU || (p.act_gain > 0.f && p.act_slope >= 0.f && p.act_slope <= 1.f));
-    bool lean = !OUT32 && lean_env && !p.out_mask && !p.residual && !p.accumulate && gains_ok && (size_t)p.OHf * p.OWf < 0xFFFFFFFFull;
+    bool lean = !OUT32 && !p.out_mask && !p.residual && !p.accumulate && gains_ok && (size_t)p.OHf * p.OWf < 0xFFFFFFFFull;
     if (p.sq_ref && !CAN_EXTRA) lean = false;              // the ContentLoss sum rides on the lean epilogue of the EXTRA instantiations only; elsewhere: the general epilogue
     L.lean_epi = lean ? 1 : 0;
     const bool extra = CAN_EXTRA && lean && (p.rgb_w || p.sq_ref);
@@ -666,11 +625,10 @@ extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     bool wide = (p.CoutP % 64) == 0;
     {   // [r5] small maps: with 64-channel blocks a launch of a <= 32^2 map has fewer blocks than the chip has CUs and every block walks its 48 - 96
-        // phases alone on its CU (1 wave per SIMD: every barrier and DMA wait exposed); 32-channel blocks double the blocks (L2I_H8_SMALL_WM1=0: off)
-        static const int small_env = getenv("L2I_H8_SMALL_WM1") ? atoi(getenv("L2I_H8_SMALL_WM1")) : 1;
+        // phases alone on its CU (1 wave per SIMD: every barrier and DMA wait exposed); 32-channel blocks double the blocks
         const int th = (p.KH == 3 && p.stride == 2) ? 4 : 8;
         const long blocks64 = (long)p.B * ((p.OW + 31) / 32) * ((p.OH + th - 1) / th) * ((p.CoutP + 63) / 64);
-        if (small_env && wide && !p.out_f32 && !p.rgb_w && blocks64 < 256) wide = false;      // (measured, batch 8, 512 -> 512 3x3: 4^2 34.8 -> 26.5 us, 8^2 35.7 -> 27.5, 16^2 37.8 -> 30.4; 32^2 = 256 blocks: no difference)
+        if (wide && !p.out_f32 && !p.rgb_w && blocks64 < 256) wide = false;      // (measured, batch 8, 512 -> 512 3x3: 4^2 34.8 -> 26.5 us, 8^2 35.7 -> 27.5, 16^2 37.8 -> 30.4; 32^2 = 256 blocks: no difference)
     }
     if (p.out_f32) {                                       // fp32 NCHW output (gradients landing on images, the last layer in front of an fp32 consumer)
         if (p.in_mask) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: ReLU-on-load needs the h8 output");
@@ -684,8 +642,7 @@ extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
     // K chunk of the 3x3 stride-1 layers: 16 channels (one MFMA step per tap) — half the LDS per block puts FOUR blocks on a CU, and it is the number
     // of tiles in flight that fills the memory pipeline on the HBM-bound high-resolution layers (64 -> 64 @1024^2: 738 against 663 TFLOP/s) and
     // hides the per-phase barriers on the others (512 -> 512 @64^2: 1188 against 1135); 32 channels only for 512 channels on <= 32^2 maps
-    static const int ks_env = getenv("L2I_H8_KS") ? atoi(getenv("L2I_H8_KS")) : 0;
-    const bool ks1 = (p.Cin % 32) != 0 || (ks_env ? ks_env == 1 : (p.Cin <= 256 || p.OW > 32));    // measured per shape (tools/probes/h8_bench.py): 16 wins everywhere but 512 channels on <= 32^2 maps
+    const bool ks1 = (p.Cin % 32) != 0 || p.Cin <= 256 || p.OW > 32;    // measured per shape (tools/probes/h8_bench.py): 16 wins everywhere but 512 channels on <= 32^2 maps
     if (p.in_mask) {                                       // ReLU-on-load: the 3x3 stride-1 layers of VGG-19
         if (p.KH == 3 && p.stride == 1) {
             if (ks1) return wide ? launch_h8<2, 2, 3, 1, 0, false, true, 1>(p, st) : launch_h8<1, 2, 3, 1, 0, false, true, 1>(p, st);
@@ -697,11 +654,8 @@ extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
     if ((p.Cin % 32) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: Cin % 32 == 0 except for 3x3 stride-1 layers (Cin % 16 == 0)");
     if (p.KH == 3 && p.stride == 1) return wide ? launch_h8<2, 2, 3, 1, 0, false>(p, st) : launch_h8<1, 2, 3, 1, 0, false>(p, st);
     if (p.KH == 1 && p.stride == 1) return wide ? launch_h8<2, 2, 1, 1, 0, false>(p, st) : launch_h8<1, 2, 1, 1, 0, false>(p, st);
-    if (p.KH == 3 && p.stride == 2) {                      // 16-channel chunks: the 9 x 65-slot tile of a 32-channel chunk leaves one block per CU
-        static const int s2_env = getenv("L2I_H8_S2KS") ? atoi(getenv("L2I_H8_S2KS")) : 1;
-        if (s2_env == 1) return wide ? launch_h8<2, 1, 3, 2, 0, false, false, 1>(p, st) : launch_h8<1, 1, 3, 2, 0, false, false, 1>(p, st);
-        return wide ? launch_h8<2, 1, 3, 2, 0, false>(p, st) : launch_h8<1, 1, 3, 2, 0, false>(p, st);
-    }
+    // 16-channel chunks: the 9 x 65-slot tile of a 32-channel chunk leaves one block per CU
+    if (p.KH == 3 && p.stride == 2) return wide ? launch_h8<2, 1, 3, 2, 0, false, false, 1>(p, st) : launch_h8<1, 1, 3, 2, 0, false, false, 1>(p, st);
     return wide ? launch_h8<2, 2, 1, 2, 0, false>(p, st) : launch_h8<1, 2, 1, 2, 0, false>(p, st);
 }
 

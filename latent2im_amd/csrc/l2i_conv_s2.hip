@@ -2,7 +2,7 @@
 // 574-583; ResNet-50's three strided 3x3s; the input-gradient of a generator up layer, networks.py:246-255) on the fp32 matrix cores with BOTH
 // operands staged global -> LDS by DMA.  The generic kernel of l2i_conv.hip carries this shape through registers (12 dword loads per thread and chunk,
 // a commit pass, two barriers per chunk; 62 % matrix-pipe busy, 20-25 % LDS bank conflicts: profiles/r03_conv_convt_counters.txt); the reviews of
-// rounds 2-4 asked for the register-free path and an A/B on the step's shapes (tools/probes/conv_s2_ab.py, profiles/r05_conv_s2_ab.txt).
+// rounds 2-4 asked for the register-free path and an A/B on the step's shapes (profiles/r05_conv_s2_ab.txt).
 //
 // Same mapping as conv_mfma_kernel<2,2>: v_mfma_f32_32x32x2_f32, block = 64 output channels x (8 rows x 32 columns) of output pixels, wave w owns
 // output rows 2 w, 2 w + 1; the two lane halves of the K = 2 MFMA take the two channels of a chunk.  What is different:
@@ -16,7 +16,6 @@
 // Epilogue: the shared fused one (l2i_epilogue.h).  Unmasked launches on maps >= 32 wide; everything else stays on l2i_conv.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_epilogue.h"
@@ -170,8 +169,6 @@ __global__ __launch_bounds__(256, 3) void conv3x3s2_dma_kernel(const l2i_conv_pa
 }
 
 bool l2i_conv3x3s2_eligible(const l2i_conv_params& p) {
-    static const bool off = getenv("L2I_CONV_S2_DMA") && atoi(getenv("L2I_CONV_S2_DMA")) == 0;      // A/B switch (tools/probes/conv_s2_ab.py)
-    if (off) return false;
     return p.KH == 3 && p.KW == 3 && p.stride == 2 && p.oy_step == 1 && p.ox_step == 1 && !p.in_mask && !p.ws && p.ksplit <= 1 && p.pad_x == p.pad_y &&
            (p.pad_x == 0 || (p.pad_x == 1 && (p.W % 4) == 0)) && (p.Cin % cs2::CK) == 0 && p.Cin >= 8 && ((p.CoutP % cs2::BM) == 0 || p.CoutP >= 160) && p.OW >= 32 && !p.sq_ref &&      // (a block is 64 channels wide: 32-channel layers keep the generic kernel's BM = 32 tile)
           

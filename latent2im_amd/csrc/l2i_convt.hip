@@ -18,11 +18,10 @@
 // positions wide): the input tile goes global -> LDS by dword DMA as well — a dense [CK][IH][IW] image, one channel plane per wave in turn, 64
 // elements per instruction, the plane pitch padded so that the two lane halves of a fragment read land on disjoint bank halves — into the other
 // stage while the current chunk multiplies: no staging registers (36 fewer per lane), no commit pass.  The rounds 2-4 reviews asked for this path
-// and an A/B on the step's shapes: tools/probes/convt_ab.py, profiles/r05_convt_ab.txt; L2I_CONVT_DMA=0 restores the register path.
+// and an A/B on the step's shapes against the register path: profiles/r05_convt_ab.txt.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
 
@@ -481,8 +480,7 @@ static int launch_convt(const l2i_conv_params& p, hipStream_t st) {
     L.plane = (TB * L.planeS + 3) & ~3;
     L.rows_c = TB * L.IH;
     L.nslots = 0;
-    static const bool dma_env = !(getenv("L2I_CONVT_DMA") && atoi(getenv("L2I_CONVT_DMA")) == 0);
-    const bool dma_in = dma_env && K == 3 && !p.in_mask && TB == 1 && Tx >= 32 && !(p.ksplit > 1 && p.ws) && L.IH * L.IW <= 6 * 64 &&
+    const bool dma_in = K == 3 && !p.in_mask && TB == 1 && Tx >= 32 && !(p.ksplit > 1 && p.ws) && L.IH * L.IW <= 6 * 64 &&
                         (size_t)p.Cin * p.H * p.W * sizeof(float) < 0x7FFF0000ull;
     if (dma_in) {                                         // dense planes, one per group of DMA slots; the pitch is fixed below once CK is known
         L.IWp = L.IW;

@@ -13,7 +13,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
 
@@ -253,7 +252,6 @@ int l2i_launch_gemm1x1(const l2i_conv_params& p, hipStream_t st) {
     // epilogue, and four 64-channel blocks per CU overlap one block's stores with three K loops better than three 128-channel blocks
     // (measured per shape: 0.185 / 0.210 / 0.304 ms against 0.209 / 0.236 / 0.317 at 256->1024 @64^2, 128->512 @128^2, 64->256 @256^2)
     if (!p.in_mask && p.Cin * 4 <= p.Cout) wide = false;
-    if (const char* e = getenv("L2I_GEMM_BM")) wide = (p.CoutP % 128) == 0 && atoi(e) == 128;          // tuning override (tools/bench_layers.py)
     const int BM = wide ? 128 : 64;
     const int mblocks = p.CoutP / BM;
     const long total = (long)p.B * tiles * mblocks;

@@ -13,16 +13,15 @@
 //     epilogue: the matrix pipe is what the wave waits for, and that much matrix time per chunk covers an HBM round trip with one chunk of prefetch;
 //   * weights (the chunk's 32 rows of W1 and 32 K rows of W2) go through two shared LDS stages by 16-byte DMA; the identity map of the chunk (32 channels x the
 //     wave's pixels) by 16-byte DMA into a per-wave ring and is read back per lane; the wide map is stored once, 128 contiguous bytes per half wave and channel.
-// Two tilings: 128-pixel blocks, two per CU (default), or 256-pixel blocks, one per CU with the accumulators in AGPRs.  Where the time goes (layer1, batch 8:
+// One tiling: 128-pixel blocks, two per CU.  Where the time goes (layer1, batch 8:
 // 400 us against 530 for the two launches; floors: 218 us of fp32 MFMA at the nominal clock, 268 us of HBM at 5 TB/s): the kernel is matrix-bound at the
 // same ~0.65 of the nominal peak as the GEMM kernel (clock under fp32 MFMA load, the epilogue's VALU on the shared issue slot, a block's prologue); what the
 // fusion removes is the byte time the two launches add on top.  Inside the training step other streams fill those stalls anyway: c3 +0.2 .. 0.5 %
-// (tools/ab/r06_pair_f32.sh), against +23 % / +16 % in isolation.
+// (round-6 A/B), against +23 % / +16 % in isolation.
 // The second conv accumulates channel pairs in another order than l2i_conv2d_f32's GEMM kernel ({c, c + 4} instead of {c, c + 1}): results agree to fp32
 // rounding (tests: 1e-5 of the map's magnitude), not bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
 
@@ -239,16 +238,10 @@ extern "C" int l2i_conv1x1_pair_f32(const l2i_conv_params* first, const l2i_conv
     hipStream_t st = (hipStream_t)stream;
     const int K1 = p1.Cin, C3 = p2.Cout;
     if ((npix % 256) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv1x1_pair_f32: H * W must be a multiple of 256");
-    // (measured, tools/ab/r06_pair_f32_variant.sh: isolated the two tilings are within 3 % of each other — 396 / 407 us at layer1, 345 / 337 at layer2 against 530 / 394
+    // 128-pixel blocks, two per CU.  (Measured in round 6 against 256-pixel blocks, one per CU, since removed: isolated the two tilings are within 3 % of each other — 396 / 407 us at layer1, 345 / 337 at layer2 against 530 / 394
     //  for the two launches — inside the step, where other streams' kernels share the CUs, the smaller blocks are ahead: 80.6 - 80.8 against 80.0 - 80.6 images/s)
-    static const int var_env = getenv("L2I_PAIR_F32_VARIANT") ? atoi(getenv("L2I_PAIR_F32_VARIANT")) : 1;      // 1: 128-pixel blocks, two per CU (default); 0: 256-pixel blocks, one per CU
-    if (var_env == 1) {
-        if (K1 == 64 && C3 == 64) return launch_pair_f32<64, 2, 1, 2>(p1, p2, st);
-        if (K1 == 64 && C3 == 128) return launch_pair_f32<64, 4, 1, 2>(p1, p2, st);
-        if (K1 == 128 && C3 == 128) return launch_pair_f32<128, 4, 1, 2>(p1, p2, st);
-    }
-    if (K1 == 64 && C3 == 64) return launch_pair_f32<64, 2, 2, 1>(p1, p2, st);
-    if (K1 == 64 && C3 == 128) return launch_pair_f32<64, 4, 2, 1>(p1, p2, st);
-    if (K1 == 128 && C3 == 128) return launch_pair_f32<128, 4, 2, 1>(p1, p2, st);
+    if (K1 == 64 && C3 == 64) return launch_pair_f32<64, 2, 1, 2>(p1, p2, st);
+    if (K1 == 64 && C3 == 128) return launch_pair_f32<64, 4, 1, 2>(p1, p2, st);
+    if (K1 == 128 && C3 == 128) return launch_pair_f32<128, 4, 1, 2>(p1, p2, st);
     return l2i_set_error(L2I_E_UNSUPPORTED, "conv1x1_pair_f32: built for (Cin1, Cout2) = (64, 64), (64, 128), (128, 128)");
 }

@@ -34,7 +34,6 @@
 // single part is worth more than 10 us of the 72), like the mid-size launches of conv_h8_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_h8_common.h"
@@ -247,9 +246,6 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
         }
     }
     auto dma_w = [&](int c, int stage) {
-#ifdef L2I_PAIR_ABL_W                                      // timing ablations (tools/probes/pair_ablate.sh): results are wrong by construction
-        if (c > 0) return;
-#endif
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage * WSTAGE);
         const unsigned so1 = (unsigned)c * 32u * 16u, so2 = (unsigned)c * 64u * (unsigned)p2.CoutP;       // W2 slice: K steps 2 c, 2 c + 1 = rows (2 c) * 2 .. of [kstep][half][CoutP] slots
 #pragma unroll
@@ -272,9 +268,6 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
     for (int n = 0; n < WN; ++n) rvoff[n] = ((unsigned)half * npix + pixn[n] + (unsigned)j) * 16u;
     u32x4* const r_mine = r_st + wave * (RS * RPW * 64);
     auto dma_r = [&](int c) {
-#ifdef L2I_PAIR_ABL_RES
-        return;
-#endif
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(r_mine + (c % RS) * (RPW * 64));
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr)
@@ -334,9 +327,7 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
         if (c == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (RDIST == 2 && c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RPW) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RPW) : "memory");
-#ifndef L2I_PAIR_ABL_BAR
         __syncthreads();
-#endif
         if (c + 1 < nch) dma_w(c + 1, (c + 1) % WST);
         if (c + RDIST < nch) dma_r(c + RDIST);
 
@@ -351,11 +342,7 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
         for (int ks = 0; ks < KB; ++ks) {
             const bf16x8 af = __builtin_bit_cast(bf16x8, w1s[ks * 64]);
 #pragma unroll
-#ifdef L2I_PAIR_ABL_MFMA1
-            for (int n = 0; n < WN; ++n) accB[n][0] += __builtin_bit_cast(f32x4_, af)[0] * __builtin_bit_cast(f32x4_, xf[ks][n])[0];
-#else
             for (int n = 0; n < WN; ++n) accB[n] = H8_MFMA(af, xf[ks][n], accB[n], 0, 0, 0);
-#endif
         }
         // ---- its epilogue: (* mask) + bias + operand (* mask), ReLU, store, sign byte; the packed slots are the second conv's B fragments ----
         const u32x4* rq = r_mine + (c % RS) * (RPW * 64) + lane;
@@ -394,9 +381,6 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
                 }
                 const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
                 const size_t off = (size_t)(4 * c + 2 * pr) * npix + pixn[n];
-#ifdef L2I_PAIR_ABL_STORE
-                if (out.x == 0x12345678u && out.y == 0x9abcdef0u)
-#endif
                 y1b[off] = out;
                 if (sign1) s1b[off] = (uint8_t)h8_sign_byte(out);
                 frag[n] = __builtin_bit_cast(bf16x8, out);
@@ -406,11 +390,7 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
             for (int m = 0; m < MC; ++m) {
                 const bf16x8 af = __builtin_bit_cast(bf16x8, w2s[pr * 2 * C3 + m * 32]);
 #pragma unroll
-#ifdef L2I_PAIR_ABL_MFMA2
-                for (int n = 0; n < WN; ++n) accC[m][n][0] += __builtin_bit_cast(f32x4_, af)[0] * __builtin_bit_cast(f32x4_, frag[n])[0];
-#else
                 for (int n = 0; n < WN; ++n) accC[m][n] = H8_MFMA(af, frag[n], accC[m][n], 0, 0, 0);
-#endif
             }
         }
     }
@@ -507,8 +487,7 @@ static int pair_dispatch(const l2i_conv_params* head, const l2i_conv_params& p1,
     const int KB = p1.Cin / 16, MC = p2.Cout / 32;
     const bool masked = p1.out_mask != nullptr;
     if (p1.res_mask && !masked) return l2i_set_error(L2I_E_UNSUPPORTED, "conv pair h8: res_mask without out_mask");
-    static const int var_env = getenv("L2I_PAIR_VARIANT") ? atoi(getenv("L2I_PAIR_VARIANT")) : -1;
-    const int v = var_env >= 0 ? var_env : variant;      // 0: two 32-pixel rows per wave (256-pixel tiles); 1: one (128-pixel tiles, three blocks per CU)
+    const int v = variant;      // 0: two 32-pixel rows per wave (256-pixel tiles); 1: one (128-pixel tiles, three blocks per CU)
     int wn;
     if (head) {
         const l2i_conv_params& p0 = *head;

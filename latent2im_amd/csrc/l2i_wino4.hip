@@ -22,76 +22,12 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// timing-ablation switches (tools/probes/w4_ablate.sh: results are wrong by construction)
-#ifdef L2I_W4_ABLATE_DMA
-#define W4_NODMA 1
-#else
-#define W4_NODMA 0
-#endif
-#ifdef L2I_W4_ABLATE_XF
-#define W4_NOXF 1
-#else
-#define W4_NOXF 0
-#endif
-#ifdef L2I_W4_ABLATE_MFMA
-#define W4_NOMFMA 1
-#else
-#define W4_NOMFMA 0
-#endif
-#ifdef L2I_W4_ABLATE_LDSD
-#define W4_NOLDSD 1
-#else
-#define W4_NOLDSD 0
-#endif
-#ifdef L2I_W4_ABLATE_EPI
-#define W4_NOEPI 1
-#else
-#define W4_NOEPI 0
-#endif
-#ifdef L2I_W4_ABLATE_UREAD
-#define W4_NOUREAD 1
-#else
-#define W4_NOUREAD 0
-#endif
-#ifdef L2I_W4_ABLATE_BAR
-#define W4_NOBAR 1
-#else
-#define W4_NOBAR 0
-#endif
-
-#ifdef L2I_W4_ABLATE_HOTU
-#define W4_HOTU 1
-#else
-#define W4_HOTU 0
-#endif
-#ifdef L2I_W4_ABLATE_HOTR
-#define W4_HOTR 1
-#else
-#define W4_HOTR 0
-#endif
-#ifdef L2I_W4_ABLATE_NOUDMA
-#define W4_NOUDMA 1
-#else
-#define W4_NOUDMA 0
-#endif
-#ifdef L2I_W4_ABLATE_NORDMA
-#define W4_NORDMA 1
-#else
-#define W4_NORDMA 0
-#endif
-#ifdef L2I_W4_UPF
-#define W4_UPF 1
-#else
-#define W4_UPF 0
-#endif
 
 namespace w4 {
 constexpr int BM = 16, CK = 4;
@@ -234,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
         asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %6 offen lds\n\t"
                      "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %7 offen lds\n\t"
                      "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %8 offen lds"
-                     :: "v"(wvoff), "s"((on && !W4_NODMA) ? rs_w : rs_null), "s"((on && w0 && !W4_NODMA) ? rs_w : rs_null),
+                     :: "v"(wvoff), "s"(on ? rs_w : rs_null), "s"((on && w0) ? rs_w : rs_null),
                         "s"(base), "s"(base + 4096u), "s"(w0 ? base + 8192u : lds_dump), "s"(so), "s"(so + 4096u), "s"(so + 8192u) : "memory");
     };
     auto issue_raw = [&](int c, int cr, int rst, bool on) {
@@ -248,7 +184,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
                      "s_mov_b32 m0, %6\n\ts_nop 0\n\t"
                      "buffer_load_dword %4, %7, %8 offen lds"
                      :: "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "s"(base), "s"(wave_u < 3 ? base + 4096u : lds_dump),
-                        "s"((on && !W4_NODMA) ? rs_x : rs_null), "s"(so) : "memory");
+                        "s"(on ? rs_x : rs_null), "s"(so) : "memory");
     };
 
     if constexpr (SCALE) {
@@ -261,7 +197,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
 
     // ---- input transform, vertical pass of one column pair: rows P[0..5] (packed columns (2 cp, 2 cp + 1)) -> B^T P ----
     auto colpass = [&](f32x2 (&P)[6], f32x2 sc) {
-        if (W4_NOXF) return;
         if constexpr (RELU) {
             const f32x2 krelu = {W4_RELU_SCALE, W4_RELU_SCALE};
 #pragma unroll
@@ -286,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
     const unsigned pa0 = lds_raw + (unsigned)((kq * PLANE + (4 * wave) * IW + 4 * n) * 4);
     auto load_pair = [&](f32x2 (&P)[6], unsigned pa, int cp) {
 #pragma unroll
-        for (int r = 0; r < 6; ++r) P[r] = W4_NOLDSD ? f32x2{(float)cp, 1.f} : w4_lds_b64(pa, (r * IW + 2 * cp) * 4);
+        for (int r = 0; r < 6; ++r) P[r] = w4_lds_b64(pa, (r * IW + 2 * cp) * 4);
     };
     auto scale_of = [&](int cch) -> f32x2 {            // style scale of channel 4 cch + kq (chunks past the end read a valid, unused entry)
         if constexpr (SCALE) { const int ci = min(cch * CK + kq, p.Cin - 1); const float s = stab[ci]; return f32x2{s, s}; }
@@ -338,14 +273,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
         const float2* ub = reinterpret_cast<const float2*>(ubuf + ucur * UST + UA) + lane;         // [i][64 lanes] float2: positions (i, 4..5)
         const unsigned pa = pa0 + (unsigned)(rnext * RAWST * 4);
         const f32x2 scn = scale_of(ch + 1);
-        float4 a4 = W4_NOUREAD ? make_float4(1.f, 2.f, 3.f, 4.f) : ua[0];
-        float2 a2 = W4_NOUREAD ? make_float2(5.f, 6.f) : ub[0];
+        float4 a4 = ua[0];
+        float2 a2 = ub[0];
         f32x2 P[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const float4 c4 = a4;
             const float2 c2 = a2;
-            if (i < 5 && !W4_NOUREAD) { a4 = ua[(i + 1) * 64]; a2 = ub[(i + 1) * 64]; }
+            if (i < 5) { a4 = ua[(i + 1) * 64]; a2 = ub[(i + 1) * 64]; }
             // the next chunk's patch, one column pair per two rows: loads at i = 0, 2, 4; vertical pass at i = 1, 3, 5 (into registers of dead T rows)
             if ((i & 1) == 0) load_pair(P, pa, i >> 1);
             if constexpr (UFIRST) {                                                // one DMA statement per row
@@ -356,30 +291,18 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
                 else if (i == CK) issue_u(ch + US - 1, ustw, on_u);
             }
             // horizontal pass of row i: V = (B^T d) B
-#if W4_NOXF
-            const f32x2 v05 = T[i][0], v12 = T[i][1], v34 = T[i][2];
-#else
             const f32x2 ac = w4_fmak_lo(T[i][1], km4m1, T[i][2]);               // (x4 - 4 x2, x4 - x2)
             const f32x2 be = w4_fmak_hi(T[i][0], km4m1, T[i][1]);               // (x3 - 4 x1, x3 - x1)
             const f32x2 v05 = w4_fmak_op(T[i][0], k4, w4_fmak(T[i][1], km5, T[i][2]));   // (4 x0 - 5 x2 + x4, 4 x1 - 5 x3 + x5)
             const f32x2 v12 = w4_lo_pm_lo_op(ac, be);                            // (a + b, a - b)
             const f32x2 v34 = w4_fmak_hi_op(be, k2m2, ac);                       // (c + 2 e, c - 2 e)
-#endif
             __builtin_amdgcn_sched_barrier(0);
-#if W4_NOMFMA
-            if (FIRST) {
-#pragma unroll
-                for (int j = 0; j < 6; ++j) acc[6 * i + j] = zero;
-            }
-            acc[6 * i][0] += c4.x * v05.x + c4.y * v12.x + c4.z * v12.y + c4.w * v34.x + c2.x * v34.y + c2.y * v05.y;
-#else
             acc[6 * i + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4.x, v05.x, FIRST ? zero : acc[6 * i + 0], 0, 0, 0);
             acc[6 * i + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4.y, v12.x, FIRST ? zero : acc[6 * i + 1], 0, 0, 0);
             acc[6 * i + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4.z, v12.y, FIRST ? zero : acc[6 * i + 2], 0, 0, 0);
             acc[6 * i + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4.w, v34.x, FIRST ? zero : acc[6 * i + 3], 0, 0, 0);
             acc[6 * i + 4] = __builtin_amdgcn_mfma_f32_16x16x4f32(c2.x, v34.y, FIRST ? zero : acc[6 * i + 4], 0, 0, 0);
             acc[6 * i + 5] = __builtin_amdgcn_mfma_f32_16x16x4f32(c2.y, v05.y, FIRST ? zero : acc[6 * i + 5], 0, 0, 0);
-#endif
             if (i & 1) {
                 w4_lds_wait6(P[0], P[1], P[2], P[3], P[4], P[5]);
                 colpass(P, scn);
@@ -390,7 +313,6 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
         }
     };
     auto top = [&]() {
-        if (W4_NOBAR) return;
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(TOPWAIT) : "memory");        // U(ch) and raw(ch + 1) landed; the other operand's youngest chunk stays in flight
         __syncthreads();                                                      // ... for every wave; every wave is past chunk ch - 1: its stages may be refilled
     };
@@ -491,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
                     const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
                     v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
                 }
-                if (!W4_NOEPI || v.x == 123.456f) *reinterpret_cast<float4*>(p.y + oidx) = v;
+                *reinterpret_cast<float4*>(p.y + oidx) = v;
                 if (p.sq_ref) {                                    // ContentLoss value of a VGG tap: sum (y - reference)^2 while y is in registers
                     const float4 rf = *reinterpret_cast<const float4*>(p.sq_ref + oidx);
                     const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
@@ -590,13 +512,6 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     const int tcol_n = NARROW ? (n & 7) : n;
 
     const int G = gridDim.x;
-#ifdef L2I_W4_STAMP                                     // timing instrumentation (tools/probes/w4_stamp.py): thread 0 of every block writes the cycle counter at six points into p.ws
-    unsigned long long stamp[6];
-#define W4_STAMP(i) stamp[i] = __builtin_readcyclecounter()
-#else
-#define W4_STAMP(i)
-#endif
-    W4_STAMP(0);
     int w = (int)((blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3));
     if (w >= L.total) return;
     const int mblk = w % L.mblocks; w /= L.mblocks;
@@ -636,14 +551,13 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     // past the image: null descriptor into the dump) and the wave's channel plane of the raw tile (3 x 16 bytes per lane).
     auto issue_u = [&](int cu, int ust, bool on) {
         const unsigned base = lds_u + (unsigned)(ust * UST * 4) + (unsigned)wave_u * 1024u;
-        const unsigned so = (unsigned)(W4_HOTU ? 0 : cu) * uchunk_b + (unsigned)mblk * (unsigned)(UST * 4) + (unsigned)wave_u * 1024u;
+        const unsigned so = (unsigned)cu * uchunk_b + (unsigned)mblk * (unsigned)(UST * 4) + (unsigned)wave_u * 1024u;
         const bool w01 = wave_u < 2;
-        if (W4_NOUDMA) on = false;
         if constexpr (TALL) {                          // 18 slots over 8 waves: slots wave, wave + 8 and (waves 0, 1) wave + 16; the third slot of the others goes to the dump
             asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %6 offen lds\n\t"
                          "s_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %7 offen lds\n\t"
                          "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %8 offen lds"
-                         :: "v"(wvoff), "s"((on && !W4_NODMA) ? rs_w : rs_null), "s"((on && w01 && !W4_NODMA) ? rs_w : rs_null),
+                         :: "v"(wvoff), "s"(on ? rs_w : rs_null), "s"((on && w01) ? rs_w : rs_null),
                             "s"(base), "s"(base + 8192u), "s"(w01 ? base + 16384u : lds_dump),
                             "s"(so), "s"(so + 8192u), "s"(so + 16384u) : "memory");
         } else {
@@ -652,32 +566,19 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
                      "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %10 offen lds\n\t"
                      "s_mov_b32 m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %11 offen lds\n\t"
                      "s_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %2, %12 offen lds"
-                     :: "v"(wvoff), "s"((on && !W4_NODMA) ? rs_w : rs_null), "s"((on && w01 && !W4_NODMA) ? rs_w : rs_null),
+                     :: "v"(wvoff), "s"(on ? rs_w : rs_null), "s"((on && w01) ? rs_w : rs_null),
                         "s"(base), "s"(base + 4096u), "s"(base + 8192u), "s"(base + 12288u), "s"(w01 ? base + 16384u : lds_dump),
                         "s"(so), "s"(so + 4096u), "s"(so + 8192u), "s"(so + 12288u), "s"(so + 16384u) : "memory");
         }
     };
     auto issue_raw = [&](int cr, int rst, bool on) {
         const unsigned base = lds_raw + (unsigned)((rst * RAWST + rpl * PLANE) * 4) + (unsigned)rsl * 1024u;
-        const unsigned so = (unsigned)((W4_HOTR ? 0 : cr) * CK + rpl) * plane_b;
-        if (W4_NORDMA) on = false;
+        const unsigned so = (unsigned)(cr * CK + rpl) * plane_b;
         asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\t"
                      "buffer_load_dwordx4 %0, %4, %5 offen lds\n\t"
                      "buffer_load_dwordx4 %1, %4, %5 offen offset:1024 lds\n\t"
                      "buffer_load_dwordx4 %2, %4, %5 offen offset:2048 lds"
-                     :: "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "s"(base), "s"((on && !W4_NODMA) ? rs_x : rs_null), "s"(so) : "memory");
-    };
-
-    // L2 prefetch of a U chunk: one dword of each of its 144 128-byte lines, DMA'd into the dump (no register target).  The weight pack of a
-    // >= 256-channel layer (9 .. 38 MB) does not live in an XCD's 4 MB L2, and a U stage has ONE chunk (~1 us) of flight: the first block of an
-    // XCD to ask for a slice would wait for HBM / the memory-side cache at every chunk.  Issued right AFTER the U DMA of a chunk, the prefetch
-    // of U(ch + 3) has until the top of chunk ch + 2 (the in-order vmcnt makes it complete before U(ch + 2)) — two chunks — and the DMA of
-    // U(ch + 3), issued at chunk ch + 2, then finds its lines in L2.
-    const unsigned pfoff = tid < NUSLOT * 8 ? (unsigned)tid * 128u : OOB;
-    auto issue_pf = [&](int cu, bool on) {
-        const unsigned so = (unsigned)cu * uchunk_b + (unsigned)mblk * (unsigned)(UST * 4);
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dword %0, %2, %3 offen lds"
-                     :: "v"(pfoff), "s"(lds_dump + (unsigned)wave_u * 256u), "s"((on && !W4_NODMA) ? rs_w : rs_null), "s"(so) : "memory");
+                     :: "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "s"(base), "s"(on ? rs_x : rs_null), "s"(so) : "memory");
     };
 
     if constexpr (SCALE) {
@@ -689,7 +590,6 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
 
     // ---- input transform, vertical pass of one column pair: raw rows P[0..5] -> rows 3 H .. 3 H + 2 of B^T P (in P[0..2]) ----
     auto colpass = [&](f32x2 (&P)[6], f32x2 sc) {
-        if (W4_NOXF) return;
         constexpr int R0 = H ? 1 : 0;                  // rows the half reads: 0..4 (H = 0), 1..5 (H = 1)
         if constexpr (RELU) {
             const f32x2 krelu = {W4_RELU_SCALE, W4_RELU_SCALE};
@@ -730,10 +630,8 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     issue_raw(0, 0, true);
     issue_raw(1, 1, 1 < L.nchunks);
     issue_raw(2, 2, 2 < L.nchunks);
-    if (W4_UPF) { issue_pf(1, 1 < L.nchunks); issue_pf(2, 2 < L.nchunks); }
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NRS + 2 * W4_UPF) : "memory");   // U(0), raw(0) landed
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NRS) : "memory");   // U(0), raw(0) landed
     __syncthreads();                                                          // (also: the style-scale table)
-    W4_STAMP(1);
     {
         const f32x2 sc = scale_of(0);
 #pragma unroll
@@ -775,34 +673,22 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
                 for (int g = 0; g < BMG; ++g) { a4[g] = ua[g * (UG / 4) + (i + 1) * 64]; a2[g] = ub[g * (UG / 2) + (i + 1) * 64]; }
             }
             load_pair(P, pa, i);                                               // the next chunk's patch, one column pair per position row
-            if (i == 0) { issue_u(ch + 1, ustw, on_u); if (W4_UPF) issue_pf(ch + 3, ch + 3 < L.nchunks); }
+            if (i == 0) issue_u(ch + 1, ustw, on_u);
             else if (i == 1) issue_raw(ch + RS, rstw, on_r);
-#if W4_NOXF
-            const f32x2 v05 = T[i][0], v12 = T[i][1], v34 = T[i][2];
-#else
             const f32x2 ac = w4_fmak_lo(T[i][1], km4m1, T[i][2]);               // (x4 - 4 x2, x4 - x2)
             const f32x2 be = w4_fmak_hi(T[i][0], km4m1, T[i][1]);               // (x3 - 4 x1, x3 - x1)
             const f32x2 v05 = w4_fmak_op(T[i][0], k4, w4_fmak(T[i][1], km5, T[i][2]));
             const f32x2 v12 = w4_lo_pm_lo_op(ac, be);
             const f32x2 v34 = w4_fmak_hi_op(be, k2m2, ac);
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < BMG; ++g) {
-#if W4_NOMFMA
-                if (FIRST) {
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) acc[g][6 * i + j] = zero;
-                }
-                acc[g][6 * i][0] += c4[g].x * v05.x + c4[g].y * v12.x + c4[g].z * v12.y + c4[g].w * v34.x + c2[g].x * v34.y + c2[g].y * v05.y;
-#else
                 acc[g][6 * i + 0] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4[g].x, v05.x, FIRST ? zero : acc[g][6 * i + 0], 0, 0, 0);
                 acc[g][6 * i + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4[g].y, v12.x, FIRST ? zero : acc[g][6 * i + 1], 0, 0, 0);
                 acc[g][6 * i + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4[g].z, v12.y, FIRST ? zero : acc[g][6 * i + 2], 0, 0, 0);
                 acc[g][6 * i + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(c4[g].w, v34.x, FIRST ? zero : acc[g][6 * i + 3], 0, 0, 0);
                 acc[g][6 * i + 4] = __builtin_amdgcn_mfma_f32_16x16x4f32(c2[g].x, v34.y, FIRST ? zero : acc[g][6 * i + 4], 0, 0, 0);
                 acc[g][6 * i + 5] = __builtin_amdgcn_mfma_f32_16x16x4f32(c2[g].y, v05.y, FIRST ? zero : acc[g][6 * i + 5], 0, 0, 0);
-#endif
             }
             w4_lds_wait6(P[0], P[1], P[2], P[3], P[4], P[5]);
             colpass(P, scn);
@@ -812,12 +698,10 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         }
     };
     auto top = [&]() {
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NRS + W4_UPF) : "memory");   // U(ch) and raw(ch + 1) landed; raw(ch + 2) (and the prefetch) stay in flight
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NRS) : "memory");   // U(ch) and raw(ch + 1) landed; raw(ch + 2) stays in flight
         __syncthreads();
     };
     auto nxt = [](int v, int m) { return v + 1 == m ? 0 : v + 1; };
-
-    W4_STAMP(2);
     top();
     chunk(std::true_type(), 0, 0, 1 % RS, Ta, Tb);
     int ch = 1, rnext = 2 % RS, ucur = 1;
@@ -833,7 +717,6 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         top();
         chunk(std::false_type(), ch, ucur, rnext, Tb, Ta);
     }
-    W4_STAMP(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                           // no DMA may outlive the block's LDS
     __syncthreads();                                                           // every wave is past its last LDS read and its last DMA: the rings are dead
 
@@ -841,30 +724,24 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     // tile — are requested HERE, so that they travel during the half exchange below (36 LDS instructions and a barrier) instead of after it: inside the
     // row loop the noise row of ry + 1 could not even be requested before row ry's stores (they may alias as far as the compiler knows).  Same values,
     // same arithmetic: bit-identical; -11 % / -8 % on the generator's 1024^2 / 512^2 launches (profiles/r06_wino4s_strip_ab.txt).
-    // -DL2I_W4_EPI_HOIST=0: the round-5 placement (A/B).
-#ifndef L2I_W4_EPI_HOIST
-#define L2I_W4_EPI_HOIST 1
-#endif
     const size_t plane_o = (size_t)p.OHf * p.OWf;
     const int oyb = oy0 + 4 * trow_n, ox = ox0 + 4 * tcol_n;
     const bool xok = ox < p.OW;
     float scv_h[2][2], bv_h[2][2];
     float4 nz_h[4];
-    if (L2I_W4_EPI_HOIST) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int co = m0 + 16 * H + 4 * kq + 2 * h + q;
-                scv_h[h][q] = (p.out_scale && co < p.Cout) ? p.out_scale[(size_t)b * p.Cout + co] : 1.f;
-                bv_h[h][q] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f;
-            }
-#pragma unroll
-        for (int ry = 0; ry < 4; ++ry) {
-            const int oy = oyb + ry;
-            nz_h[ry] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (xok && oy < p.OH && p.noise) nz_h[ry] = *reinterpret_cast<const float4*>(p.noise + (size_t)b * plane_o + (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off);
+        for (int q = 0; q < 2; ++q) {
+            const int co = m0 + 16 * H + 4 * kq + 2 * h + q;
+            scv_h[h][q] = (p.out_scale && co < p.Cout) ? p.out_scale[(size_t)b * p.Cout + co] : 1.f;
+            bv_h[h][q] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f;
         }
+#pragma unroll
+    for (int ry = 0; ry < 4; ++ry) {
+        const int oy = oyb + ry;
+        nz_h[ry] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (xok && oy < p.OH && p.noise) nz_h[ry] = *reinterpret_cast<const float4*>(p.noise + (size_t)b * plane_o + (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off);
     }
     // ---- the two position halves of a tile row meet: wave (H, t) hands over its rows of group 1 - H and finishes group H ----
     {
@@ -886,7 +763,6 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         }
     }
     auto M = [&](int r, int j) -> const f32x4& { return (r / 3 == H) ? acc[H][6 * (r - 3 * H) + j] : oth[6 * (r - 3 * (1 - H)) + j]; };
-    W4_STAMP(4);
 
     // ---- epilogue: lane-local inverse transform Y = A^T M A, then 16-byte row stores (lane (g, n): channels m0 + 16 H + 4 g + 0..3, tile (trow, n)) ----
     float sq = 0.f;
@@ -909,10 +785,8 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         float scv[2], bv[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            const int co = co0 + q;
-            if (L2I_W4_EPI_HOIST) { scv[q] = scv_h[h][q]; bv[q] = bv_h[h][q]; continue; }
-            scv[q] = (p.out_scale && co < p.Cout) ? p.out_scale[(size_t)b * p.Cout + co] : 1.f;
-            bv[q] = (p.bias && co < p.Cout) ? p.bias[co] : 0.f;
+            scv[q] = scv_h[h][q];
+            bv[q] = bv_h[h][q];
         }
         float4 prow[2];                                // pool_out: the even row of the current window pair, per channel of the register pair
         bool pvalid[2] = {false, false};
@@ -927,7 +801,7 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
             float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pok && p.noise) {
-                nz = L2I_W4_EPI_HOIST ? nz_h[ry] : *reinterpret_cast<const float4*>(p.noise + (size_t)b * plane_o + poff);
+                nz = nz_h[ry];
                 nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
             }
 #pragma unroll
@@ -966,7 +840,7 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
                     const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
                     v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
                 }
-                if (!W4_NOEPI || v.x == 123.456f) *reinterpret_cast<float4*>(p.y + oidx) = v;
+                *reinterpret_cast<float4*>(p.y + oidx) = v;
                 if (p.pool_out) {                                  // [r5] MaxPool2d(2, 2) of y from the tile in registers (l2i.h: pool_out / pool_idx)
                     if ((ry & 1) == 0) { prow[q] = v; pvalid[q] = true; }
                     else if (pvalid[q]) {
@@ -1004,13 +878,6 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
             atomicAdd(p.sq_out + (blockIdx.x & (L2I_SQ_SLOTS - 1)), t);
         }
     }
-#ifdef L2I_W4_STAMP
-    W4_STAMP(5);
-    if (p.ws && tid == 0) {
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws) + (size_t)blockIdx.x * 8;
-        for (int i = 0; i < 6; ++i) o[i] = stamp[i];
-    }
-#endif
 }
 
 template <bool SCALE, bool RELU, int VAR = 0>
@@ -1024,9 +891,8 @@ __global__ __launch_bounds__(VAR == 2 ? 512 : 256, VAR == 2 ? 1 : 2) void conv_w
 static int launch_wino4s(const l2i_conv_params& p, hipStream_t st) {
     Wino4sLaunch L;
     const bool narrow = p.OW < 64;                     // maps 32 .. 63 wide: the 32 x 16-pixel tile
-    // TALL (64 x 16 pixels, eight waves): L2I_W4_TALL=1 takes it on every launch with >= 16 rows, 0 = never (the A/B: DESIGN.md section 4.0)
-    static const int tall_env = getenv("L2I_W4_TALL") ? atoi(getenv("L2I_W4_TALL")) : 0;
-    const bool tall = !narrow && p.OH >= 16 && (tall_env != 0 || p.tile_hint == 2);
+    // TALL (64 x 16 pixels, eight waves): only where the caller asks for it with tile_hint == 2 (the A/B: DESIGN.md section 4.0)
+    const bool tall = !narrow && p.OH >= 16 && p.tile_hint == 2;
     L.tiles_x = narrow ? (p.OW + 31) / 32 : (p.OW + 63) / 64;
     L.tiles_y = (narrow || tall) ? (p.OH + 15) / 16 : (p.OH + 7) / 8;
     L.mblocks = p.CoutP / w4s::BM;
@@ -1073,21 +939,20 @@ static int launch_wino4(const l2i_conv_params& p, hipStream_t st) {
     const bool relu_in = p.in_mask != nullptr;         // (checked by the caller: the mask IS the input, ReLU slopes)
     const bool scale = p.in_scale != nullptr;
     // which operand gets the deeper DMA ring (see w4::lds_floats): the weight pack once it no longer fits an XCD's L2 next to the tiles
-    static const int rs_env = getenv("L2I_W4_RS") ? atoi(getenv("L2I_W4_RS")) : 0;
-    const int rs = (rs_env == 2 || rs_env == 3) ? rs_env : (((size_t)p.Cin * p.CoutP * 36 * sizeof(float) > (size_t)(3u << 20)) ? 2 : 3);
+    const int rs = ((size_t)p.Cin * p.CoutP * 36 * sizeof(float) > (size_t)(3u << 20)) ? 2 : 3;
     const size_t lds = (size_t)((rs == 3 ? w4::lds_floats<3, 2>() : w4::lds_floats<2, 3>()) + (scale ? ((p.Cin + 3) & ~3) : 0)) * sizeof(float);
     if (lds > 80 * 1024) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino4: too many input channels for the style-scale table");
-#define L2I_WINO4(S_, R_, RS_)                                                                                                          \
+#define L2I_WINO4_GO(S_, R_, RS_)                                                                                                          \
     do {                                                                                                                                \
         L2I_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4_kernel<S_, R_, RS_>),                    \
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));                         \
         hipLaunchKernelGGL((conv_wino4_kernel<S_, R_, RS_>), dim3(grid), dim3(256), lds, st, p, L);                                      \
     } while (0)
-#define L2I_WINO4_RS(S_, R_) do { if (rs == 3) L2I_WINO4(S_, R_, 3); else L2I_WINO4(S_, R_, 2); } while (0)
+#define L2I_WINO4_RS(S_, R_) do { if (rs == 3) L2I_WINO4_GO(S_, R_, 3); else L2I_WINO4_GO(S_, R_, 2); } while (0)
     if (relu_in) { if (scale) L2I_WINO4_RS(true, true); else L2I_WINO4_RS(false, true); }
     else { if (scale) L2I_WINO4_RS(true, false); else L2I_WINO4_RS(false, false); }
 #undef L2I_WINO4_RS
-#undef L2I_WINO4
+#undef L2I_WINO4_GO
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }

@@ -360,7 +360,7 @@ class TransformGraph:
     def get_reg_loss(self, feed_dict):
         logit = feed_dict['logit']
         reg = self.regressor
-        if constants.FUSED_REG_LOSS and hasattr(reg, 'features') and len(self.attrIdx) <= 64:
+        if hasattr(reg, 'features') and len(self.attrIdx) <= 64:
             # [r6] fc + column select + the float64 BCE and everything autograd would run backwards through them as ONE launch each way (csrc/l2i_loss.hip):
             # ~40 launches of a few microseconds between the regressor's last conv and its first gradient conv otherwise
             return _RegBceFn.apply(reg.features(logit), reg.fc_w, reg.fc_b, self._attr_columns(), feed_dict['alpha'])
@@ -374,12 +374,11 @@ class TransformGraph:
         matrix-bound launches that fill the chip where the regressor's tail and the generator's 4^2 .. 64^2 layers do not.  ``get_content_loss`` picks
         the taps up when it is handed the same tensor; the values are the same launches' outputs, issued earlier.  The drivers call this (capture.forward,
         trainer.train_step) when the content loss is on; without the call nothing changes."""
-        # Measured (tools/ab/r06_prefetch_taps.sh, alternating runs on one box): the 16-bit path gains 0.8 % (c5 35.43 / 35.24 -> 35.08 / 34.99 ms per step: its
+        # Measured in round 6 (alternating runs on one box): the 16-bit path gains 0.8 % (c5 35.43 / 35.24 -> 35.08 / 34.99 ms per step: its
         # launches are short and the chip has holes to fill); the fp32 path LOSES 0.4 % (c3 99.27 / 99.54 -> 99.82 / 99.94: its launches saturate the chip
-        # and the early taps only lengthen the critical chain) — so: on for the 16-bit path, off for fp32 (L2I_PREFETCH_TAPS=1 / 0 force it).
+        # and the early taps only lengthen the critical chain) — so: on for the 16-bit path, off for fp32.
         from . import conv
-        on = constants.PREFETCH_CONTENT_TAPS if constants.PREFETCH_CONTENT_TAPS is not None else conv.PRECISION in conv.H8_PRECISIONS
-        if self.vgg19 is None or not constants.CONCURRENT_LOSS_BRANCHES or not on:
+        if self.vgg19 is None or not constants.CONCURRENT_LOSS_BRANCHES or conv.PRECISION not in conv.H8_PRECISIONS:
             return
         cur = torch.cuda.current_stream()
         side = self._side_streams()[1]

@@ -26,7 +26,7 @@ from . import specs
 from .discriminator import Discriminator as _Discriminator32, _ConvLReLUFn, _eq_conv, _vec
 from .generator import Generator as _Generator32, _ModPlan, _Mod, _ToRGB, _draw_noise, _noise_for, _t
 from .perceptual import VGG_STD, VGG_MEAN
-from .regressor import _CB, _fold_bn
+from .regressor import _fold_bn
 from .specs import RESNET50_LAYERS
 
 SQRT2 = math.sqrt(2.0)
@@ -43,19 +43,16 @@ LRELU_MASK = (SQRT2, 0.2 * SQRT2)
 # again after `constants.LOSS_SCALE_GROWTH_INTERVAL` clean steps.  bf16 elements: every scale is 1 (not applied).
 # [r5] the three image-side convs (VGG conv1_1, the discriminator's from-RGB 1x1, ResNet-50's 7x7 stem) read the fp32 3-channel image and STORE h8
 # (l2i_conv_img_h8, csrc/l2i_img_h8.hip), the stem's input gradient READS h8 (l2i_conv_params::in_h8): no padded 16 / 32-channel 16-bit copy of the
-# image, no fp32 stem map, no cast passes (-6 GB of the step's HBM traffic at 1024^2 batch 8).  L2I_H8_IMG_CONVS=0: the round-4 form (A/B).
-IMG_CONVS = os.environ.get('L2I_H8_IMG_CONVS', '1') != '0'
+# image, no fp32 stem map, no cast passes (-6 GB of the step's HBM traffic at 1024^2 batch 8 against the round-4 form, since removed).
 # [r5] ToRGB of the 512^2 / 1024^2 StyledConv outputs (64 / 32 channels: one block of the conv holds them all) in that conv's epilogue
-# (l2i_conv_params::rgb_w) instead of a pass that reads the feature map again.  L2I_H8_RGB_FUSED=0: the separate l2i_torgb_fwd_h8 launch (A/B).
-RGB_FUSED = os.environ.get('L2I_H8_RGB_FUSED', '1') != '0'
+# (l2i_conv_params::rgb_w) instead of a pass that reads the feature map again.
 # [r6] ResNet-50's backward reads one-bit sign planes written by the forward convs instead of the activation maps themselves (l2i.h: mask_out / mask_bits).
-# L2I_H8_SIGN_PLANES=0: the maps, as in round 5 (A/B).
-SIGN_PLANES = os.environ.get('L2I_H8_SIGN_PLANES', '1') != '0'
-CHAIN3 = os.environ.get('L2I_H8_CHAIN3', '1') != '0'       # [r6] ... and the 3x3 conv in front of such a pair in the same launch (l2i_conv_chain3_h8)
-PAIR = os.environ.get('L2I_H8_PAIR', '1') != '0'          # [r6] ResNet-50's trunk: chained 1x1 convs as one launch (csrc/l2i_pair_h8.hip); 0: separate launches (A/B)
+# False: the maps, as in round 5 (the comparator the tests set).
+SIGN_PLANES = True
+CHAIN3 = True       # [r6] ... and the 3x3 conv in front of such a pair in the same launch (l2i_conv_chain3_h8)
+PAIR = True         # [r6] ResNet-50's trunk: chained 1x1 convs as one launch (csrc/l2i_pair_h8.hip); False: separate launches (the comparator the tests set)
 # [r5] the per-sample weight planes of all modulated convs of a pass in ONE launch (kernels16.ModulatePlan) instead of one 15 us launch per layer and
-# pass (51 per step).  L2I_H8_MOD_MULTI=0: per layer (A/B).
-MOD_MULTI = os.environ.get('L2I_H8_MOD_MULTI', '1') != '0'
+# pass (51 per step).
 
 PROBE = None            # tools/bf16_study.py --probe: a list that receives (tag, shape, max |g|, median |g| of the non-zero entries) per gradient map
 
@@ -136,7 +133,7 @@ class VGG19Prefix:
         ws = [w0] + [torch.as_tensor(np.asarray(P['%d.weight' % i]), dtype=torch.float32) for i in (2, 5, 7)]
         self.convs = [C.H8Conv(w, 1, 1, device=device, cin_pad=16 if i == 0 else 32) for i, w in enumerate(ws)]      # conv1_1: three real channels of ONE 16-channel chunk
         self.biases = [torch.as_tensor(np.asarray(P['%d.bias' % i]), dtype=torch.float32).contiguous().to(device) for i in (0, 2, 5, 7)]
-        self.conv0_img = C.ImgConvH8(w0, 1, 1, device=device) if IMG_CONVS else None      # conv1_1 forward on the fp32 image, h8 out (its gradient: convs[0].dgrad)
+        self.conv0_img = C.ImgConvH8(w0, 1, 1, device=device)      # conv1_1 forward on the fp32 image, h8 out (its gradient: convs[0].dgrad)
         self.neg_mean = (-torch.tensor(VGG_MEAN, dtype=torch.float32)).to(device)
 
     def taps(self, img, org=None):
@@ -147,11 +144,7 @@ class VGG19Prefix:
         if org is not None:
             acc = torch.zeros(4, C._lib.SQ_SLOTS, device=img.device, dtype=torch.float32)
             sq = [(org[k], acc[k], [False]) for k in range(4)]
-        if self.conv0_img is not None:
-            c1 = self.conv0_img.forward(xc, bias=self.biases[0], sq=sq[0])
-        else:
-            xh = K16.cast_to_h8(xc, 16, dtype=self.dtype)          # three real channels of a 16-channel chunk
-            c1 = self.convs[0].forward(xh, bias=self.biases[0], sq=sq[0])
+        c1 = self.conv0_img.forward(xc, bias=self.biases[0], sq=sq[0])
         c2 = self.convs[1].forward(c1, relu_in=True, bias=self.biases[1], sq=sq[1])
         p, idx = K16.maxpool2d_fwd(c2, 2, 2, 0, relu=True)          # relu(maxpool(.)) == maxpool(relu(.)); the stored map is already rectified
         c3 = self.convs[2].forward(p, bias=self.biases[2], sq=sq[2])
@@ -224,10 +217,11 @@ class ResNet50:
         P = state
         self.device = device
         self.dtype = K16.h8_dtype()
-        self.stem = _CB(P, 'conv1', 'bn1', 2, 3, device)            # 7x7 stride 2 on the 3-channel fp32 image: fp32 kernels (L2I_H8_IMG_CONVS=0) and the input gradient
-        self.stem_img = C.ImgConvH8(_fold_bn(P, 'conv1', 'bn1')[0], 2, 3, device=device) if IMG_CONVS else None
-        if IMG_CONVS:       # the input gradient contracts with the weights the forward multiplied by: the folded weights rounded to the element type
-            self.stem_bwd = C.FrozenConv2d(_fold_bn(P, 'conv1', 'bn1')[0].to(self.dtype).float(), 2, 3, device=device)
+        w0, b0 = _fold_bn(P, 'conv1', 'bn1')                       # 7x7 stride 2 on the 3-channel fp32 image
+        self.stem_img = C.ImgConvH8(w0, 2, 3, device=device)
+        self.stem_bias = b0.contiguous().to(device)
+        # the input gradient contracts with the weights the forward multiplied by: the folded weights rounded to the element type
+        self.stem_bwd = C.FrozenConv2d(w0.to(self.dtype).float(), 2, 3, device=device)
         self.blocks = []
         for li, (planes, blocks, stride) in enumerate(RESNET50_LAYERS):
             for b in range(blocks):
@@ -257,17 +251,13 @@ class _ResNet16Fn(torch.autograd.Function):
     def forward(ctx, img, net):
         keep = img.requires_grad
         x = img.detach().contiguous()
-        if IMG_CONVS:
-            a0 = net.stem_img.forward(x, bias=net.stem.bias, act=C.ACT_RELU)            # h8 [B,8,H/2,W/2,8] from the fp32 image (csrc/l2i_img_h8.hip)
-            p0, idx0 = K16.maxpool2d_fwd(a0, 3, 2, 1)
-        else:
-            a0 = net.stem.conv.forward(x, bias=net.stem.bias, act=C.ACT_RELU)          # fp32 [B,64,H/2,W/2]
-            p0, idx0 = K16.maxpool2d_fwd(K16.cast_to_h8(a0, dtype=net.dtype), 3, 2, 1)
+        a0 = net.stem_img.forward(x, bias=net.stem_bias, act=C.ACT_RELU)               # h8 [B,8,H/2,W/2,8] from the fp32 image (csrc/l2i_img_h8.hip)
+        p0, idx0 = K16.maxpool2d_fwd(a0, 3, 2, 1)
         saved = dict(in_hw=(x.shape[2], x.shape[3]), a0=a0 if keep else None, idx0=idx0 if keep else None, blocks=[])
         cur = p0
         # [r6] SIGN_PLANES: the backward needs ONE BIT of every activation of this net (is the ReLU output positive); the three convs of a bottleneck write it
         # beside their map (l2i.h: mask_out, one byte per 16-byte pixel slot) and the gradient launches read the byte planes (mask_bits) — 1/16 of the
-        # bytes of the maps they stand for, and y1 / y2 / out need not be kept for the backward at all.  L2I_H8_SIGN_PLANES=0: the round-5 form (A/B).
+        # bytes of the maps they stand for, and y1 / y2 / out need not be kept for the backward at all.  SIGN_PLANES = False: the round-5 form.
         bits = keep and SIGN_PLANES
         plane = lambda t: torch.empty(t.shape[:4], device=t.device, dtype=torch.uint8)
         n_blk = len(net.blocks)
@@ -388,13 +378,9 @@ class _ResNet16Fn(torch.autograd.Function):
             G = Gp
             if PROBE is not None and (bi in (0, n - 1) or net.blocks[bi]['down'] is not None):
                 _probe('R.G%d' % bi, G)
-        a0 = saved['a0']
-        if a0.dim() == 5:                                  # [r5] h8 stem map: the 7x7 gradient kernel reads the 16-bit pool gradient and mask
-            g_a0 = K16.maxpool2d_bwd(G, saved['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
-            g_img = net.stem_bwd.dgrad_h8in(g_a0, saved['in_hw'], in_mask=a0, mask=(1.0, 0.0), out_gain=1.0 / S)
-        else:
-            g_a0 = K16.cast_from_h8(K16.maxpool2d_bwd(G, saved['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1), a0.shape[1])
-            g_img = net.stem.conv.dgrad(g_a0, saved['in_hw'], in_mask=a0, mask=(1.0, 0.0), out_gain=1.0 / S)
+        a0 = saved['a0']                                   # [r5] h8 stem map: the 7x7 gradient kernel reads the 16-bit pool gradient and mask
+        g_a0 = K16.maxpool2d_bwd(G, saved['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
+        g_img = net.stem_bwd.dgrad_h8in(g_a0, saved['in_hw'], in_mask=a0, mask=(1.0, 0.0), out_gain=1.0 / S)
         ctx.saved = ctx.last = None
         return g_img, None
 
@@ -418,7 +404,7 @@ class Discriminator(_Discriminator32):
         log_size = int(math.log2(size))
         self.conv0 = _eq16(P, 'convs.0.0.weight', 1, 0, device)
         w0 = torch.as_tensor(np.asarray(P['convs.0.0.weight']), dtype=torch.float32)
-        self.conv0_img = C.ImgConvH8(w0 * (1.0 / math.sqrt(w0.shape[1] * w0.shape[2] * w0.shape[3])), 1, 0, device=device) if IMG_CONVS else None
+        self.conv0_img = C.ImgConvH8(w0 * (1.0 / math.sqrt(w0.shape[1] * w0.shape[2] * w0.shape[3])), 1, 0, device=device)
         self.bias0 = _vec(P, 'convs.0.1.bias', device)
         self.blocks = []
         for n in range(1, log_size - 1):
@@ -448,10 +434,7 @@ class _DBody16Fn(torch.autograd.Function):
         keep = img.requires_grad
         x = img.detach().contiguous()
         lr = dict(act=C.ACT_LRELU, slope=0.2, gain=SQRT2)
-        if net.conv0_img is not None:
-            y0 = net.conv0_img.forward(x, bias=net.bias0, **lr)                            # from-RGB 1x1 on the fp32 image, h8 out
-        else:
-            y0 = net.conv0.forward(K16.cast_to_h8(x, 32, dtype=net.dtype), bias=net.bias0, **lr)
+        y0 = net.conv0_img.forward(x, bias=net.bias0, **lr)                                # from-RGB 1x1 on the fp32 image, h8 out
         saved = [y0]
         cur = y0
         bits = keep and SIGN_PLANES                    # [r6] the backward needs the SIGNS of y1 / y2 only: the convs write their sign planes, the maps are not kept
@@ -547,10 +530,8 @@ class Generator(_Generator32):
             self.rgbs.append(_ToRGB(P, 'to_rgbs.%d' % j, geo[2 + 2 * j][2], True, device))
         self.randomize_noise = True
         self.modplan = _ModPlan(self, device)
-        self.mod_fwd = self.mod_bwd = None
-        if MOD_MULTI:
-            self.mod_fwd = K16.ModulatePlan([L.w32_fwd for L in self.layers], self.modplan.s_off[:len(self.layers)], device, widths=self.modplan.cin)
-            self.mod_bwd = K16.ModulatePlan([L.w32_bwd for L in self.layers], self.modplan.d_off, device, widths=self.modplan.cout)
+        self.mod_fwd = K16.ModulatePlan([L.w32_fwd for L in self.layers], self.modplan.s_off[:len(self.layers)], device, widths=self.modplan.cin)
+        self.mod_bwd = K16.ModulatePlan([L.w32_bwd for L in self.layers], self.modplan.d_off, device, widths=self.modplan.cout)
 
     def synthesis(self, latent, noise=None):
         return _Synthesis16Fn.apply(latent, self, noise)
@@ -570,13 +551,13 @@ class _Synthesis16Fn(torch.autograd.Function):
         skip = None
         lr = dict(act=C.ACT_LRELU, slope=0.2, gain=SQRT2)
         drawn = _draw_noise(gen, noise, B, dev)
-        planes_all = gen.mod_fwd.run(s_all, B, gen.dtype) if gen.mod_fwd is not None else None      # weight * style for every layer (networks.py:234-235)
+        planes_all = gen.mod_fwd.run(s_all, B, gen.dtype)      # weight * style for every layer (networks.py:234-235)
         for li, L in enumerate(gen.layers):
             s, demod = plan.s(s_all, B, li), plan.demod(d_all, B, li)
             h = x.shape[2]
             res = h * 2 if L.up else h
             nz = _noise_for(gen, noise, li, B, res, dev, drawn)
-            planes = planes_all[li] if planes_all is not None else K16.modulate_planes(L.w32_fwd, s, dtype=gen.dtype)        # weight * style, one plane set per sample
+            planes = planes_all[li]                    # weight * style, one plane set per sample
             bstride = planes[0].numel() * 2
             if L.up:
                 t = L.conv.forward(x, planes=planes, w_bstride=bstride, out_scale=demod)          # (2H+1)^2
@@ -585,18 +566,18 @@ class _Synthesis16Fn(torch.autograd.Function):
             else:
                 has_rgb = li == 0 or li % 2 == 0
                 rgb = None
-                if has_rgb and RGB_FUSED and L.cout in (32, 64):                     # ToRGB in this conv's epilogue (the block holds every channel of its pixels)
+                if has_rgb and L.cout in (32, 64):                     # ToRGB in this conv's epilogue (the block holds every channel of its pixels)
                     rgb = torch.empty(B, 3, res, res, device=dev, dtype=torch.float32)
                 y = L.conv.forward(x, planes=planes, w_bstride=bstride, out_scale=demod, noise=nz, noise_w=L.noise_w, bias=L.bias,
                                    rgb=None if rgb is None else (plan.wmod(w_all, B, li // 2), gen.rgbs[li // 2].bias, rgb), **lr)
             del planes
             if PROBE is not None and li % 2 == 0:
                 _probe('G.fwd.y%d@%d' % (li, res), y)
-            rec = dict(x=x if keep else None, y=y if keep else None, s=s, demod=demod, nz=nz)
+            rec = dict(x=x if keep else None, y=y if keep else None, s=s, nz=nz)
             if li == 0 or (li % 2 == 0):
                 R = gen.rgbs[li // 2]
                 wmod = plan.wmod(w_all, B, li // 2)
-                if L.up or not (RGB_FUSED and L.cout in (32, 64)):
+                if L.up or L.cout not in (32, 64):
                     rgb = K16.torgb_fwd(y, wmod, R.bias)                       # fp32 [B,3,H,W]: the skip image stays fp32
                 skip = K.upfirdn2d(skip, R.up_k, up=(2, 2), pad=(2, 1, 2, 1), addend=rgb) if R.up else rgb
                 rec['wmod'] = wmod
@@ -625,7 +606,7 @@ class _Synthesis16Fn(torch.autograd.Function):
             if j > 0:
                 g = K.upfirdn2d(g, gen.rgbs[j].up_k_flip, up=(1, 1), down=(2, 2), pad=(1, 1, 1, 1))
         gin, gin_scale = None, None
-        planes_all = gen.mod_bwd.run(d_all, B, gen.dtype) if gen.mod_bwd is not None else None     # the gradient convs' weights carry the demodulation factor
+        planes_all = gen.mod_bwd.run(d_all, B, gen.dtype)     # the gradient convs' weights carry the demodulation factor
         for li in range(len(gen.layers) - 1, -1, -1):
             L, rec = gen.layers[li], saved[li]
             has_rgb = 'wmod' in rec
@@ -633,10 +614,10 @@ class _Synthesis16Fn(torch.autograd.Function):
             dz = K16.sg2_act_bwd(rec['y'], gin, gin_scale, grgb, rec.get('wmod'), L.bias, rec['nz'], L.noise_w, 0.2, SQRT2,
                                  plan.demod(red_dz, B, li), plan.red_rgb(red_rgb, B, li // 2) if has_rgb else None,
                                  red_q=plan.s(q_all, B, li + 1).view(-1) if gin is not None else None)      # layer li + 1's d s = sum_p gin * y (generator.py)
-            demod, s = rec['demod'], rec['s']
+            s = rec['s']
             x = rec['x']
             hw = (x.shape[2], x.shape[3])
-            planes = planes_all[li] if planes_all is not None else K16.modulate_planes(L.w32_bwd, demod, dtype=gen.dtype)
+            planes = planes_all[li]
             bstride = planes[0].numel() * 2
             if L.up:
                 dt = K16.upfirdn2d(dz, L.blur_k_flip, pad=(2, 2, 2, 2), sep=L.blur_flip_sep)        # gradient of the (2H+1)^2 map under the blur

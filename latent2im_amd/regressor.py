@@ -61,12 +61,11 @@ class ResNet50:
         return torch.addmm(self.fc_b, self.features(img), self.fc_w.t())
 
 
-PAIR = __import__('os').environ.get('L2I_R_PAIR', '1') != '0'            # [r6] chained 1x1 convs of the trunk as one launch (csrc/l2i_pair_f32.hip); 0: separate launches (A/B)
-PREMASK = __import__('os').environ.get('L2I_R_PREMASK', '1') != '0'      # 0: the round-5 mask plumbing of the backward (A/B)
+PREMASK = True      # False: the consumer-side masking reference of the backward (the comparator the tests set)
 
 
-def _backward_r5(net, saved, g):
-    """The round-5 form (L2I_R_PREMASK=0): g = the gradient w.r.t. a block's ReLU output; its mask rides on BOTH consumers of g."""
+def _backward_consumer_masked(net, saved, g):
+    """The reference form (PREMASK = False, as built in round 5): g = the gradient w.r.t. a block's ReLU output; its mask rides on BOTH consumers of g."""
     for blk, (y1, y2, out, in_hw) in zip(reversed(net.blocks), reversed(saved['blocks'])):
         pre = blk['c2'].conv.stride == 1
         g_y2 = blk['c3'].conv.dgrad(g, (y2.shape[2], y2.shape[3]), in_mask=out, mask=(1.0, 0.0), **(dict(out_mask=y2) if pre else {}))
@@ -110,7 +109,7 @@ class _ResNetFeatFn(torch.autograd.Function):
             nxt = net.blocks[bi + 1] if bi + 1 < n_blk else None
             ahead = None
             c3 = blk['c3'].conv
-            if (PAIR and C.PRECISION == 'f32' and nxt is not None and c3.k == 1 and c3.stride == 1 and nxt['c1'].conv.stride == 1
+            if (C.PRECISION == 'f32' and nxt is not None and c3.k == 1 and c3.stride == 1 and nxt['c1'].conv.stride == 1
                     and C.pair_f32_shapes_ok(c3.cin, c3.cout, nxt['c1'].conv.cout, y2.shape[2] * y2.shape[3])):
                 d = []
                 out = c3.forward(y2, bias=blk['c3'].bias, residual=idt, act=C.ACT_RELU, _defer=d)
@@ -140,7 +139,7 @@ class _ResNetFeatFn(torch.autograd.Function):
         # second DMA stream and 3 VALU per fragment in its K loop — and res_mask = out on c1's): one read of every wide map less per block (3.7 GB per
         # 1024^2 batch-8 step) and c3's gradient conv becomes the unmasked GEMM.  The 16-bit path has always done this (nets16._ResNet16Fn).
         if not PREMASK:
-            return _backward_r5(net, saved, g), None
+            return _backward_consumer_masked(net, saved, g), None
         G = K.relu_mask(g, blocks[-1][2])
         del g
         for bi in range(len(net.blocks) - 1, -1, -1):

@@ -1,5 +1,5 @@
 """l2i_conv2d_h8 / l2i_conv_transpose2d_h8 on the step's conv shapes (batch 8): ms, TFLOP/s of the dense correlation, GB/s of the algorithmic bytes.
-usage: python tools/probes/h8_bench.py [lib.so]   (another build of the library, e.g. a timing ablation from tools/probes/h8_ablate.sh); H8_ONLY=k3s1 limits the cases"""
+usage: python tools/probes/h8_bench.py [lib.so]   (another build of the library); H8_ONLY=k3s1 limits the cases"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

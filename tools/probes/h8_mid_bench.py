@@ -1,12 +1,12 @@
 """[r6] l2i_conv2d_h8 on the MID-SIZE launches of the c5 step (ResNet-50 at 1024^2 input, batch 8: <= 2048 blocks, where the trace shows 35 - 80 us per
 launch whatever the work) — per shape: us, TFLOP/s, GB/s of the algorithmic bytes, blocks.  Rotates over NBUF input / output buffers so that a launch
-does not find its own previous output in L2.  usage: python tools/probes/h8_mid_bench.py [f16|bf16]; env L2I_H8_KS / L2I_H8_SPLITK ... select variants."""
+does not find its own previous output in L2.  usage: python tools/probes/h8_mid_bench.py [f16|bf16]; env H8_LIB: another build of the library."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 import torch
 from latent2im_amd import conv, _lib
-if os.environ.get('H8_LIB'):                      # another build of the library (a timing ablation from tools/probes/h8_ablate.sh)
+if os.environ.get('H8_LIB'):                      # another build of the library
     import ctypes
     lib = ctypes.CDLL(os.path.abspath(os.environ['H8_LIB']))
     for name, (res_, args) in _lib._SIGNATURES.items():

@@ -1,4 +1,4 @@
-"""the 16-bit conv kernel on the small-map shapes of the c5 step (batch 8): 64- against 32-channel blocks (L2I_H8_SMALL_WM1 is read once per process)."""
+"""the 16-bit conv kernel on the small-map shapes of the c5 step (batch 8): per shape, median time of a launch (to compare two builds: L2I_LIB)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

@@ -3,7 +3,7 @@ import sys, os, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path
 import torch
 from latent2im_amd import conv, _lib
 if os.environ.get('L2I_ALT_LIB'):
-    _lib.LIB_PATH = os.path.abspath(os.environ['L2I_ALT_LIB'])      # e.g. a timing-ablation build (tools/probes/h8_ablate.sh)
+    _lib.LIB_PATH = os.path.abspath(os.environ['L2I_ALT_LIB'])      # another build of the library
 cin, cout, k, stride, res = (int(v) for v in sys.argv[1:6])
 secs = float(sys.argv[6])
 b = 8

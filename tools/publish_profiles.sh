@@ -1,5 +1,5 @@
 #!/bin/bash
-# Runs HERE (build container) after `gpurun -- bash tools/r06_collect_and_bench.sh`: copies the summaries that DESIGN.md cites from gpurun_out/ (scratch) into
+# Runs where the tree is edited, after tools/collect_profiles.sh ran on the GPU machine: copies the summaries that DESIGN.md cites from that collection's output directory (scratch) into
 # profiles/ (tracked).   usage: bash tools/publish_profiles.sh [round tag, default r06]
 set -eu
 R=$(cd "$(dirname "$0")/.." && pwd)
