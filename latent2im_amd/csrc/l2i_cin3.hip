@@ -13,8 +13,8 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace c3 {
 constexpr int TH = 8, TW = 64, IH = TH + 2, IW = TW + 2, IWp = 67, PLANE = IH * IWp;      // block tile: 8 rows x 64 columns

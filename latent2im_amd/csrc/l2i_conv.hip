@@ -27,9 +27,8 @@
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvLaunch {
     int tw_log2, th_log2, tb_log2;     // pixel tile = 2^tb samples x 2^th rows x 2^tw columns
@@ -47,8 +46,6 @@ struct ConvLaunch {
     int ksplit, cin_per;               // split-K: ksplit channel ranges of cin_per (multiple of CK) channels, raw partial sums into p.ws
                                        // (stride-2 1x1 convs gather only the pixels they use: lstride 1, gstep 2)
 };
-
-__device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }   // magic 0 encodes d == 1
 
 template <int BM> struct WSlots { static constexpr int value = (BM == 128) ? 10 : (BM == 64 ? 8 : 4); };
 
@@ -117,13 +114,12 @@ __global__ __launch_bounds__(256, (WM * WN <= 4) ? 3 : ((WM == 2 && WN == 4) ? 2
     const int nb = (p.B - b0) < (1 << L.tb_log2) ? (p.B - b0) : (1 << L.tb_log2);
     const unsigned in_bytes = (unsigned)((size_t)nb * p.Cin * plane_x * sizeof(float));   // host guarantees < 4 GiB
     const size_t grp_off = (size_t)b0 * p.Cin * plane_x;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + grp_off), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)((MASK ? p.in_mask : p.x) + grp_off), 0, in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(p.x + grp_off, in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_m = l2i_buffer_rsrc((MASK ? p.in_mask : p.x) + grp_off, in_bytes);
     const unsigned w_bytes = (unsigned)((size_t)p.Cin * KK * p.CoutP * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, w_bytes);
     const unsigned sc_bytes = (unsigned)((size_t)nb * p.Cin * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((p.in_scale ? p.in_scale : p.x) + (size_t)b0 * p.Cin), 0, p.in_scale ? sc_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_s = l2i_buffer_rsrc((p.in_scale ? p.in_scale : p.x) + (size_t)b0 * p.Cin, p.in_scale ? sc_bytes : 0u);
 
     typedef typename std::conditional<VEC, u32x4, unsigned>::type in_t;
     in_t rin[NIN];
@@ -508,13 +504,12 @@ __global__ __launch_bounds__(256) void conv_direct_small_kernel(const l2i_conv_p
         __syncthreads();
         // the taps are the same for every lane: they come through the scalar cache into SGPRs (constant address space -> s_load; one SGPR
         // operand per FMA) instead of LDS broadcasts, which cost 8 LDS cycles per 16 FMAs and bounded this kernel (see l2i_convt_small.hip)
-        typedef float f32x4v __attribute__((ext_vector_type(4)));
-        typedef __attribute__((address_space(4))) const f32x4v cfloat4;
+        typedef __attribute__((address_space(4))) const f32x4 cfloat4;
         const int cn = p.Cin - c0 < CK ? p.Cin - c0 : CK;
         for (int c = 0; c < cn; ++c) {
             const float* tc = tile + (c * IH + r0) * IWp + col;
             const float* wbase = p.w + (size_t)(c0 + c) * KK * p.CoutP;
-            auto tap = [&](int t) -> f32x4v { return *(cfloat4*)(uintptr_t)(wbase + (size_t)t * p.CoutP); };
+            auto tap = [&](int t) -> f32x4 { return *(cfloat4*)(uintptr_t)(wbase + (size_t)t * p.CoutP); };
             if constexpr (TKH > 0) {
                 float win[TKH + 3][TKW];
 #pragma unroll
@@ -525,7 +520,7 @@ __global__ __launch_bounds__(256) void conv_direct_small_kernel(const l2i_conv_p
                 for (int ky = 0; ky < TKH; ++ky) {
 #pragma unroll
                     for (int kx = 0; kx < TKW; ++kx) {
-                        const f32x4v w4 = tap(ky * TKW + kx);
+                        const f32x4 w4 = tap(ky * TKW + kx);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float x = win[r + ky][kx];
@@ -536,7 +531,7 @@ __global__ __launch_bounds__(256) void conv_direct_small_kernel(const l2i_conv_p
             } else {
                 for (int ky = 0; ky < p.KH; ++ky) {
                     for (int kx = 0; kx < p.KW; ++kx) {
-                        const f32x4v w4 = tap(ky * p.KW + kx);
+                        const f32x4 w4 = tap(ky * p.KW + kx);
                         const float* tr = tc + ky * IWp + kx;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {                   // static register indexing only (no scratch)
@@ -575,8 +570,7 @@ __global__ __launch_bounds__(256) void conv_direct_small_kernel(const l2i_conv_p
 template <bool MASK>
 __global__ __launch_bounds__(256) void conv3x3_small_stream_kernel(const l2i_conv_params p, int bands, int strips) {
     constexpr int RS = 4;
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-    typedef __attribute__((address_space(4))) const f32x4v cfloat4;
+    typedef __attribute__((address_space(4))) const f32x4 cfloat4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long bid = blockIdx.x;
     const int strip = (int)(bid % strips); bid /= strips;
@@ -631,7 +625,7 @@ __global__ __launch_bounds__(256) void conv3x3_small_stream_kernel(const l2i_con
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) {
-                const f32x4v w4 = wc[ky * 3 + kx];
+                const f32x4 w4 = wc[ky * 3 + kx];
 #pragma unroll
                 for (int r = 0; r < RS; ++r)
 #pragma unroll

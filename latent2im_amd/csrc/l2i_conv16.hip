@@ -29,10 +29,9 @@
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 #include "l2i_epilogue.h"
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace s16 {
 // K x K window, stride S, WN 32-pixel rows per wave (TH = 4 WN output rows per block, 32 columns).
@@ -68,20 +67,14 @@ struct S16Launch {
     int vec_epi;
 };
 
-__device__ __forceinline__ unsigned cvt_pk_bf16_b(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-
 // 8 fp32 -> 8 bf16 hi (round to nearest even) and 8 bf16 lo = bf16(x - hi)
 __device__ __forceinline__ void split8b(const float (&v)[8], u32x4& hi, u32x4& lo) {
     unsigned h[4], l[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        h[q] = cvt_pk_bf16_b(v[2 * q], v[2 * q + 1]);
+        h[q] = h8_pk(v[2 * q], v[2 * q + 1]);
         const float h0 = __uint_as_float(h[q] << 16), h1 = __uint_as_float(h[q] & 0xffff0000u);
-        l[q] = cvt_pk_bf16_b(v[2 * q] - h0, v[2 * q + 1] - h1);
+        l[q] = h8_pk(v[2 * q] - h0, v[2 * q + 1] - h1);
     }
     hi = u32x4{h[0], h[1], h[2], h[3]};
     lo = u32x4{l[0], l[1], l[2], l[3]};
@@ -123,13 +116,13 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
     const unsigned plane_b = (unsigned)(plane_x * sizeof(float));
     const unsigned in_bytes = (unsigned)p.Cin * plane_b;
     const size_t smp = (size_t)b * p.Cin * plane_x;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + smp), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)((MASK ? p.in_mask : p.x) + smp), 0, in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(p.x + smp, in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_m = l2i_buffer_rsrc((MASK ? p.in_mask : p.x) + smp, in_bytes);
     const unsigned wpl_bytes = (unsigned)((size_t)(p.Cin / 16) * K * K * 2 * p.CoutP * 16);
-    const __amdgpu_buffer_rsrc_t rs_wh = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hi, 0, wpl_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_wl = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_lo, 0, wpl_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)((p.in_scale ? p.in_scale : p.x) + (size_t)b * p.Cin), 0,
-                                                                            p.in_scale ? (unsigned)(p.Cin * sizeof(float)) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_wh = l2i_buffer_rsrc(p.w_hi, wpl_bytes);
+    const __amdgpu_buffer_rsrc_t rs_wl = l2i_buffer_rsrc(p.w_lo, wpl_bytes);
+    const __amdgpu_buffer_rsrc_t rs_s = l2i_buffer_rsrc((p.in_scale ? p.in_scale : p.x) + (size_t)b * p.Cin,
+                                                                            p.in_scale ? (unsigned)(p.Cin * sizeof(float)) : 0u);
 
     // ---- input staging: a thread owns one 8-channel half and NS (row, 4-pixel vector) items of the tile ----
     const int nh = tid % G::NH, tq = tid / G::NH;
@@ -165,17 +158,13 @@ __global__ __launch_bounds__(256, (S == 1 && WM * WN <= 4) ? 2 : 1) void conv_bf
 
     auto dma_w = [&](int chunk, int ky, int stage) {
         const unsigned soff = (unsigned)((((size_t)chunk * G::KS * K * K + ky * K) * 2) * p.CoutP * 16);
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage * W_STAGE);
+        const unsigned lds0 = l2i_lds_addr(w_st + stage * W_STAGE);
 #pragma unroll
         for (int t = 0; t < WPW; ++t) {
             const int q = wave_u + 4 * t;                  // wave-uniform: a scalar branch (a DMA through a null descriptor would WRITE zeros)
             if (q < WPIECES) {
                 const bool lo = q >= WPIECES / 2;
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep)
-                             : "v"(wvoff[t]), "s"(lo ? rs_wl : rs_wh), "s"(__builtin_amdgcn_readfirstlane(lds0 + q * 1024)), "s"(soff)
-                             : "memory");
+                l2i_lds_dma16(wvoff[t], lo ? rs_wl : rs_wh, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), soff);
             }
         }
     };

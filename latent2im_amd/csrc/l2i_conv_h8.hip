@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 #include "l2i_epilogue.h"
 
 #include "l2i_h8_common.h"
@@ -147,7 +148,7 @@ struct H8Out {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += o[e];
         }
-        const u32x4 out = {cvt_pk_bf16_h8(v[0], v[1]), cvt_pk_bf16_h8(v[2], v[3]), cvt_pk_bf16_h8(v[4], v[5]), cvt_pk_bf16_h8(v[6], v[7])};
+        const u32x4 out = {h8_pk(v[0], v[1]), h8_pk(v[2], v[3]), h8_pk(v[4], v[5]), h8_pk(v[6], v[7])};
         reinterpret_cast<u32x4*>(p.y)[slot] = out;
         if (p.mask_out) p.mask_out[slot] = (uint8_t)h8_sign_byte(out);
         if (p.sq_ref) {                                            // ContentLoss value of a VGG tap on the ROUNDED output (what the next layer reads)
@@ -223,10 +224,10 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
     const unsigned plane_b = (unsigned)((size_t)p.H * p.W * 16);                       // bytes of one 8-channel group
     const unsigned in_bytes = (unsigned)(p.Cin / 8) * plane_b;
     const char* xb = reinterpret_cast<const char*>(p.x) + (size_t)b * in_bytes;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(xb, in_bytes);
     const unsigned wpl_bytes = (unsigned)((size_t)(p.Cin / 16) * K * K * 2 * p.CoutP * 16);
     const char* wb = reinterpret_cast<const char*>(p.w_hi) + (size_t)b * (size_t)p.w_bstride;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)wb, 0, wpl_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(wb, wpl_bytes);
 
     // ---- tile DMA: piece q = wave + 4 t covers LDS slots [64 q, 64 q + 64) of the stage; slot -> (group, row, column) ----
     const int tw = wave, tw_u = wave_u;
@@ -245,14 +246,10 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
     }
     auto dma_in = [&](int chunk, int stage) {
         const unsigned soff = (unsigned)chunk * G::NH * plane_b;
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(in_st + stage * IN_STAGE);
+        const unsigned lds0 = l2i_lds_addr(in_st + stage * IN_STAGE);
 #pragma unroll
         for (int t = 0; t < NPT; ++t) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(ivoff[t]), "s"(rs_x), "s"(__builtin_amdgcn_readfirstlane(lds0 + (tw_u + TW * t) * 1024)), "s"(soff)
-                         : "memory");
+            l2i_lds_dma16(ivoff[t], rs_x, __builtin_amdgcn_readfirstlane(lds0 + (tw_u + TW * t) * 1024), soff);
         }
     };
     // ---- weight DMA: piece q covers slots [64 q, 64 q + 64) of the phase ([tap][step][half][channel]) ----
@@ -266,16 +263,12 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
     }
     auto dma_w = [&](int chunk, int ky, int stage_slot) {       // stage_slot: first LDS slot of the phase's weights (relative to w_st)
         const unsigned soff = (unsigned)((((size_t)chunk * G::KS * K * K + ky * K) * 2) * p.CoutP * 16);
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage_slot);
+        const unsigned lds0 = l2i_lds_addr(w_st + stage_slot);
 #pragma unroll
         for (int t = 0; t < WPW; ++t) {
             const int q = tw_u + TW * t;                   // wave-uniform: a scalar branch
             if (q < WPIECES) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep)
-                             : "v"(wvoff[t]), "s"(rs_w), "s"(__builtin_amdgcn_readfirstlane(lds0 + q * 1024)), "s"(soff)
-                             : "memory");
+                l2i_lds_dma16(wvoff[t], rs_w, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), soff);
             }
         }
     };
@@ -412,15 +405,15 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
             const bool gok = co0 < p.Cout;
             const int cc = gok ? co0 : 0;
             // scale (1 when absent) and bias (0 when absent) as four channel pairs: g * s + b is one packed FMA per pair
-            f32x2_ sc2[4] = {{1.f, 1.f}, {1.f, 1.f}, {1.f, 1.f}, {1.f, 1.f}}, bs2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+            f32x2 sc2[4] = {{1.f, 1.f}, {1.f, 1.f}, {1.f, 1.f}, {1.f, 1.f}}, bs2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
             if (p.out_scale) {
                 const float* sp = p.out_scale + (size_t)b * p.Cout + cc;
                 const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
-                sc2[0] = f32x2_{s0.x, s0.y}; sc2[1] = f32x2_{s0.z, s0.w}; sc2[2] = f32x2_{s1.x, s1.y}; sc2[3] = f32x2_{s1.z, s1.w};
+                sc2[0] = f32x2{s0.x, s0.y}; sc2[1] = f32x2{s0.z, s0.w}; sc2[2] = f32x2{s1.x, s1.y}; sc2[3] = f32x2{s1.z, s1.w};
             }
             if (p.bias) {
                 const float4 b0 = *reinterpret_cast<const float4*>(p.bias + cc), b1 = *reinterpret_cast<const float4*>(p.bias + cc + 4);
-                bs2[0] = f32x2_{b0.x, b0.y}; bs2[1] = f32x2_{b0.z, b0.w}; bs2[2] = f32x2_{b1.x, b1.y}; bs2[3] = f32x2_{b1.z, b1.w};
+                bs2[0] = f32x2{b0.x, b0.y}; bs2[1] = f32x2{b0.z, b0.w}; bs2[2] = f32x2{b1.x, b1.y}; bs2[3] = f32x2{b1.z, b1.w};
             }
             u32x4* const yq = yb + (size_t)(4 * m + 2 * pr) * plane;
             float rw[3][8];
@@ -439,11 +432,11 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
                 for (int a = 0; a < NACC; ++a) {
                     float g[8];
                     h8_gather(acc[a][m][n], pr, half, g);
-                    f32x2_ v[4];
+                    f32x2 v[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = f32x2_{g[2 * i], g[2 * i + 1]} * sc2[i] + bs2[i];
+                    for (int i = 0; i < 4; ++i) v[i] = f32x2{g[2 * i], g[2 * i + 1]} * sc2[i] + bs2[i];
                     if (p.noise) {
-                        const f32x2_ z = {nz[n][a], nz[n][a]};
+                        const f32x2 z = {nz[n][a], nz[n][a]};
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] += z;
                     }
@@ -451,10 +444,10 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
 #pragma unroll
                         for (int i = 0; i < 4; ++i) { v[i].x = fmaxf(v[i].x, 0.f); v[i].y = fmaxf(v[i].y, 0.f); }
                     } else if (!identity) {                     // leaky ReLU / gains: max(v * gpos, v * gneg), gpos >= gneg >= 0
-                        const f32x2_ gp2 = {gpos, gpos}, gn2 = {gneg, gneg};
+                        const f32x2 gp2 = {gpos, gpos}, gn2 = {gneg, gneg};
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const f32x2_ hi = v[i] * gp2, lo = v[i] * gn2;
+                            const f32x2 hi = v[i] * gp2, lo = v[i] * gn2;
                             v[i].x = fmaxf(hi.x, lo.x); v[i].y = fmaxf(hi.y, lo.y);
                         }
                     }
@@ -465,7 +458,7 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
 #pragma unroll
                             for (int e = 0; e < 8; ++e) racc[n][a][o] += g[e] * rw[o][e];
                     }
-                    const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
+                    const u32x4 out = {h8_pk(g[0], g[1]), h8_pk(g[2], g[3]), h8_pk(g[4], g[5]), h8_pk(g[6], g[7])};
                     unsigned off;
                     const bool ok = pix(n, a, off);
                     if (ok && gok) yq[off] = out;

@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 #include "l2i_epilogue.h"
 
 namespace cs2 {
@@ -71,9 +72,9 @@ __global__ __launch_bounds__(256, 3) void conv3x3s2_dma_kernel(const l2i_conv_pa
     // starts 2048 bytes BEFORE the sample (never dereferenced there: every offset is built from an in-image pixel) and is 2048 bytes longer; every
     // register offset is byte + 2048 - immediate >= 0.
     constexpr unsigned XSHIFT = 2048u;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(p.x + smp) - XSHIFT), 0, (unsigned)p.Cin * plane_b + XSHIFT, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (unsigned)p.Cin * 9u * wrow_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc((const char*)(p.x + smp) - XSHIFT, (unsigned)p.Cin * plane_b + XSHIFT);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, (unsigned)p.Cin * 9u * wrow_b);
+    const __amdgpu_buffer_rsrc_t rs_null = l2i_buffer_rsrc(p.x, 0u);
     constexpr unsigned OOB = 0x80000000u;
 
     // input: wave pair (wave & 1) = channel plane of the chunk; wave >> 1 = 0 takes slots 0, 2, 4 of its 289 groups, wave >> 1 = 1 slots 1, 3 (+ a null one)
@@ -96,8 +97,8 @@ __global__ __launch_bounds__(256, 3) void conv3x3s2_dma_kernel(const l2i_conv_pa
         const bool ok = (e < CK * 9 * 16) & (u == 0 || wave == 0);
         wvoff[u] = ok ? (unsigned)(c * 9 + (r >> 4)) * wrow_b + (unsigned)(m0 + 4 * (r & 15)) * 4u : OOB;
     }
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
-    const unsigned lds_dump = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)dump;
+    const unsigned lds0 = l2i_lds_addr(smem);
+    const unsigned lds_dump = l2i_lds_addr(dump);
 
     auto issue = [&](int ch, int st, bool on) {
         const unsigned sbase = lds0 + (unsigned)(st * STAGE * 4);

@@ -24,9 +24,8 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvTLaunch {
     int TW, TH, tb_log2;               // tile = 2^tb samples x TH rows x TW columns of positions (TW even; TW*TH*2^tb <= 128*WN slots)
@@ -40,7 +39,6 @@ struct ConvTLaunch {
     int nslots;                        // DMAIN: 64-element DMA slots per channel plane (IH * IW elements, dense)
 };
 
-__device__ __forceinline__ unsigned fast_div_t(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }
 
 template <int K, int PAD> struct TrGeom {
     static constexpr int k0(int pi) { return (pi + PAD) % 2; }
@@ -84,8 +82,8 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
 #pragma unroll
     for (int n = 0; n < WN; ++n) {
         const int pi = (wave * WN + n) * 32 + j;
-        const int rowi = (int)fast_div_t((unsigned)pi, L.magic_tw), c = pi - rowi * TW;
-        int tb = (int)fast_div_t((unsigned)rowi, L.magic_th);
+        const int rowi = (int)fast_div((unsigned)pi, L.magic_tw), c = pi - rowi * TW;
+        int tb = (int)fast_div((unsigned)rowi, L.magic_th);
         int r = rowi - tb * TH;
         const bool used = tb < (1 << L.tb_log2);                   // slots past TB*TH*TW (tiles that do not fill 128*WN positions) idle on pixel 0
         if (!used) { tb = 0; r = 0; }
@@ -107,6 +105,8 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
     const int nb = (p.B - b0) < (1 << L.tb_log2) ? (p.B - b0) : (1 << L.tb_log2);
     const unsigned in_bytes = (unsigned)((size_t)nb * p.Cin * plane_x * sizeof(float));
     const size_t grp_off = (size_t)b0 * p.Cin * plane_x;
+    // (the builtin itself, not l2i_buffer_rsrc: through the helper these five descriptors are scheduled in another order — the one file whose
+    // assembly the helper changes, so it keeps the statements it was measured with)
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + grp_off), 0, in_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)((MASK ? p.in_mask : p.x) + grp_off), 0, in_bytes, 0x00020000);
     const unsigned w_bytes = (unsigned)((size_t)p.Cin * KK * p.CoutP * sizeof(float));
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
 #pragma unroll
         for (int s_ = 0; s_ < NSL; ++s_) {
             const unsigned e = (unsigned)(s_ * 64 + lane);
-            const unsigned row = fast_div_t(e, L.magic_iw), ixu = e - row * L.IW;
+            const unsigned row = fast_div(e, L.magic_iw), ixu = e - row * L.IW;
             const int gy = iy0 + (int)row, gx = ix0 + (int)ixu;
             const bool ok = (s_ < L.nslots) & ((int)row < L.IH) & (gy >= 0) & (gy < p.H) & (gx >= 0) & (gx < p.W);
             dvoff[s_] = ok ? (unsigned)(gy * p.W + gx) * 4u + (DSHIFT - (unsigned)s_ * 256u) : 0x80000000u;      // >= 0: rs_xd starts DSHIFT bytes early
@@ -142,10 +142,10 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
         voff[u] = in_bytes;
         loff[u] = -1;
         if ((int)e < L.in_elems) {
-            const unsigned row = fast_div_t(e, L.magic_iw), ixu = e - row * L.IW;
-            const unsigned c = fast_div_t(row, L.magic_rc);
+            const unsigned row = fast_div(e, L.magic_iw), ixu = e - row * L.IW;
+            const unsigned c = fast_div(row, L.magic_rc);
             const unsigned r2 = row - c * L.rows_c;
-            const unsigned tb = fast_div_t(r2, L.magic_ih);
+            const unsigned tb = fast_div(r2, L.magic_ih);
             const int iy = (int)(r2 - tb * L.IH);
             const int gy = iy0 + iy, gx = ix0 + (int)ixu;
             loff[u] = (int)(c * L.plane + tb * L.planeS + iy * L.IWp + ixu);
@@ -172,14 +172,11 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
     // weights of a chunk: global -> LDS by DMA, 16 B per lane, a wave instruction fills 1 KiB of the [CK][KK][BM] tile in lane order
     // (inline asm: through the builtin hipcc drains every outstanding load before the next ds_read); no registers, no commit
     auto dma_w = [&](int c0, int st) {
-        const unsigned lds_w = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + st * stage_f + L.CK * L.plane);
+        const unsigned lds_w = l2i_lds_addr(smem + st * stage_f + L.CK * L.plane);
         const unsigned sw = (unsigned)((size_t)c0 * KK * p.CoutP * sizeof(float));
         for (int u = 0; u * 256 < L.w_vec; ++u) {
             if (tid + u * 256 < L.w_vec) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(wvoff), "s"(rs_w), "s"(__builtin_amdgcn_readfirstlane(lds_w + (u * 256 + wave * 64) * 16)),
-                               "s"(sw + u * wstep) : "memory");
+                l2i_lds_dma16(wvoff, rs_w, __builtin_amdgcn_readfirstlane(lds_w + (u * 256 + wave * 64) * 16), sw + u * wstep);
             }
         }
     };
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto dma_in = [&](int c0, int st) {
         if constexpr (DMAIN) {
-            const unsigned lds_in0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(smem + st * stage_f);
+            const unsigned lds_in0 = l2i_lds_addr(smem + st * stage_f);
             for (int c = wave_u; c < L.CK; c += 4) {
                 const unsigned base = lds_in0 + (unsigned)(c * L.plane * 4);
                 const unsigned so = (unsigned)((size_t)(c0 + c) * plane_x * sizeof(float));
@@ -362,8 +359,8 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
 #pragma unroll
         for (int n = 0; n < WN; ++n) {
             const int pi = (wave * WN + n) * 32 + j;
-            const int rowi = (int)fast_div_t((unsigned)pi, L.magic_tw);
-            const int tbi = (int)fast_div_t((unsigned)rowi, L.magic_th);
+            const int rowi = (int)fast_div((unsigned)pi, L.magic_tw);
+            const int tbi = (int)fast_div((unsigned)rowi, L.magic_th);
             const int tcol = tx0 + (pi - rowi * TW), trow = ty0 + (rowi - tbi * TH);
             const int bb = tbi < (1 << L.tb_log2) ? b0 + tbi : p.B;
             if (bb < p.B) {
@@ -387,8 +384,8 @@ __global__ __launch_bounds__(256, WN == 1 ? 3 : 2) void convt_mfma_kernel(const 
 #pragma unroll
     for (int n = 0; n < WN; ++n) {
         const int pi = (wave * WN + n) * 32 + 2 * q4;      // input-resolution position of this lane's 4 outputs
-        const int rowi = (int)fast_div_t((unsigned)pi, L.magic_tw);
-        const int tbi = (int)fast_div_t((unsigned)rowi, L.magic_th);
+        const int rowi = (int)fast_div((unsigned)pi, L.magic_tw);
+        const int tbi = (int)fast_div((unsigned)rowi, L.magic_th);
         const int tcol = tx0 + (pi - rowi * TW);
         const int trow = ty0 + (rowi - tbi * TH);
         const int bb = tbi < (1 << L.tb_log2) ? b0 + tbi : p.B;       // unused slots: no sample

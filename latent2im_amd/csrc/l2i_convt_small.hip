@@ -16,7 +16,8 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
-#include "l2i_epilogue.h"      // [r5] l2i_h8_lo / l2i_h8_hi: the 16-bit unpack of the in_h8 variant
+#include "l2i_device.h"
+#include "l2i_epilogue.h"      // [r5] h8_lo / h8_hi: the 16-bit unpack of the in_h8 variant
 
 namespace cts {
 constexpr int K = 7, PAD = 3, KK = K * K;
@@ -55,18 +56,18 @@ __global__ __launch_bounds__(256) void convt7_small_kernel(const l2i_conv_params
         if constexpr (H8) {
             const bool f16 = p.in_h8 == 2;
             const size_t gbase = ((size_t)b * (p.Cin >> 3) + (c0 >> 3)) * plane_x;
-            l2i_u32x4 q[NS], qm[NS];
+            u32x4 q[NS], qm[NS];
 #pragma unroll
             for (int n = 0; n < NS; ++n) {
                 const int e = threadIdx.x + n * 256;
                 const int r = e / PITCH, col = e - r * PITCH;
                 const int gy = t0 - 1 + r, gx = s0 - 4 + col;
-                q[n] = l2i_u32x4{0u, 0u, 0u, 0u};
+                q[n] = u32x4{0u, 0u, 0u, 0u};
                 qm[n] = q[n];
                 if (e < IH * PITCH && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {
                     const size_t slot = gbase + (size_t)gy * p.W + gx;
-                    q[n] = reinterpret_cast<const l2i_u32x4*>(p.x)[slot];
-                    if constexpr (MASK) qm[n] = reinterpret_cast<const l2i_u32x4*>(p.in_mask)[slot];
+                    q[n] = reinterpret_cast<const u32x4*>(p.x)[slot];
+                    if constexpr (MASK) qm[n] = reinterpret_cast<const u32x4*>(p.in_mask)[slot];
                 }
             }
 #pragma unroll
@@ -76,10 +77,10 @@ __global__ __launch_bounds__(256) void convt7_small_kernel(const l2i_conv_params
                     const unsigned u[4] = {q[n].x, q[n].y, q[n].z, q[n].w}, m[4] = {qm[n].x, qm[n].y, qm[n].z, qm[n].w};
 #pragma unroll
                     for (int h = 0; h < 4; ++h) {
-                        float a0 = l2i_h8_lo(u[h], f16), a1 = l2i_h8_hi(u[h], f16);
+                        float a0 = h8_lo(u[h], f16), a1 = h8_hi(u[h], f16);
                         if constexpr (MASK) {
-                            a0 *= l2i_h8_lo(m[h], f16) > 0.f ? p.mask_pos : p.mask_neg;
-                            a1 *= l2i_h8_hi(m[h], f16) > 0.f ? p.mask_pos : p.mask_neg;
+                            a0 *= h8_lo(m[h], f16) > 0.f ? p.mask_pos : p.mask_neg;
+                            a1 *= h8_hi(m[h], f16) > 0.f ? p.mask_pos : p.mask_neg;
                         }
                         tile[(2 * h) * IH * PITCH + e] = a0;
                         tile[(2 * h + 1) * IH * PITCH + e] = a1;
@@ -123,8 +124,7 @@ __global__ __launch_bounds__(256) void convt7_small_kernel(const l2i_conv_params
                 for (int j = 0; j < 5; ++j) win[r][j] = tc[r * PITCH + j];
             // the taps are the same for every lane: scalar loads (constant address space -> s_load into SGPRs), one kernel row at a time;
             // as LDS broadcasts they cost 8 LDS cycles per 6 FMAs and bound the kernel (measured: 1.9 ms, no faster than four launches)
-            typedef float f32x4v __attribute__((ext_vector_type(4)));
-            typedef __attribute__((address_space(4))) const f32x4v cfloat4;
+            typedef __attribute__((address_space(4))) const f32x4 cfloat4;
             cfloat4* wc = (cfloat4*)(uintptr_t)(p.w + (size_t)(c0 + c) * KK * 4);
 #pragma unroll
             for (int ky = 0; ky < K; ++ky) {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void convt7_small_kernel(const l2i_conv_params
                 for (int kx = 0; kx < K; ++kx) {
                     const int px = (kx + 1) & 1;
                     const int rx = (px + PAD - kx) / 2 + 1;            // window column of the first position
-                    const f32x4v w4 = wc[ky * K + kx];
+                    const f32x4 w4 = wc[ky * K + kx];
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         const float x = win[ry][rx + q];

@@ -15,6 +15,7 @@
 #include <math.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 namespace l2i_face {
 
@@ -80,16 +81,6 @@ __global__ __launch_bounds__(FR_THREADS) void face_resize_kernel(float* __restri
 constexpr int HEAD_THREADS = 256;
 constexpr int HEAD_MAXC = 2048;
 constexpr int HEAD_MAXE = 2 * HEAD_THREADS;
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {             // fixed order: deterministic
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // Block j makes samples s[0], s[1]: (j, j + npairs) when pairs are asked for, else (2j, 2j + 1).
 __global__ __launch_bounds__(HEAD_THREADS) void face_head_kernel(float* __restrict__ emb, double* __restrict__ dist, const float* __restrict__ feat,

@@ -15,8 +15,8 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace gm {
 constexpr int CK = 16, CKh = 8, BN = 256;              // channels per chunk, pixels per block (4 waves x 64)
@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256, (MASK || NOPS > 0) ? 2 : 3) void gemm1x1_kerne
     const size_t HW = (size_t)p.H * p.W;
 
     const unsigned x_bytes = (unsigned)((size_t)p.Cin * HW * sizeof(float));
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + (size_t)b * p.Cin * HW), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)((MASK ? p.in_mask : p.x) + (size_t)b * p.Cin * HW), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (unsigned)((size_t)p.Cin * p.CoutP * sizeof(float)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(p.x + (size_t)b * p.Cin * HW, x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_m = l2i_buffer_rsrc((MASK ? p.in_mask : p.x) + (size_t)b * p.Cin * HW, x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, (unsigned)((size_t)p.Cin * p.CoutP * sizeof(float)));
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     // x: wave k-th piece = row (k * 4 + wave) of the chunk, lane l = pixels px0 + 4 l .. + 3   (1 KiB contiguous in global and in LDS)
     const unsigned xvoff = (unsigned)((px0 + lane * 4) * sizeof(float));
@@ -56,25 +56,21 @@ __global__ __launch_bounds__(256, (MASK || NOPS > 0) ? 2 : 3) void gemm1x1_kerne
     // Staging of the next chunk in DMA slots (inline asm, not the builtin: hipcc cannot tell the DMA target from the stage being read
     // and would drain vmcnt before the next ds_read, see l2i_wino.hip): slots 0..3 = x rows (k*4 + wave) (+ the mask rows), slots
     // 4..4+WPW-1 = weight pieces.  The K loop issues one slot per k-pair, between the MFMAs; `on` = false swaps in null descriptors.
-    const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_null = l2i_buffer_rsrc(p.x, 0u);
     auto issue_slot = [&](int sl, int c0, float* stage, bool on) {
-        const unsigned lds_x = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)stage;
-        unsigned keep;
+        const unsigned lds_x = l2i_lds_addr(stage);
         if (sl < CK / 4) {
             const int row = sl * 4 + wave_u;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(xvoff), "s"(on ? rs_x : rs_null), "s"(__builtin_amdgcn_readfirstlane(lds_x + row * BN * 4)), "s"((unsigned)(c0 + row) * xrow_b));
+            l2i_lds_dma16<false>(xvoff, on ? rs_x : rs_null, __builtin_amdgcn_readfirstlane(lds_x + row * BN * 4), (unsigned)(c0 + row) * xrow_b);
             if constexpr (MASK)
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(xvoff), "s"(on ? rs_m : rs_null), "s"(__builtin_amdgcn_readfirstlane(lds_x + (XS + row * BN) * 4)), "s"((unsigned)(c0 + row) * xrow_b));
+                l2i_lds_dma16<false>(xvoff, on ? rs_m : rs_null, __builtin_amdgcn_readfirstlane(lds_x + (XS + row * BN) * 4), (unsigned)(c0 + row) * xrow_b);
         } else if (sl < CK / 4 + WPW) {
             const int piece = (sl - CK / 4) * 4 + wave_u;
             const int q = (piece < WPIECES ? piece : 0) * 64 + lane;
             const unsigned wv = (unsigned)((((q / WV)) * p.CoutP + m0 + (q % WV) * 4) * sizeof(float));
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wv), "s"((on && piece < WPIECES) ? rs_w : rs_null),
-                           "s"(__builtin_amdgcn_readfirstlane(lds_x + (XS + MS + (piece < WPIECES ? piece : 0) * 256) * 4)),
-                           "s"((unsigned)((size_t)c0 * p.CoutP * sizeof(float))));
+            l2i_lds_dma16<false>(wv, (on && piece < WPIECES) ? rs_w : rs_null,
+                                 __builtin_amdgcn_readfirstlane(lds_x + (XS + MS + (piece < WPIECES ? piece : 0) * 256) * 4),
+                                 (unsigned)((size_t)c0 * p.CoutP * sizeof(float)));
         }
     };
 

@@ -1,5 +1,5 @@
 // Shared by the h8 (16-bit, channel-blocked) translation units, each compiled once per element type (bf16 as is, IEEE fp16 with -DL2I_H8_F16):
-// element macros, fragment types, the pack / unpack converts, the sign-plane byte and the accumulator -> pixel-slot exchange.
+// element macros, the sign-plane byte and the accumulator -> pixel-slot exchange (fragment type and pack / unpack converts: l2i_device.h).
 #ifndef L2I_H8_COMMON_H
 #define L2I_H8_COMMON_H
 #include <hip/hip_runtime.h>
@@ -7,53 +7,25 @@
 #include "l2i.h"
 #include "l2i_epilogue.h"
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-typedef float f32x2_ __attribute__((ext_vector_type(2)));
-
 // [r5] Every h8 file is compiled twice (csrc/Makefile): as is = bf16 elements (l2i_conv2d_h8, l2i_conv_transpose2d_h8), and with -DL2I_H8_F16 = IEEE
 // fp16 elements (the same entry points with the suffix _f16: BASELINE configs[4] says "fp16 MFMA").  The h8 layout, the DMA pipeline and the
 // epilogues are element-type agnostic; what differs is the MFMA instruction (v_mfma_f32_32x32x16_{bf16,f16}: same rate), the two unpack
 // converts and the packing convert (v_cvt_pk_{bf16,f16}_f32: one instruction per pair, round to nearest even, both).  ReLU-on-load stays the
 // packed integer max: a negative fp16 is a negative int16 as well.  Everything lives in a per-type namespace: two objects with the same
-// template kernels would otherwise be merged by the linker.
+// template kernels would otherwise be merged by the linker (H8S_NS: the namespace of l2i_stream_h8.hip's kernels).
 #ifdef L2I_H8_F16
 #define H8_NS l2i_h8_f16
+#define H8S_NS l2i_h8s_f16
 #define H8_NAME(n) n##_f16
-typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));          // (the fragment type keeps its name: "bf16x8" = eight 16-bit elements)
 #define H8_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
 #else
 #define H8_NS l2i_h8_bf16
+#define H8S_NS l2i_h8s_bf16
 #define H8_NAME(n) n
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define H8_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #endif
 
 namespace H8_NS {
-
-#ifdef L2I_H8_F16
-__device__ __forceinline__ unsigned cvt_pk_bf16_h8(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { float r; asm("v_cvt_f32_f16 %0, %1" : "=v"(r) : "v"(u)); return r; }
-__device__ __forceinline__ float bf16_hi(unsigned u) { float r; asm("v_cvt_f32_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(u)); return r; }
-#else
-__device__ __forceinline__ unsigned cvt_pk_bf16_h8(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-#endif
-
-__device__ __forceinline__ void h8_unpack(const u32x4& u, float (&v)[8]) {
-    v[0] = bf16_lo(u.x); v[1] = bf16_hi(u.x); v[2] = bf16_lo(u.y); v[3] = bf16_hi(u.y);
-    v[4] = bf16_lo(u.z); v[5] = bf16_hi(u.z); v[6] = bf16_lo(u.w); v[7] = bf16_hi(u.w);
-}
 
 // [r6] sign plane: bit e of the byte = (16-bit element e of the slot > 0).  Per dword (two elements): max with 0 as signed 16-bit integers (a negative
 // fp16 / bf16, and -0, is a negative int16) then min with 1 as unsigned -> 0 / 1 in bits 0 and 16; the four dwords shifted by 0, 2, 4, 6 and folded.

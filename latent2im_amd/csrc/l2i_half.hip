@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 __device__ __forceinline__ float hr(float v) { return __half2float(__float2half_rn(v)); }      // round a float result to half precision
 

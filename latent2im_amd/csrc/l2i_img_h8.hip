@@ -21,10 +21,9 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 #include "l2i_epilogue.h"
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8_ __attribute__((ext_vector_type(8)));
 
 namespace img8 {
 constexpr int TH = 8, TW = 64, BM = 64;
@@ -41,12 +40,10 @@ template <int K, int S> struct Geo {
 template <bool F16> struct Elem;
 template <> struct Elem<false> {
     typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-    static __device__ __forceinline__ unsigned pk(float lo, float hi) { unsigned r; asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi)); return r; }
     static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
 template <> struct Elem<true> {
     typedef _Float16 v8 __attribute__((ext_vector_type(8)));
-    static __device__ __forceinline__ unsigned pk(float lo, float hi) { unsigned r; asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi)); return r; }
     static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 }  // namespace img8
@@ -141,7 +138,7 @@ __global__ __launch_bounds__(256, K <= 3 ? 4 : 2) void conv_img_h8_kernel(const 
             const float* rp = pr_ < rows ? bp + c * G::PLANE + ky * G::IWP : zpad;      // rows past Cin K: the zero pad
             // (a compiler-generated conversion, not the inline-asm pack of the epilogue: the hazard recognizer does not look inside inline asm, and an
             // MFMA that reads a VGPR written by the VALU instruction right before it gets the old value — measured: garbage in the first tile only)
-            f32x8_ v;
+            f32x8 v;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = e < K ? rp[e] : 0.f;
             const typename E::v8 bf = __builtin_convertvector(v, typename E::v8);
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(256, K <= 3 ? 4 : 2) void conv_img_h8_kernel(const 
                 const float t = v[e] + bs[q][e];
                 v[e] = fmaxf(t * gpos, t * gneg);
             }
-            const u32x4 out = {E::pk(v[0], v[1]), E::pk(v[2], v[3]), E::pk(v[4], v[5]), E::pk(v[6], v[7])};
+            const u32x4 out = {h8_pk<F16>(v[0], v[1]), h8_pk<F16>(v[2], v[3]), h8_pk<F16>(v[4], v[5]), h8_pk<F16>(v[6], v[7])};
             if (pok && grp * 8 < p.Cout) {
                 const size_t slot = slot0 + (size_t)grp * plane_o;
                 reinterpret_cast<u32x4*>(p.y)[slot] = out;
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(256, K <= 3 ? 4 : 2) void conv_img_h8_kernel(const 
                     const unsigned o4[4] = {out.x, out.y, out.z, out.w}, r4[4] = {rf.x, rf.y, rf.z, rf.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float d0 = l2i_h8_lo(o4[e], F16) - l2i_h8_lo(r4[e], F16), d1 = l2i_h8_hi(o4[e], F16) - l2i_h8_hi(r4[e], F16);
+                        const float d0 = h8_lo(o4[e], F16) - h8_lo(r4[e], F16), d1 = h8_hi(o4[e], F16) - h8_hi(r4[e], F16);
                         sq += d0 * d0 + d1 * d1;
                     }
                 }

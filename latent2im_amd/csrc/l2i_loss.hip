@@ -11,17 +11,9 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 namespace {
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void reg_bce_kernel(double* loss, float* preds, float* g_feat, const float* feat, const float* fc_w, const float* fc_b,
                                                       const int64_t* cols, const void* target, int target_f64, int B, int F, int K, float eps) {
     __shared__ float red[4];
@@ -36,7 +28,7 @@ __global__ __launch_bounds__(256) void reg_bce_kernel(double* loss, float* preds
         const float* w = fc_w + (size_t)cols[k] * F;
         float s = 0.f;
         for (int i = tid; i < F; i += 256) s += x[i] * w[i];
-        return block_sum_256(s, red) + fc_b[cols[k]];
+        return block_sum(s, red) + fc_b[cols[k]];
     };
     for (int k = 0; k < K; ++k) {
         const float p = logit(b, k);

@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 namespace {
 constexpr int BT = 8;          // samples per accumulator pass

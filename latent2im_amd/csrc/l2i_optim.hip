@@ -18,6 +18,7 @@
 #include <math.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 namespace {
 constexpr int NT = 1024;

@@ -24,22 +24,14 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float pf32x16 __attribute__((ext_vector_type(16)));
-typedef float pf32x4 __attribute__((ext_vector_type(4)));
 
 namespace l2i_pair_f32 {
 
 struct PairF32Launch {
     int total, tiles_per_sample, npix, nch;
 };
-
-#define L2I_PF_DMA16(voff, rsrc, ldsaddr, soff)                                                                                            \
-    do {                                                                                                                                   \
-        unsigned keep_;                                                                                                                    \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"     \
-                     : "=&s"(keep_) : "v"(voff), "s"(rsrc), "s"(ldsaddr), "s"(soff) : "memory");                                           \
-    } while (0)
 
 template <int K1, int MC, int WN, int OCC>
 __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_params p1, const l2i_conv_params p2, const PairF32Launch L) {
@@ -68,10 +60,10 @@ __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_param
     const unsigned pix0 = (unsigned)tile * (4u * PXW) + (unsigned)wave_u * PXW;
     const int nch = L.nch, c1n = p1.Cout, c2n = p2.Cout;
 
-    const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p1.w, 0, (unsigned)((size_t)p1.Cin * p1.CoutP * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p2.w, 0, (unsigned)((size_t)p2.Cin * p2.CoutP * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w1 = l2i_buffer_rsrc(p1.w, (unsigned)((size_t)p1.Cin * p1.CoutP * 4));
+    const __amdgpu_buffer_rsrc_t rs_w2 = l2i_buffer_rsrc(p2.w, (unsigned)((size_t)p2.Cin * p2.CoutP * 4));
     const unsigned res_bytes = (unsigned)c1n * npix * 4u;
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(p1.residual) + (size_t)b * res_bytes), 0, res_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_r = l2i_buffer_rsrc(reinterpret_cast<const char*>(p1.residual) + (size_t)b * res_bytes, res_bytes);
 
     // ---- weight DMA: piece q = wave + 4 t.  q < W1P: rows 8 q .. 8 q + 7 of W1[k][32 c ..] (8 lanes = 32 channels a row); else rows of W2[32 c + .][0 .. C3) ----
     unsigned wvoff[NPW];
@@ -86,13 +78,13 @@ __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_param
         }
     }
     auto dma_w = [&](int c, int stage) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage * WSTAGE);
+        const unsigned lds0 = l2i_lds_addr(w_st + stage * WSTAGE);
         const unsigned so1 = (unsigned)c * 32u * 4u, so2 = (unsigned)c * 32u * (unsigned)p2.CoutP * 4u;
 #pragma unroll
         for (int t = 0; t < NPW; ++t) {
             const int q = wave_u + 4 * t;
-            if (q < W1P) L2I_PF_DMA16(wvoff[t], rs_w1, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), so1);
-            else L2I_PF_DMA16(wvoff[t], rs_w2, __builtin_amdgcn_readfirstlane(lds0 + (W1F + (q - W1P) * 256) * 4), so2);
+            if (q < W1P) l2i_lds_dma16(wvoff[t], rs_w1, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), so1);
+            else l2i_lds_dma16(wvoff[t], rs_w2, __builtin_amdgcn_readfirstlane(lds0 + (W1F + (q - W1P) * 256) * 4), so2);
         }
     };
     // ---- identity-map DMA: the wave's [32 channels][PXW pixels] of chunk c into its ring stage: piece p = channels p CPP .. , 16 bytes = 4 pixels per lane ----
@@ -100,10 +92,10 @@ __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_param
     const unsigned rvoff = ((unsigned)(lane / LPC) * npix + pix0 + 4u * (unsigned)(lane % LPC)) * 4u;
     float* const r_mine = r_st + wave * (RS * RF);
     auto dma_r = [&](int c) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(r_mine + (c % RS) * RF);
+        const unsigned lds0 = l2i_lds_addr(r_mine + (c % RS) * RF);
 #pragma unroll
         for (int p = 0; p < RPW; ++p)
-            L2I_PF_DMA16(rvoff, rs_r, __builtin_amdgcn_readfirstlane(lds0 + p * 1024), (unsigned)(32 * c + p * CPP) * npix * 4u);
+            l2i_lds_dma16(rvoff, rs_r, __builtin_amdgcn_readfirstlane(lds0 + p * 1024), (unsigned)(32 * c + p * CPP) * npix * 4u);
     };
 
     // ---- prologue ----
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_param
     for (int i = tid; i < c1n + C3; i += 256) bias_s[i] = i < c1n ? (p1.bias ? p1.bias[i] : 0.f) : (p2.bias ? p2.bias[i - c1n] : 0.f);
     const bool relu1 = p1.act == L2I_ACT_RELU, relu2 = p2.act == L2I_ACT_RELU;
 
-    pf32x16 accC[MC][WN];
+    f32x16 accC[MC][WN];
 #pragma unroll
     for (int m = 0; m < MC; ++m)
 #pragma unroll
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256, OCC) void pair_f32_kernel(const l2i_conv_param
         const float* w1s = w_st + (c & 1) * WSTAGE + half * 32 + j;       // A of K step ks: W1[32 c + j][2 ks + half] = stage[(2 ks + half) * 32 + j]
         const float* w2s = w_st + (c & 1) * WSTAGE + W1F + j;
         const float* rq = r_mine + (c % RS) * RF + j;
-        pf32x16 accB[WN];
+        f32x16 accB[WN];
 #pragma unroll
         for (int n = 0; n < WN; ++n)
 #pragma unroll

@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 #include "l2i_h8_common.h"
 
 namespace H8_NS {
@@ -61,9 +62,9 @@ __device__ __forceinline__ void head3x3_to_frags(const l2i_conv_params& p, u32x4
     const int iy0 = oy0 - 1, ix0 = ox0 - 1;
     const unsigned plane_b = (unsigned)((size_t)p.H * p.W * 16);
     const unsigned in_bytes = (unsigned)(p.Cin / 8) * plane_b;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(p.x) + (size_t)b * in_bytes), 0, in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(reinterpret_cast<const char*>(p.x) + (size_t)b * in_bytes, in_bytes);
     const unsigned wpl_bytes = (unsigned)((size_t)(p.Cin / 16) * 9 * 2 * p.CoutP * 16);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w_hi, 0, wpl_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w_hi, wpl_bytes);
     unsigned ivoff[NPWA];
 #pragma unroll
     for (int t = 0; t < NPWA; ++t) {
@@ -77,12 +78,10 @@ __device__ __forceinline__ void head3x3_to_frags(const l2i_conv_params& p, u32x4
     }
     auto dma_in = [&](int chunk, int stage) {
         const unsigned soff = (unsigned)chunk * 2u * plane_b;
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(in_st + stage * IN_STAGE);
+        const unsigned lds0 = l2i_lds_addr(in_st + stage * IN_STAGE);
 #pragma unroll
         for (int t = 0; t < NPWA; ++t) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(ivoff[t]), "s"(rs_x), "s"(__builtin_amdgcn_readfirstlane(lds0 + (wave_u + 4 * t) * 1024)), "s"(soff) : "memory");
+            l2i_lds_dma16(ivoff[t], rs_x, __builtin_amdgcn_readfirstlane(lds0 + (wave_u + 4 * t) * 1024), soff);
         }
     };
     unsigned wvoff[WPW];
@@ -94,14 +93,12 @@ __device__ __forceinline__ void head3x3_to_frags(const l2i_conv_params& p, u32x4
     }
     auto dma_w = [&](int chunk, int ky, int stage_slot) {
         const unsigned soff = (unsigned)((((size_t)chunk * 9 + ky * 3) * 2) * p.CoutP * 16);
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage_slot);
+        const unsigned lds0 = l2i_lds_addr(w_st + stage_slot);
 #pragma unroll
         for (int t = 0; t < WPW; ++t) {
             const int q = wave_u + 4 * t;
             if (q < WPIECES) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(wvoff[t]), "s"(rs_w), "s"(__builtin_amdgcn_readfirstlane(lds0 + q * 1024)), "s"(soff) : "memory");
+                l2i_lds_dma16(wvoff[t], rs_w, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), soff);
             }
         }
     };
@@ -185,7 +182,7 @@ __device__ __forceinline__ void head3x3_to_frags(const l2i_conv_params& p, u32x4
 #pragma unroll
                     for (int e = 0; e < 8; ++e) g[e] = g[e] > 0.f ? g[e] : 0.f;
                 }
-                const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
+                const u32x4 out = {h8_pk(g[0], g[1]), h8_pk(g[2], g[3]), h8_pk(g[4], g[5]), h8_pk(g[6], g[7])};
                 if (yq) yq[off] = out;
                 if (sq) sq[off] = (uint8_t)h8_sign_byte(out);
                 xf[2 * m + pr][n] = __builtin_bit_cast(bf16x8, out);
@@ -229,10 +226,10 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
 
     // ---- descriptors ----
     const unsigned w1_bytes = (unsigned)((size_t)(p1.Cin / 16) * 2 * p1.CoutP * 16), w2_bytes = (unsigned)((size_t)(p2.Cin / 16) * 2 * p2.CoutP * 16);
-    const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc((void*)p1.w_hi, 0, w1_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc((void*)p2.w_hi, 0, w2_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w1 = l2i_buffer_rsrc(p1.w_hi, w1_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w2 = l2i_buffer_rsrc(p2.w_hi, w2_bytes);
     const unsigned res_bytes = (unsigned)cg1 * npix * 16u;
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(p1.residual) + (size_t)b * res_bytes), 0, res_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_r = l2i_buffer_rsrc(reinterpret_cast<const char*>(p1.residual) + (size_t)b * res_bytes, res_bytes);
 
     // ---- weight DMA: piece q = wave + 4 t; q < KB: K step q of W1 (both lane halves' 32 rows), else a 64-channel run of one (kstep, half) row of W2's slice ----
     unsigned wvoff[NPW];
@@ -246,19 +243,16 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
         }
     }
     auto dma_w = [&](int c, int stage) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(w_st + stage * WSTAGE);
+        const unsigned lds0 = l2i_lds_addr(w_st + stage * WSTAGE);
         const unsigned so1 = (unsigned)c * 32u * 16u, so2 = (unsigned)c * 64u * (unsigned)p2.CoutP;       // W2 slice: K steps 2 c, 2 c + 1 = rows (2 c) * 2 .. of [kstep][half][CoutP] slots
 #pragma unroll
         for (int t = 0; t < NPW; ++t) {
             const int q = wave_u + 4 * t;
-            unsigned keep;
             if (q < KB) {
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(wvoff[t]), "s"(rs_w1), "s"(__builtin_amdgcn_readfirstlane(lds0 + q * 1024)), "s"(so1) : "memory");
+                l2i_lds_dma16(wvoff[t], rs_w1, __builtin_amdgcn_readfirstlane(lds0 + q * 1024), so1);
             } else {
                 const int q2 = q - KB, r = q2 / (MC / 2), i64 = q2 - r * (MC / 2);
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(wvoff[t]), "s"(rs_w2), "s"(__builtin_amdgcn_readfirstlane(lds0 + (W1S + r * C3 + i64 * 64) * 16)), "s"(so2) : "memory");
+                l2i_lds_dma16(wvoff[t], rs_w2, __builtin_amdgcn_readfirstlane(lds0 + (W1S + r * C3 + i64 * 64) * 16), so2);
             }
         }
     };
@@ -268,15 +262,12 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
     for (int n = 0; n < WN; ++n) rvoff[n] = ((unsigned)half * npix + pixn[n] + (unsigned)j) * 16u;
     u32x4* const r_mine = r_st + wave * (RS * RPW * 64);
     auto dma_r = [&](int c) {
-        const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(r_mine + (c % RS) * (RPW * 64));
+        const unsigned lds0 = l2i_lds_addr(r_mine + (c % RS) * (RPW * 64));
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr)
 #pragma unroll
             for (int n = 0; n < WN; ++n) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(rvoff[n]), "s"(rs_r), "s"(__builtin_amdgcn_readfirstlane(lds0 + (pr * WN + n) * 1024)),
-                               "s"((unsigned)(4 * c + 2 * pr) * npix * 16u) : "memory");
+                l2i_lds_dma16(rvoff[n], rs_r, __builtin_amdgcn_readfirstlane(lds0 + (pr * WN + n) * 1024), (unsigned)(4 * c + 2 * pr) * npix * 16u);
             }
     };
 
@@ -379,7 +370,7 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
 #pragma unroll
                     for (int e = 0; e < 8; ++e) g[e] = g[e] > 0.f ? g[e] : 0.f;
                 }
-                const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
+                const u32x4 out = {h8_pk(g[0], g[1]), h8_pk(g[2], g[3]), h8_pk(g[4], g[5]), h8_pk(g[6], g[7])};
                 const size_t off = (size_t)(4 * c + 2 * pr) * npix + pixn[n];
                 y1b[off] = out;
                 if (sign1) s1b[off] = (uint8_t)h8_sign_byte(out);
@@ -428,7 +419,7 @@ __global__ __launch_bounds__(256, OCC) void pair_h8_kernel(const l2i_conv_params
 #pragma unroll
                     for (int e = 0; e < 8; ++e) g[e] = g[e] > 0.f ? g[e] : 0.f;
                 }
-                const u32x4 out = {cvt_pk_bf16_h8(g[0], g[1]), cvt_pk_bf16_h8(g[2], g[3]), cvt_pk_bf16_h8(g[4], g[5]), cvt_pk_bf16_h8(g[6], g[7])};
+                const u32x4 out = {h8_pk(g[0], g[1]), h8_pk(g[2], g[3]), h8_pk(g[4], g[5]), h8_pk(g[6], g[7])};
                 y2b[off] = out;
                 if (s2b) s2b[off] = (uint8_t)h8_sign_byte(out);
             }

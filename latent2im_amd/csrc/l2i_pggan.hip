@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 // y[b,c,p] = lrelu(x[b,c,p] * rsqrt(mean_c x[b,c,p]^2 + eps), slope)          (slope = 1: plain PixelNorm)
 // V = pixels per thread (4: 16-byte accesses, HW % 4 == 0; 1: any HW, e.g. the [B, 511] latent code with HW = 1)

@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 static thread_local char g_err[256] = "";
@@ -20,12 +21,6 @@ int l2i_set_error(int code, const char* msg) {
 extern "C" const char* l2i_last_error(void) { return g_err; }
 extern "C" int l2i_abi_version(void) { return L2I_ABI_VERSION; }
 extern "C" int l2i_sizeof_conv_params(void) { return (int)sizeof(l2i_conv_params); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // fused_bias_act: reference op/fused_bias_act_kernel.cu:18-49 (all act*10+grad cases)

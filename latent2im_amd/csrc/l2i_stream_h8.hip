@@ -10,47 +10,12 @@
 #include <stdlib.h>
 #include "l2i.h"
 #include "l2i_internal.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "l2i_device.h"
+#include "l2i_h8_common.h"
 
 // [r5] Compiled twice like l2i_conv_h8.hip: bf16 elements as is, IEEE fp16 elements with -DL2I_H8_F16 (entry points with the suffix _f16).
-// Only the three converts below know the element type.
-#ifdef L2I_H8_F16
-#define H8_NS l2i_h8s_f16
-#define H8_NAME(n) n##_f16
-#else
-#define H8_NS l2i_h8s_bf16
-#define H8_NAME(n) n
-#endif
-
-namespace H8_NS {
-namespace {
-#ifdef L2I_H8_F16
-__device__ __forceinline__ float blo(unsigned u) { float r; asm("v_cvt_f32_f16 %0, %1" : "=v"(r) : "v"(u)); return r; }
-__device__ __forceinline__ float bhi(unsigned u) { float r; asm("v_cvt_f32_f16_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(r) : "v"(u)); return r; }
-#else
-__device__ __forceinline__ float blo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-#endif
-__device__ __forceinline__ void unpack8(const u32x4& u, float (&v)[8]) {
-    v[0] = blo(u.x); v[1] = bhi(u.x); v[2] = blo(u.y); v[3] = bhi(u.y); v[4] = blo(u.z); v[5] = bhi(u.z); v[6] = blo(u.w); v[7] = bhi(u.w);
-}
-__device__ __forceinline__ unsigned pk(float lo, float hi) {
-    unsigned r;
-#ifdef L2I_H8_F16
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-#else
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-#endif
-    return r;
-}
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) { return u32x4{pk(v[0], v[1]), pk(v[2], v[3]), pk(v[4], v[5]), pk(v[6], v[7])}; }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-}
+// Only the converts of l2i_device.h know the element type.
+namespace H8S_NS {
 
 // ---- layout casts ---------------------------------------------------------------------------------------------------------------------
 // y[b][g][p][e] = bf16(x[b][8 g + e][p]) (zero for channels >= C); lane = pixel: eight strided 4-byte reads (each a coalesced 256-byte row
@@ -63,7 +28,7 @@ __global__ __launch_bounds__(256) void cast_f32_to_h8_kernel(u32x4* __restrict__
         float v[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (8 * g + e < C) ? x[(b * C + 8 * g + e) * HW + pix] : 0.f;
-        y[i] = pack8(v);
+        y[i] = h8_pack(v);
     }
 }
 __global__ __launch_bounds__(256) void cast_h8_to_f32_kernel(float* __restrict__ y, const u32x4* __restrict__ x, int C, int G8, long long HW, long long total) {
@@ -72,7 +37,7 @@ __global__ __launch_bounds__(256) void cast_h8_to_f32_kernel(float* __restrict__
         const int g = (int)(bg % G8);
         const long long b = bg / G8;
         float v[8];
-        unpack8(x[i], v);
+        h8_unpack(x[i], v);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
             if (8 * g + e < C) y[(b * C + 8 * g + e) * HW + pix] = v[e];
@@ -126,7 +91,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_kernel(u32x4* __restrict__ y
                 if (ix >= in_w) continue;
                 const float t = taps[(kh - 1 - ky) * kw + (kw - 1 - kx)];
                 float v[8];
-                unpack8(xp[(long long)iy * in_w + ix], v);
+                h8_unpack(xp[(long long)iy * in_w + ix], v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] += t * v[e];
             }
@@ -145,17 +110,17 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_kernel(u32x4* __restrict__ y
         }
         if (mask) {                                            // a gradient through a (leaky) ReLU: * (mask > 0 ? mpos : mneg)
             float m[8];
-            unpack8(mask[i], m);
+            h8_unpack(mask[i], m);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] *= m[e] > 0.f ? mpos : mneg;
         }
         if (addend) {
             float a[8];
-            unpack8(addend[i], a);
+            h8_unpack(addend[i], a);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += a[e];
         }
-        y[i] = pack8(acc);
+        y[i] = h8_pack(acc);
     }
 }
 // Separable 4x4 FIR without resampling (up = down = 1: the blurs of the generator's up layers and of the discriminator, forward and backward — 90 %
@@ -193,7 +158,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_kernel(u32x4* __restric
         const int ox = chunk * 61 + lane - 3;                  // this lane's output column (lanes 0-2: none)
         const int ix = ox - pad_x0 + 3;                        // its input column: the LAST tap of its window
         const bool colok = ix >= 0 && ix < in_w;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + pl * (long long)in_h * in_w), 0, plane_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = l2i_buffer_rsrc(x + pl * (long long)in_h * in_w, plane_bytes);
         const int g = (int)(pl % G8);
         const long long b = pl / G8;
         float bs[8];
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_kernel(u32x4* __restric
             const int r = rb + i;
             if (r >= NR) break;
             float v[8];
-            unpack8(q[i], v);
+            h8_unpack(q[i], v);
             q[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, r + PF < NR ? off(r + PF) : -1, 0, 0));
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -261,19 +226,19 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_kernel(u32x4* __restric
                         for (int e = 0; e < 8; ++e) acc[e] *= ((mb >> e) & 1u) ? mpos : mneg;
                     } else {
                         float m[8];
-                        unpack8(mq[(i + 1) & 3], m);
+                        h8_unpack(mq[(i + 1) & 3], m);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc[e] *= m[e] > 0.f ? mpos : mneg;
                     }
                 }
                 if (addend) {
                     float a2[8];
-                    unpack8(aq[(i + 1) & 3], a2);
+                    h8_unpack(aq[(i + 1) & 3], a2);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[e] += a2[e];
                 }
                 if (j + EP < RB) issue_ops(j + EP, (i + 1) & 3);
-                if (lane_out && oy < out_h) y[(pl * out_h + oy) * out_w + ox] = pack8(acc);
+                if (lane_out && oy < out_h) y[(pl * out_h + oy) * out_w + ox] = h8_pack(acc);
             }
           }
         }
@@ -307,7 +272,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_down2_kernel(u32x4* __r
         const int ox = chunk * 62 + lane - 1;                  // lanes 1 .. 62 store
         const int ixa = 2 * ox, ixb = 2 * ox + 1;
         const bool oka = ixa >= 0 && ixa < in_w, okb = ixb >= 0 && ixb < in_w;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + pl * (long long)in_h * in_w), 0, plane_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = l2i_buffer_rsrc(x + pl * (long long)in_h * in_w, plane_bytes);
         const int iy0 = 2 * r0 - 1;
         auto offa = [&](int r) -> int { return oka ? ((iy0 + r) * in_w + ixa) * 16 : -1; };
         auto offb = [&](int r) -> int { return okb ? ((iy0 + r) * in_w + ixb) * 16 : -1; };
@@ -322,8 +287,8 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_down2_kernel(u32x4* __r
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             float va[8], vb[8];
-            unpack8(qa[r % PF], va);
-            unpack8(qb[r % PF], vb);
+            h8_unpack(qa[r % PF], va);
+            h8_unpack(qb[r % PF], vb);
             if (r + PF < NR) {
                 qa[r % PF] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, offa(r + PF), 0, 0));
                 qb[r % PF] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, offb(r + PF), 0, 0));
@@ -337,7 +302,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_down2_kernel(u32x4* __r
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     acc[e] = ty.x * ring[(r - 3) & 3][e] + ty.y * ring[(r - 2) & 3][e] + ty.z * ring[(r - 1) & 3][e] + ty.w * ring[r & 3][e];
-                if (lane_out && oy < out_h) y[(pl * out_h + oy) * out_w + ox] = pack8(acc);
+                if (lane_out && oy < out_h) y[(pl * out_h + oy) * out_w + ox] = h8_pack(acc);
             }
         }
     }
@@ -359,7 +324,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_up2_kernel(u32x4* __res
         const int r0 = band * RB;
         const int jx = chunk * 62 + lane - 1;                  // this lane's input column; lanes 1 .. 62 store output columns 2 jx, 2 jx + 1
         const bool ok = jx >= 0 && jx < in_w;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + pl * (long long)in_h * in_w), 0, plane_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = l2i_buffer_rsrc(x + pl * (long long)in_h * in_w, plane_bytes);
         auto off = [&](int r) -> int { return ok ? ((r0 - 1 + r) * in_w + jx) * 16 : -1; };      // rows above / below the map: out of range, zeros
         const bool lane_out = lane >= 1 && lane <= 62 && ok;
         u32x4* const yp = y + pl * (long long)out_h * out_w + 2 * jx;
@@ -382,7 +347,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_up2_kernel(u32x4* __res
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             float v[8], he[8], ho[8];
-            unpack8(q[r % PF], v);
+            h8_unpack(q[r % PF], v);
             if (r + PF < NR) q[r % PF] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off(r + PF), 0, 0));
             if (ap && r + 1 < NR) issue_add(r + 1, (r + 1) & 1);
 #pragma unroll
@@ -398,11 +363,11 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_up2_kernel(u32x4* __res
                 for (int e = 0; e < 8; ++e) { a0[e] = fmaf(ty.y, pe[e], ty.w * he[e]); a1[e] = fmaf(ty.y, po[e], ty.w * ho[e]); }
                 if (ap) {
                     float t0[8], t1[8];
-                    unpack8(ad[r & 1][0], t0); unpack8(ad[r & 1][1], t1);
+                    h8_unpack(ad[r & 1][0], t0); h8_unpack(ad[r & 1][1], t1);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { a0[e] += t0[e]; a1[e] += t1[e]; }
                 }
-                if (lane_out && oy < out_h) { yp[(long long)oy * out_w] = pack8(a0); yp[(long long)oy * out_w + 1] = pack8(a1); }
+                if (lane_out && oy < out_h) { yp[(long long)oy * out_w] = h8_pack(a0); yp[(long long)oy * out_w + 1] = h8_pack(a1); }
             }
             if (r >= 1 && r <= RB) {                            // even output row of input row i: t0 H[i-1] + t2 H[i]
                 const int oy = 2 * i;
@@ -411,11 +376,11 @@ __global__ __launch_bounds__(256) void upfirdn2d_h8_sep4_up2_kernel(u32x4* __res
                 for (int e = 0; e < 8; ++e) { a0[e] = fmaf(ty.x, pe[e], ty.z * he[e]); a1[e] = fmaf(ty.x, po[e], ty.z * ho[e]); }
                 if (ap) {
                     float t0[8], t1[8];
-                    unpack8(ad[r & 1][2], t0); unpack8(ad[r & 1][3], t1);
+                    h8_unpack(ad[r & 1][2], t0); h8_unpack(ad[r & 1][3], t1);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) { a0[e] += t0[e]; a1[e] += t1[e]; }
                 }
-                if (lane_out && oy < out_h) { yp[(long long)oy * out_w] = pack8(a0); yp[(long long)oy * out_w + 1] = pack8(a1); }
+                if (lane_out && oy < out_h) { yp[(long long)oy * out_w] = h8_pack(a0); yp[(long long)oy * out_w + 1] = h8_pack(a1); }
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) { pe[e] = he[e]; po[e] = ho[e]; }
@@ -503,7 +468,7 @@ __global__ __launch_bounds__(256) void torgb_fwd_h8_kernel(float* __restrict__ r
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 float v[8];
-                unpack8(q[u], v);
+                h8_unpack(q[u], v);
                 const float4 w0a = wl4[2 * (g + u)], w0b = wl4[2 * (g + u) + 1], w1a = wl4[C4 + 2 * (g + u)], w1b = wl4[C4 + 2 * (g + u) + 1];
                 const float4 w2a = wl4[2 * C4 + 2 * (g + u)], w2b = wl4[2 * C4 + 2 * (g + u) + 1];
                 const float w0[8] = {w0a.x, w0a.y, w0a.z, w0a.w, w0b.x, w0b.y, w0b.z, w0b.w}, w1[8] = {w1a.x, w1a.y, w1a.z, w1a.w, w1b.x, w1b.y, w1b.z, w1b.w};
@@ -514,7 +479,7 @@ __global__ __launch_bounds__(256) void torgb_fwd_h8_kernel(float* __restrict__ r
         }
         for (; g < G8; ++g) {
             float v[8];
-            unpack8(xp[(size_t)g * HW], v);
+            h8_unpack(xp[(size_t)g * HW], v);
 #pragma unroll
             for (int e = 0; e < 8; ++e) { a0 += v[e] * wl[8 * g + e]; a1 += v[e] * wl[C + 8 * g + e]; a2 += v[e] * wl[2 * C + 8 * g + e]; }
         }
@@ -591,8 +556,8 @@ __global__ __launch_bounds__(256) void sg2_act_bwd_h8_kernel(u32x4* __restrict__
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && !two) break;
             float yv[8], gv[8], d[8];
-            unpack8(h ? yq1 : yq0, yv);
-            unpack8(h ? gq1 : gq0, gv);
+            h8_unpack(h ? yq1 : yq0, yv);
+            h8_unpack(h ? gq1 : gq0, gv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float gg = gv[e] * sc[e];
@@ -604,7 +569,7 @@ __global__ __launch_bounds__(256) void sg2_act_bwd_h8_kernel(u32x4* __restrict__
                 r1[e] += d[e] * zpre;
                 r2[0][e] += yv[e] * q[h][0]; r2[1][e] += yv[e] * q[h][1]; r2[2][e] += yv[e] * q[h][2];
             }
-            dz[base + (h ? pix2 : pix)] = pack8(d);
+            dz[base + (h ? pix2 : pix)] = h8_pack(d);
         }
     }
     // block-level reduction: wave sums meet in LDS, ONE atomic per block and sum (the per-wave atomics of the first version were the
@@ -613,16 +578,16 @@ __global__ __launch_bounds__(256) void sg2_act_bwd_h8_kernel(u32x4* __restrict__
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float s0 = wave_sum(r1[e]);
+        const float s0 = wave_sum_all(r1[e]);
         if (lane == 0) part[wv][e] = s0;
         if (gin && red_gin_y) {
-            const float t = wave_sum(r3[e]);
+            const float t = wave_sum_all(r3[e]);
             if (lane == 0) part[wv][32 + e] = t;
         }
         if (red_x_grgb) {
 #pragma unroll
             for (int o = 0; o < 3; ++o) {
-                const float t = wave_sum(r2[o][e]);
+                const float t = wave_sum_all(r2[o][e]);
                 if (lane == 0) part[wv][8 + 3 * e + o] = t;
             }
         }
@@ -667,13 +632,13 @@ __global__ __launch_bounds__(256) void dot_reduce_h8_kernel(float* __restrict__ 
         const long long p2 = two ? pix2 : pix;
         const u32x4 a0 = a[base + pix], a1 = a[base + p2];
         float av[8], bv[8], cv[8], dv[8];
-        unpack8(a0, av);
-        unpack8(a1, cv);
+        h8_unpack(a0, av);
+        h8_unpack(a1, cv);
         const float w2 = two ? 1.f : 0.f;
         if (bb) {
             const u32x4 b0 = bb[base + pix], b1 = bb[base + p2];
-            unpack8(b0, bv);
-            unpack8(b1, dv);
+            h8_unpack(b0, bv);
+            h8_unpack(b1, dv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) r[e] += av[e] * bv[e] + w2 * (cv[e] * dv[e]);
         } else {
@@ -685,7 +650,7 @@ __global__ __launch_bounds__(256) void dot_reduce_h8_kernel(float* __restrict__ 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        const float t = wave_sum(r[e]);
+        const float t = wave_sum_all(r[e]);
         if (lane == 0) part[wv][e] = t;
     }
     __syncthreads();
@@ -721,7 +686,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_h8_kernel(u32x4* __restrict__
                 const int ix = ox * s - pad + kx;
                 if (ix < 0 || ix >= W) continue;
                 float v[8];
-                unpack8(xp[(long long)iy * W + ix], v);
+                h8_unpack(xp[(long long)iy * W + ix], v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     if (!found || v[e] > best[e] || (v[e] != v[e])) { best[e] = v[e]; bi[e] = (unsigned)(ky * k + kx); }
@@ -732,7 +697,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_h8_kernel(u32x4* __restrict__
 #pragma unroll
             for (int e = 0; e < 8; ++e) best[e] = best[e] > 0.f ? best[e] : (best[e] != best[e] ? best[e] : 0.f);
         }
-        y[i] = pack8(best);
+        y[i] = h8_pack(best);
         idx[i] = make_uint2(bi[0] | (bi[1] << 8) | (bi[2] << 16) | (bi[3] << 24), bi[4] | (bi[5] << 8) | (bi[6] << 16) | (bi[7] << 24));
     }
 }
@@ -762,7 +727,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_h8_kernel(u32x4* __restrict__
                 const long long o = pl * OH * OW + (long long)oy * OW + ox;
                 const uint2 id = idx[o];
                 float g[8];
-                unpack8(gy[o], g);
+                h8_unpack(gy[o], g);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const unsigned w8 = ((e < 4 ? id.x : id.y) >> (8 * (e & 3))) & 0xffu;
@@ -772,12 +737,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_h8_kernel(u32x4* __restrict__
         }
         if (a) {
             float av[8], bv[8];
-            unpack8(a[i], av);
-            unpack8(bq[i], bv);
+            h8_unpack(a[i], av);
+            h8_unpack(bq[i], bv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += cf * (bv[e] - av[e]);
         }
-        gx[i] = pack8(acc);
+        gx[i] = h8_pack(acc);
     }
 }
 extern "C" int H8_NAME(l2i_maxpool2d_fwd_h8)(void* y, void* idx, const void* x, int64_t planes, int H, int W, int k, int s, int pad, int OH, int OW, int relu, void* stream) {
@@ -805,14 +770,14 @@ __global__ __launch_bounds__(256) void sqdiff_h8_kernel(float* __restrict__ sum_
     float s = 0.f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float av[8], bv[8], g[8];
-        unpack8(a[i], av);
-        unpack8(b[i], bv);
+        h8_unpack(a[i], av);
+        h8_unpack(b[i], bv);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float d = bv[e] - av[e]; s += d * d; g[e] = cf * d; }
-        if (grad) grad[i] = pack8(g);
+        if (grad) grad[i] = h8_pack(g);
     }
     if (sum_out) {
-        s = wave_sum(s);
+        s = wave_sum_all(s);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
         __syncthreads();
         if (threadIdx.x == 0) atomicAdd(sum_out, (red[0] + red[1]) + (red[2] + red[3]));
@@ -837,17 +802,17 @@ __global__ __launch_bounds__(256) void add_zero_insert_h8_kernel(u32x4* __restri
         if (2 * oy >= H || 2 * ox >= W) continue;
         const long long o = pl * H * W + (long long)(2 * oy) * W + 2 * ox;
         float a[8], b[8];
-        unpack8(y[o], a);
-        unpack8(c[i], b);
+        h8_unpack(y[o], a);
+        h8_unpack(c[i], b);
         if (mask) {                                            // ReLU mask of the map the sum is the gradient of
             float m[8];
-            unpack8(mask[o], m);
+            h8_unpack(mask[o], m);
 #pragma unroll
             for (int e = 0; e < 8; ++e) b[e] = m[e] > 0.f ? b[e] : 0.f;
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] += b[e];
-        y[o] = pack8(a);
+        y[o] = h8_pack(a);
     }
 }
 extern "C" int H8_NAME(l2i_add_zero_insert_h8)(void* y, const void* c, const void* mask, int64_t planes, int H, int W, int OH, int OW, void* stream) {
@@ -871,7 +836,7 @@ __global__ __launch_bounds__(256) void modulate_planes_kernel(u32x4* __restrict_
         const float4 w0 = *reinterpret_cast<const float4*>(w32 + sl * 8), w1 = *reinterpret_cast<const float4*>(w32 + sl * 8 + 4);
         const float* sp = s + b * Cs + 16 * c16 + 8 * half;
         float v[8] = {w0.x * sp[0], w0.y * sp[1], w0.z * sp[2], w0.w * sp[3], w1.x * sp[4], w1.y * sp[5], w1.z * sp[6], w1.w * sp[7]};
-        planes[i] = pack8(v);
+        planes[i] = h8_pack(v);
     }
 }
 extern "C" int H8_NAME(l2i_modulate_planes_h8)(void* planes, const float* w32, const float* s, int B, int Cs, int CinP, int KK, int CoutP, void* stream) {
@@ -906,7 +871,7 @@ __global__ __launch_bounds__(256) void modulate_planes_multi_kernel(u32x4* __res
         const float4 w0 = *reinterpret_cast<const float4*>(wl + slot * 8), w1 = *reinterpret_cast<const float4*>(wl + slot * 8 + 4);
         const float* sp = sl + b * Cs + 16 * c16 + 8 * half;
         float v[8] = {w0.x * sp[0], w0.y * sp[1], w0.z * sp[2], w0.w * sp[3], w1.x * sp[4], w1.y * sp[5], w1.z * sp[6], w1.w * sp[7]};
-        out[i] = pack8(v);
+        out[i] = h8_pack(v);
     }
 }
 extern "C" int H8_NAME(l2i_modulate_planes_multi_h8)(void* planes, const float* w32, const float* s, const void* table, int nseg, int B, int nblocks, void* stream) {
@@ -921,22 +886,22 @@ extern "C" int H8_NAME(l2i_modulate_planes_multi_h8)(void* planes, const float* 
 __global__ __launch_bounds__(256) void mask_mul_h8_kernel(u32x4* __restrict__ y, const u32x4* __restrict__ g, const u32x4* __restrict__ ref, float pos, float neg, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float a[8], m[8];
-        unpack8(g[i], a);
-        unpack8(ref[i], m);
+        h8_unpack(g[i], a);
+        h8_unpack(ref[i], m);
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] *= m[e] > 0.f ? pos : neg;
-        y[i] = pack8(a);
+        y[i] = h8_pack(a);
     }
 }
 // [r6] the same with `ref` given as its sign plane (one byte per slot)
 __global__ __launch_bounds__(256) void mask_mul_bits_h8_kernel(u32x4* __restrict__ y, const u32x4* __restrict__ g, const uint8_t* __restrict__ bits, float pos, float neg, long long n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float a[8];
-        unpack8(g[i], a);
+        h8_unpack(g[i], a);
         const unsigned mb = bits[i];
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] *= ((mb >> e) & 1u) ? pos : neg;
-        y[i] = pack8(a);
+        y[i] = h8_pack(a);
     }
 }
 extern "C" int H8_NAME(l2i_mask_mul_bits_h8)(void* y, const void* g, const void* bits, float pos, float neg, int64_t slots, void* stream) {
@@ -952,4 +917,4 @@ extern "C" int H8_NAME(l2i_mask_mul_h8)(void* y, const void* g, const void* ref,
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }
-}  // namespace H8_NS
+}  // namespace H8S_NS

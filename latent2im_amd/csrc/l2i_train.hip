@@ -17,8 +17,8 @@
 #include <stdint.h>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WgradParams {
     const float* x; const float* gy; float* dw;
@@ -101,12 +101,6 @@ extern "C" int l2i_conv2d_wgrad_f32(float* dw, const float* x, const float* gy, 
 // ---------------------------------------------------------------------------------------------------------------
 // BatchNorm2d, training mode
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // grid (C, chunks): block sums one slice of channel c over all samples
 __global__ __launch_bounds__(256) void bn_stats_kernel(double* __restrict__ sum, double* __restrict__ sumsq, const float* __restrict__ x,
                                                        int B, int C, long long HW) {
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(double* __restrict__ sum,
         s += v; q += v * v;
     }
     __shared__ double sh[2][4];
-    s = wave_sum_d(s); q = wave_sum_d(q);
+    s = wave_sum(s); q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(double* __restrict__
         q += (double)dy * (double)((x[idx] - mu) * is);
     }
     __shared__ double sh[2][4];
-    s = wave_sum_d(s); q = wave_sum_d(q);
+    s = wave_sum(s); q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = s; sh[1][threadIdx.x >> 6] = q; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -32,30 +32,16 @@
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// Packed fp32 VALU (two independent lanes of work per issue slot).  Inline asm because hipcc scalarises most f32x2
-// arithmetic (and cannot see hazards inside asm: see pk_mul_op).  [r3] A/B against the same arithmetic as two single-lane
-// v_add / v_sub / v_mul per packed instruction (one asm statement each, so that the SLP vectoriser cannot re-pack them), interleaved in one
-// process on fifteen launch shapes of the step: the single-lane build is 1.2 - 6.4 % SLOWER on every shape.  Packed stays.
-__device__ __forceinline__ f32x2 pk_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x2 pk_mul(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// pk_mul_op: the product feeds an MFMA next, the 2 wait states of "VALU write -> MFMA read" ride in the same asm statement
-__device__ __forceinline__ f32x2 pk_mul_op(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2\n\ts_nop 1" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// (a.lo + b.hi, a.lo - b.hi).  The half selection sits on SRC0 (b first: the sum commutes, the bits are the same): packed fp32 with op_sel set on
-// src1 (the first form of this helper, and what hipcc's SLP vectorizer emits) returns sporadically wrong results while a bf16-MFMA kernel is resident
-// on the same CUs; op_sel on src0, op_sel_hi and plain operands do not (tools/probes/pk_beside_conv_h8.py).  No configuration
+// (a.lo + b.hi, a.lo - b.hi).  The half selection sits on SRC0 (b first: the sum commutes, the bits are the same), not on src1 as in the first form
+// of this helper: the rule and its evidence are in l2i_device.h.  No configuration
 // of the step runs this kernel beside a bf16-MFMA one; tools/probes/wino_beside_conv_h8.py does: 170-197 distinct results in 200 before, 1 now.
 __device__ __forceinline__ f32x2 pk_lo_pm_hi(f32x2 a, f32x2 b) {
     f32x2 r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(b), "v"(a)); return r;
 }
-// the same two with the "VALU write -> MFMA read" wait states attached (layers without a style scale feed them to the MFMAs directly)
-__device__ __forceinline__ f32x2 pk_sub_op(f32x2 a, f32x2 b) {
-    f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 1" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
+// the same with the "VALU write -> MFMA read" wait states attached (layers without a style scale feed it to the MFMAs directly, like pk_sub_op)
 __device__ __forceinline__ f32x2 pk_lo_pm_hi_op(f32x2 a, f32x2 b) {
     f32x2 r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[1,0]\n\ts_nop 1" : "=v"(r) : "v"(b), "v"(a)); return r;
 }
@@ -119,11 +105,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
     const unsigned plane_b = (unsigned)((size_t)p.H * p.W * sizeof(float));
     const unsigned in_bytes = (unsigned)p.Cin * plane_b;
     const size_t smp = (size_t)b * p.Cin * ((size_t)p.H * p.W);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x + smp), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void*)((MASK ? p.in_mask : p.x) + smp), 0, in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (unsigned)((size_t)p.Cin * 16 * p.CoutP * sizeof(float)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)((p.in_scale ? p.in_scale : p.x) + (size_t)b * p.Cin), 0,
-                                                                            p.in_scale ? (unsigned)(p.Cin * sizeof(float)) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc(p.x + smp, in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_m = l2i_buffer_rsrc((MASK ? p.in_mask : p.x) + smp, in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, (unsigned)((size_t)p.Cin * 16 * p.CoutP * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t rs_s = l2i_buffer_rsrc((p.in_scale ? p.in_scale : p.x) + (size_t)b * p.Cin,
+                                                                            p.in_scale ? (unsigned)(p.Cin * sizeof(float)) : 0u);
     unsigned voff[NIN];
     {   // element e = tid + 256 u of the [CK][IH][IW] tile -> (c, iy, ix), walked incrementally (256 = 7 * 34 + 18: one division for u = 0 instead of
         // two per slot: every VALU instruction of this kernel is matrix time lost, and at Cin = 32 .. 64 a block has only 4 .. 8 chunks to amortise it)
@@ -152,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
     // LDS target from the stage being read and drains vmcnt before the next ds_read; the explicit vmcnt(0) before the publishing
     // barrier is in the chunk loop), slots NWV.. = raw halo elements (+ the style scale) into registers.  `on` = false (no next
     // chunk) swaps in null descriptors: no traffic, zeros.  compute() issues two slots per MFMA group, between the MFMAs.
-    const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_null = l2i_buffer_rsrc(p.x, 0u);
     constexpr int NSLOT = NWV + NIN + (MASK ? 1 : 0);
     // [r3] Unmasked path: the raw tile is fetched TWO chunks ahead into a ring of three LDS stages (c0r / rstage), U one chunk ahead (c0 /
     // ustage): a chunk is ~1.2 us of matrix work, and on the high-resolution layers (2 GB inputs streamed from HBM while the chip moves
@@ -162,10 +148,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
     auto issue_slot = [&](int sl, int c0, float* ustage, int c0r, float* rstage, bool on) {
         if (sl < NWV) {
             const unsigned sw = (unsigned)((size_t)c0 * 4 * p.CoutP * 16);
-            const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(ustage + wave_u * 256);
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(on ? rs_w : rs_null), "s"(__builtin_amdgcn_readfirstlane(lds0 + sl * 4096)), "s"(sw + sl * wstep));
+            const unsigned lds0 = l2i_lds_addr(ustage + wave_u * 256);
+            l2i_lds_dma16<false>(wvoff, on ? rs_w : rs_null, __builtin_amdgcn_readfirstlane(lds0 + sl * 4096), sw + sl * wstep);
         } else if (sl < NWV + NIN) {
             const int u = sl - NWV;
             const unsigned so = (unsigned)(MASK ? c0 : c0r) * plane_b;
@@ -173,10 +157,8 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
                 rin[u] = __builtin_amdgcn_raw_buffer_load_b32(on ? rs_x : rs_null, voff[u], so, 0);
                 rmk[u] = __builtin_amdgcn_raw_buffer_load_b32(on ? rs_m : rs_null, voff[u], so, 0);
             } else {                                       // element e = u * 256 + tid lands at rstage[e]: lane l of the wave at M0 base + 4 l
-                const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(rstage + wave_u * 64);
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(voff[u]), "s"(on ? rs_x : rs_null), "s"(__builtin_amdgcn_readfirstlane(lds0 + u * 1024)), "s"(so));
+                const unsigned lds0 = l2i_lds_addr(rstage + wave_u * 64);
+                l2i_lds_dma4(voff[u], on ? rs_x : rs_null, __builtin_amdgcn_readfirstlane(lds0 + u * 1024), so);
             }
         } else if (MASK && sl == NWV + NIN) {
             rsc = __builtin_amdgcn_raw_buffer_load_b32(on ? rs_s : rs_null, svoff, (unsigned)(c0 * sizeof(float)), 0);

@@ -25,9 +25,8 @@
 #include <type_traits>
 #include "l2i.h"
 #include "l2i_internal.h"
+#include "l2i_device.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace w4 {
 constexpr int BM = 16, CK = 4;
@@ -57,12 +56,7 @@ struct Wino4Launch {
     int nchunks;                       // Cin / 4
 };
 
-// ---- packed fp32 VALU helpers (inline asm: hipcc scalarises f32x2 arithmetic).  Constants come in SGPR pairs. ----
-#define W4_PK3(name, text)                                                                                           \
-    __device__ __forceinline__ f32x2 name(f32x2 a, f32x2 b, f32x2 c) { f32x2 r; asm(text : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ f32x2 w4_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x2 w4_sub(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ f32x2 w4_mul(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// ---- packed fp32 VALU helpers of this kernel (pk_add / pk_sub / pk_mul and the src0 rule: l2i_device.h).  Constants come in SGPR pairs. ----
 // ReLU-on-load without a packed fp32 max: clamp(x * 2^-60) with the instruction's clamp bit ([0, 1]) is relu(x) * 2^-60 EXACTLY for |x| <= 2^60
 // (a power-of-two scale is exact; values below 2^-66 flush to zero: an absolute error of 1e-20) — one v_pk_mul per pair instead of two v_max_f32.
 // The accumulators then carry y * 2^-60 (products of order 2^-60 .. 2^-75: far above the denormal range) and the epilogue multiplies back.
@@ -136,9 +130,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
     const size_t smp = (size_t)b * p.Cin * ((size_t)p.H * p.W);
     const unsigned uchunk_b = (unsigned)(p.CoutP / BM) * (unsigned)(UST * sizeof(float));            // bytes of one 4-channel chunk of the weight pack
     constexpr unsigned XSHIFT = (NSL - 2) * 1024u;     // [r6] the descriptor starts this far before the sample: every register offset below stays >= 0
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(p.x + smp) - XSHIFT), 0, in_bytes + XSHIFT, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (unsigned)(p.Cin / CK) * uchunk_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc((const char*)(p.x + smp) - XSHIFT, in_bytes + XSHIFT);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, (unsigned)(p.Cin / CK) * uchunk_b);
+    const __amdgpu_buffer_rsrc_t rs_null = l2i_buffer_rsrc(p.x, 0u);
     // element e = u * 256 + tid of the [18][66] plane -> byte offset in the channel plane.  Slots 0..3 of a channel go out in ONE statement with
     // immediate offsets u * 1024 (the immediate moves the LDS target AND the global address: voff carries XSHIFT - u * 1024 against a descriptor that
     // starts XSHIFT bytes early); out-of-image / past-the-plane
@@ -154,9 +148,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
         voff[u] = ok ? (unsigned)(gy * p.W + gx) * 4u + (XSHIFT - (u < NSL - 1 ? (unsigned)u * 1024u : 0u)) : OOB;
     }
     const unsigned wvoff = (unsigned)tid * 16u;        // U: the chunk image is copied linearly, 16 bytes per lane and slot
-    const unsigned lds_raw = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)rawbuf;
-    const unsigned lds_u = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)ubuf;
-    const unsigned lds_dump = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)dump;
+    const unsigned lds_raw = l2i_lds_addr(rawbuf);
+    const unsigned lds_u = l2i_lds_addr(ubuf);
+    const unsigned lds_dump = l2i_lds_addr(dump);
 
     // DMA of one chunk = 5 statements per wave: U (3 x 16 bytes per lane; lanes 0 .. 575 of 768 carry the image, the rest — slot 2 of waves 1-3 —
     // land in the dump) and one per channel of the raw tile (5 x 4 bytes per lane; wave 3's part of the last slot is past the plane: dump).
@@ -204,13 +198,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
         }
         if constexpr (SCALE) {
 #pragma unroll
-            for (int r = 0; r < 6; ++r) P[r] = w4_mul(P[r], sc);
+            for (int r = 0; r < 6; ++r) P[r] = pk_mul(P[r], sc);
         }
         const f32x2 a = w4_fmak(P[2], km4, P[4]), bq = w4_fmak(P[1], km4, P[3]);
-        const f32x2 c = w4_sub(P[4], P[2]), e = w4_sub(P[3], P[1]);
+        const f32x2 c = pk_sub(P[4], P[2]), e = pk_sub(P[3], P[1]);
         const f32x2 t0 = w4_fmak(P[0], k4, w4_fmak(P[2], km5, P[4]));
         const f32x2 t5 = w4_fmak(P[1], k4, w4_fmak(P[3], km5, P[5]));
-        P[0] = t0; P[1] = w4_add(a, bq); P[2] = w4_sub(a, bq); P[3] = w4_fmak(e, k2, c); P[4] = w4_fmak(e, km2, c); P[5] = t5;
+        P[0] = t0; P[1] = pk_add(a, bq); P[2] = pk_sub(a, bq); P[3] = w4_fmak(e, k2, c); P[4] = w4_fmak(e, km2, c); P[5] = t5;
     };
 
     f32x4 acc[36];
@@ -350,11 +344,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
             f32x2 m[6];
 #pragma unroll
             for (int r = 0; r < 6; ++r) m[r] = h ? f32x2{acc[6 * r + j][2], acc[6 * r + j][3]} : f32x2{acc[6 * r + j][0], acc[6 * r + j][1]};
-            const f32x2 pp = w4_add(m[1], m[2]), qq = w4_sub(m[1], m[2]), rr = w4_add(m[3], m[4]), ss = w4_sub(m[3], m[4]);
-            yv[0][j] = w4_add(w4_add(m[0], pp), rr);
+            const f32x2 pp = pk_add(m[1], m[2]), qq = pk_sub(m[1], m[2]), rr = pk_add(m[3], m[4]), ss = pk_sub(m[3], m[4]);
+            yv[0][j] = pk_add(pk_add(m[0], pp), rr);
             yv[1][j] = w4_fmak(ss, k2, qq);
             yv[2][j] = w4_fmak(rr, k4, pp);
-            yv[3][j] = w4_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
+            yv[3][j] = pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
         }
         float scv[2], bv[2];
 #pragma unroll
@@ -366,9 +360,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
 #pragma unroll
         for (int ry = 0; ry < 4; ++ry) {
             const f32x2* m = yv[ry];
-            const f32x2 pp = w4_add(m[1], m[2]), qq = w4_sub(m[1], m[2]), rr = w4_add(m[3], m[4]), ss = w4_sub(m[3], m[4]);
-            const f32x2 y0 = w4_add(w4_add(m[0], pp), rr), y1 = w4_fmak(ss, k2, qq), y2 = w4_fmak(rr, k4, pp);
-            const f32x2 y3 = w4_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
+            const f32x2 pp = pk_add(m[1], m[2]), qq = pk_sub(m[1], m[2]), rr = pk_add(m[3], m[4]), ss = pk_sub(m[3], m[4]);
+            const f32x2 y0 = pk_add(pk_add(m[0], pp), rr), y1 = w4_fmak(ss, k2, qq), y2 = w4_fmak(rr, k4, pp);
+            const f32x2 y3 = pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
             const int oy = oyb + ry;
             const bool pok = xok && (oy < p.OH);
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
@@ -529,9 +523,9 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     // descriptor starts XSHIFT bytes before the sample and is XSHIFT bytes longer, so that every register offset (byte + XSHIFT - 1024 u) is >= 0 — round 5
     // let the first pixels of a sample wrap below zero and relied on voffset + immediate being added modulo 2^32 before the range check (round-5 advice).
     constexpr unsigned XSHIFT = (NRS - 1) * 1024u;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)(p.x + smp) - XSHIFT), 0, in_bytes + XSHIFT, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (unsigned)(p.Cin / CK) * uchunk_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_null = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = l2i_buffer_rsrc((const char*)(p.x + smp) - XSHIFT, in_bytes + XSHIFT);
+    const __amdgpu_buffer_rsrc_t rs_w = l2i_buffer_rsrc(p.w, (unsigned)(p.Cin / CK) * uchunk_b);
+    const __amdgpu_buffer_rsrc_t rs_null = l2i_buffer_rsrc(p.x, 0u);
     constexpr unsigned OOB = 0x80000000u;
     unsigned voff[NRS];                                // group 64 u + lane of the [10][18] plane -> byte offset in the channel plane (+ XSHIFT - the immediate)
 #pragma unroll
@@ -543,9 +537,9 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         voff[u] = ok ? (unsigned)(gy * p.W + gx) * 4u + (XSHIFT - (unsigned)u * 1024u) : OOB;
     }
     const unsigned wvoff = (unsigned)lane * 16u;
-    const unsigned lds_raw = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)rawbuf;
-    const unsigned lds_u = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)ubuf;
-    const unsigned lds_dump = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)dump;
+    const unsigned lds_raw = l2i_lds_addr(rawbuf);
+    const unsigned lds_u = l2i_lds_addr(ubuf);
+    const unsigned lds_dump = l2i_lds_addr(dump);
 
     // DMA of one chunk = 2 statements per wave: U (5 x 16 bytes per lane: slots wave + 4 j of the 18 KiB image; the fifth slot of waves 2, 3 is
     // past the image: null descriptor into the dump) and the wave's channel plane of the raw tile (3 x 16 bytes per lane).
@@ -598,14 +592,14 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
         }
         if constexpr (SCALE) {
 #pragma unroll
-            for (int r = R0; r < R0 + 5; ++r) P[r] = w4_mul(P[r], sc);
+            for (int r = R0; r < R0 + 5; ++r) P[r] = pk_mul(P[r], sc);
         }
         if constexpr (H == 0) {
             const f32x2 a = w4_fmak(P[2], km4, P[4]), bq = w4_fmak(P[1], km4, P[3]);
             const f32x2 t0 = w4_fmak(P[0], k4, w4_fmak(P[2], km5, P[4]));
-            P[0] = t0; P[1] = w4_add(a, bq); P[2] = w4_sub(a, bq);
+            P[0] = t0; P[1] = pk_add(a, bq); P[2] = pk_sub(a, bq);
         } else {
-            const f32x2 c = w4_sub(P[4], P[2]), e = w4_sub(P[3], P[1]);
+            const f32x2 c = pk_sub(P[4], P[2]), e = pk_sub(P[3], P[1]);
             const f32x2 t5 = w4_fmak(P[1], k4, w4_fmak(P[3], km5, P[5]));
             P[0] = w4_fmak(e, k2, c); P[1] = w4_fmak(e, km2, c); P[2] = t5;
         }
@@ -776,11 +770,11 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
             f32x2 m[6];
 #pragma unroll
             for (int r = 0; r < 6; ++r) m[r] = h ? f32x2{M(r, j)[2], M(r, j)[3]} : f32x2{M(r, j)[0], M(r, j)[1]};
-            const f32x2 pp = w4_add(m[1], m[2]), qq = w4_sub(m[1], m[2]), rr = w4_add(m[3], m[4]), ss = w4_sub(m[3], m[4]);
-            yv[0][j] = w4_add(w4_add(m[0], pp), rr);
+            const f32x2 pp = pk_add(m[1], m[2]), qq = pk_sub(m[1], m[2]), rr = pk_add(m[3], m[4]), ss = pk_sub(m[3], m[4]);
+            yv[0][j] = pk_add(pk_add(m[0], pp), rr);
             yv[1][j] = w4_fmak(ss, k2, qq);
             yv[2][j] = w4_fmak(rr, k4, pp);
-            yv[3][j] = w4_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
+            yv[3][j] = pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
         }
         float scv[2], bv[2];
 #pragma unroll
@@ -793,9 +787,9 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
 #pragma unroll
         for (int ry = 0; ry < 4; ++ry) {
             const f32x2* m = yv[ry];
-            const f32x2 pp = w4_add(m[1], m[2]), qq = w4_sub(m[1], m[2]), rr = w4_add(m[3], m[4]), ss = w4_sub(m[3], m[4]);
-            const f32x2 y0 = w4_add(w4_add(m[0], pp), rr), y1 = w4_fmak(ss, k2, qq), y2 = w4_fmak(rr, k4, pp);
-            const f32x2 y3 = w4_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
+            const f32x2 pp = pk_add(m[1], m[2]), qq = pk_sub(m[1], m[2]), rr = pk_add(m[3], m[4]), ss = pk_sub(m[3], m[4]);
+            const f32x2 y0 = pk_add(pk_add(m[0], pp), rr), y1 = w4_fmak(ss, k2, qq), y2 = w4_fmak(rr, k4, pp);
+            const f32x2 y3 = pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
             const int oy = oyb + ry;
             const bool pok = xok && (oy < p.OH);
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
