@@ -3,6 +3,8 @@
 // acc[m][n][r] = channel m0 + 32 m + (r & 3) + 8 (r >> 2) + 4 (lane >> 5), pixel lane & 31.
 //   epi(a) = act( a*out_scale[b,co] * (out_mask > 0) + noise*noise_w + bias[co] + R * (res_mask > 0) ) * out_gain (+ y if accumulate)
 // (include/l2i.h).  vec = true: per-wave LDS transpose (8 KiB strip per wave at `smemf`) -> 16-byte global accesses.
+// Every copy of this epilogue (this header, the fp32 kernels' inline ones, any new one) is a route of tests/test_epilogue_contract_gpu.py:
+// a new copy must be added there, where it is checked term by term against the float64 model of the contract.
 #ifndef L2I_EPILOGUE_H
 #define L2I_EPILOGUE_H
 #include <hip/hip_runtime.h>

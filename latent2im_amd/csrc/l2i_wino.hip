@@ -455,6 +455,7 @@ extern "C" int l2i_conv2d_wino_f32(const l2i_conv_params* pp, void* stream) {
     if ((size_t)p.Cin * p.H * p.W * sizeof(float) >= 0xFFFFFFF0ull || (size_t)p.Cin * 16 * p.CoutP * sizeof(float) >= 0xFFFFFFF0ull)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino: one sample / the weight pack must stay below 4 GiB (32-bit buffer offsets)");
     if (p.tile_hint != 0) return l2i_set_error(L2I_E_ARG, "conv2d_wino: tile_hint must be 0 (one configuration)");
+    if (p.res_sub && !p.residual) return l2i_set_error(L2I_E_ARG, "conv2d_wino: res_sub needs residual");
     if ((p.sq_ref != nullptr) != (p.sq_out != nullptr) || (((uintptr_t)p.sq_ref) % 16) != 0) return l2i_set_error(L2I_E_ARG, "conv2d_wino: sq_ref (16-byte aligned) and sq_out go together");
     return launch_wino(p, (hipStream_t)stream);
 }

@@ -973,6 +973,7 @@ extern "C" int l2i_conv2d_wino4_f32(const l2i_conv_params* pp, void* stream) {
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino4: one sample must stay below 2 GiB, the weight pack below 4 GiB (32-bit buffer offsets)");
     if (p.tile_hint < 0 || p.tile_hint > 2) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: tile_hint must be 0 (position-split kernel), 1 (the round-4 kernel) or 2 (position-split, 64 x 16 tile on eight waves)");
     if ((p.sq_ref != nullptr) != (p.sq_out != nullptr) || (((uintptr_t)p.sq_ref) % 16) != 0) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: sq_ref (16-byte aligned) and sq_out go together");
+    if (p.res_sub && !p.residual) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: res_sub needs residual");
     if ((p.pool_out != nullptr) != (p.pool_idx != nullptr)) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: pool_out and pool_idx go together");
     if (p.pool_out && (p.tile_hint == 1 || (p.OHf % 2) != 0 || (p.OWf % 4) != 0 || p.oy_off != 0 || p.ox_off != 0 || p.OH != p.OHf || p.OW != p.OWf || (((uintptr_t)p.pool_out) % 8) != 0 ||
                        (((uintptr_t)p.pool_idx) % 2) != 0))
