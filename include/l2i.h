@@ -164,6 +164,12 @@ int l2i_conv2d_wino_f32(const l2i_conv_params* p, void* stream);
  * needs pad_x == 1 and W % 4 == 0); tile_hint 1: the round-4 kernel (16 channels per block), same arithmetic, bit-identical results;
  * tile_hint 2: the position-split kernel on 64 x 16-pixel tiles / eight waves where the map has >= 64 columns and >= 16 rows (an A/B form: slower). */
 int l2i_conv2d_wino4_f32(const l2i_conv_params* p, void* stream);
+/* Host only, no launch: the epilogue class the position-split kernel (tile_hint 0 / 2) takes for this struct.  A lean class is compiled for one exact
+ * operand set (in_scale / ReLU-on-load, out_scale, noise, bias, out_mask, residual, res_sub, res_mask, act, out_gain != 1, accumulate, pool_out,
+ * sq_ref) of the training step: 0 .. L2I_WINO4S_LEAN_CLASSES - 1; every other set takes the generic body = L2I_WINO4S_LEAN_CLASSES.  Same results
+ * bit for bit either way.  -1: p is NULL.  (The struct's shape is not validated here: l2i_conv2d_wino4_f32 does that.) */
+#define L2I_WINO4S_LEAN_CLASSES 8
+int l2i_wino4s_epilogue_class(const l2i_conv_params* p);
 
 /* ---- the 16-bit path (BASELINE config 5: "fp16 MFMA"; bf16 here: fp32's exponent range, so gradients of 1e-9 need no loss scaling) ----
  * Tensors in the channel-blocked "h8" layout [B][C/8][H][W][8] bf16 (the 8 channels of a pixel = 16 contiguous bytes = one MFMA fragment);
@@ -457,8 +463,8 @@ int l2i_face_head_f32(float* emb, double* dist, const float* feat, const float* 
 
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
- * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
-#define L2I_ABI_VERSION 8
+ * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
+#define L2I_ABI_VERSION 9
 int l2i_abi_version(void);
 int l2i_sizeof_conv_params(void);       /* sizeof(struct l2i_conv_params) of THIS build */
 

@@ -42,6 +42,7 @@ class ConvParams(ctypes.Structure):
 
 
 SQ_SLOTS = 1024          # L2I_SQ_SLOTS
+WINO4S_LEAN_CLASSES = 8   # L2I_WINO4S_LEAN_CLASSES: l2i_wino4s_epilogue_class returns this for the generic body
 
 
 class SegmvPart(ctypes.Structure):
@@ -64,6 +65,7 @@ _SIGNATURES = {
     'l2i_conv_transpose2d_bf16x3_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_wino_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_wino4_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
+    'l2i_wino4s_epilogue_class': (c_i, [ctypes.POINTER(ConvParams)]),
     'l2i_conv1x1_pair_f32': (c_i, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_h8': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv_transpose2d_h8': (c_i, [ctypes.POINTER(ConvParams), c_p]),
@@ -125,7 +127,7 @@ _F16_TWINS = frozenset(k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i
 for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
-ABI_VERSION = 8          # L2I_ABI_VERSION of include/l2i.h this binding mirrors
+ABI_VERSION = 9          # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 
 EXPORTS = tuple(_SIGNATURES)
 

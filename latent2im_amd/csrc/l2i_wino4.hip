@@ -87,6 +87,14 @@ __device__ __forceinline__ f32x2 w4_fmak_op(f32x2 a, f32x2 k, f32x2 c) {
     f32x2 r; asm("v_pk_fma_f32 %0, %1, %2, %3\n\ts_nop 1" : "=v"(r) : "v"(a), "s"(k), "v"(c)); return r;
 }
 
+// the lean epilogue classes of conv_wino4s_kernel: a * k with the constant pair k in SGPRs; (a.lo + b.lo, a.lo + b.hi) and (a.hi + b.lo, a.hi + b.hi)
+// (the half selections on src0 only); v_max_f32 by hand (the operands come out of asm statements: fmaxf would canonicalise them first)
+__device__ __forceinline__ f32x2 w4_mulk(f32x2 a, f32x2 k) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "s"(k)); return r; }
+__device__ __forceinline__ f32x2 w4_lo_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ f32x2 w4_hi_add(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float w4_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float w4_max0(float a) { float r; asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(a)); return r; }
+
 // ds_read_b64 by hand: hipcc would merge two of them into ds_read2_b64, which the LDS serves per 16 lanes on 32 banks — the patches of 16 tiles are
 // 16 bytes apart, a 2-way conflict on every access.  The matching wait is w4_lds_wait6 (the compiler does not count asm LDS reads).
 __device__ __forceinline__ f32x2 w4_lds_b64(unsigned addr, int off) {
@@ -479,13 +487,70 @@ static_assert(4 * XCH <= US * UST + 4 + RS * RAWST, "the exchange area lives in 
 static_assert(NUS * 4 >= NUSLOT && (NUS - 1) * 4 < NUSLOT, "U slots");
 }
 
+// ---- epilogue classes of conv_wino4s_kernel -------------------------------------------------------------------------------------------------
+// The operands of a launch as a bit set.  A LEAN class is one exact set (the sets the training step launches: profiles/wino4s_epilogue_classes_ab.txt):
+// its epilogue has the absent operands compiled out, packed arithmetic and its operand loads one row ahead.  Every other set takes the generic body.
+enum : unsigned {
+    W4E_IN_SCALE = 1u << 0, W4E_IN_RELU = 1u << 1, W4E_OUT_SCALE = 1u << 2, W4E_NOISE = 1u << 3, W4E_BIAS = 1u << 4, W4E_OUT_MASK = 1u << 5,
+    W4E_RESIDUAL = 1u << 6, W4E_RES_SUB = 1u << 7, W4E_RES_MASK = 1u << 8, W4E_LRELU = 1u << 9, W4E_RELU = 1u << 10, W4E_OUT_GAIN = 1u << 11,
+    W4E_ACCUM = 1u << 12, W4E_POOL = 1u << 13, W4E_SQ = 1u << 14, W4E_GENERIC = 0xffffffffu
+};
+constexpr int W4S_LEAN_CLASSES = L2I_WINO4S_LEAN_CLASSES;
+constexpr unsigned W4S_CLASS_SET[W4S_LEAN_CLASSES] = {
+    W4E_IN_SCALE | W4E_OUT_SCALE | W4E_NOISE | W4E_BIAS | W4E_LRELU,       // 0: the generator's styled convs
+    W4E_IN_RELU | W4E_BIAS,                                                // 1: VGG forward on ReLU-on-load input ...
+    W4E_IN_RELU | W4E_BIAS | W4E_POOL,                                     // 2: ... in front of a pool
+    W4E_IN_RELU | W4E_BIAS | W4E_SQ,                                       // 3: ... a ContentLoss tap
+    W4E_IN_RELU | W4E_BIAS | W4E_POOL | W4E_SQ,                            // 4: ... both
+    W4E_OUT_MASK,                                                          // 5: input gradient through a ReLU
+    W4E_OUT_MASK | W4E_RESIDUAL | W4E_RES_SUB,                             // 6: VGG input gradient at a tap: + coef * (feature - target)
+    W4E_BIAS | W4E_RELU,                                                   // 7: ResNet-50 conv2 forward
+};
+#define W4S_LEAN_CASES L2I_WINO4S_LEAN(0); L2I_WINO4S_LEAN(1); L2I_WINO4S_LEAN(2); L2I_WINO4S_LEAN(3); L2I_WINO4S_LEAN(4); L2I_WINO4S_LEAN(5); \
+                       L2I_WINO4S_LEAN(6); L2I_WINO4S_LEAN(7);
+static unsigned w4s_operand_set(const l2i_conv_params& p) {
+    return (p.in_scale ? W4E_IN_SCALE : 0u) | (p.in_mask ? W4E_IN_RELU : 0u) | (p.out_scale ? W4E_OUT_SCALE : 0u) | (p.noise ? W4E_NOISE : 0u) |
+           (p.bias ? W4E_BIAS : 0u) | (p.out_mask ? W4E_OUT_MASK : 0u) | (p.residual ? W4E_RESIDUAL : 0u) | (p.res_sub ? W4E_RES_SUB : 0u) |
+           (p.res_mask ? W4E_RES_MASK : 0u) | (p.act == L2I_ACT_LRELU ? W4E_LRELU : 0u) | (p.act == L2I_ACT_RELU ? W4E_RELU : 0u) |
+           (p.out_gain != 1.f ? W4E_OUT_GAIN : 0u) | (p.accumulate ? W4E_ACCUM : 0u) | (p.pool_out ? W4E_POOL : 0u) | (p.sq_ref ? W4E_SQ : 0u);
+}
+static bool w4s_tall(const l2i_conv_params& p) { return p.OW >= 64 && p.OH >= 16 && p.tile_hint == 2; }
+static int w4s_epilogue_class(const l2i_conv_params& p) {
+    if (w4s_tall(p)) return W4S_LEAN_CLASSES;          // the eight-wave tile is an A/B form outside the step: generic body only
+    const unsigned set = w4s_operand_set(p);
+    for (int c = 0; c < W4S_LEAN_CLASSES; ++c)
+        if (W4S_CLASS_SET[c] == set) return c;
+    return W4S_LEAN_CLASSES;                           // the generic body
+}
+
+// the pool_out / sq_ref tails of a lean class: the generic body's statements (same comparisons, same sum order)
+struct W4Ops { float4 mk, rv, sb, rm, o, rf; };        // the per-element operands of one (row, channel): out_mask, residual, res_sub, res_mask, y (accumulate), sq_ref
+__device__ __forceinline__ float4 w4_ld4(const float* q) { return *reinterpret_cast<const float4*>(q); }
+__device__ __forceinline__ float w4_f4(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+__device__ __forceinline__ float w4s_sq_term(const float4& v, const float4& rf) {
+    const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
+    return (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+}
+__device__ __forceinline__ void w4s_pool_pair(const float4& u, const float4& v, float* pool_out, unsigned char* pool_idx, size_t pidx) {
+    float b0 = u.x, b1 = u.z;
+    unsigned i0 = 0u, i1 = 0u;
+    if (u.y > b0 || u.y != u.y) { b0 = u.y; i0 = 1u; }
+    if (v.x > b0 || v.x != v.x) { b0 = v.x; i0 = 2u; }
+    if (v.y > b0 || v.y != v.y) { b0 = v.y; i0 = 3u; }
+    if (u.w > b1 || u.w != u.w) { b1 = u.w; i1 = 1u; }
+    if (v.z > b1 || v.z != v.z) { b1 = v.z; i1 = 2u; }
+    if (v.w > b1 || v.w != v.w) { b1 = v.w; i1 = 3u; }
+    *reinterpret_cast<float2*>(pool_out + pidx) = make_float2(b0, b1);
+    *reinterpret_cast<unsigned short*>(pool_idx + pidx) = (unsigned short)(i0 | (i1 << 8));
+}
+
 struct Wino4sLaunch {
     int tiles_x, tiles_y, mblocks;
     int total;
     int nchunks;
 };
 
-template <bool SCALE, bool RELU, int H, int VAR>
+template <bool SCALE, bool RELU, int H, int VAR, unsigned EM>
 __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino4sLaunch& L, float* smem) {
     using namespace w4s;
     using GE = Geo<VAR>;
@@ -761,9 +826,44 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     // ---- epilogue: lane-local inverse transform Y = A^T M A, then 16-byte row stores (lane (g, n): channels m0 + 16 H + 4 g + 0..3, tile (trow, n)) ----
     float sq = 0.f;
     const float rc = p.res_sub ? p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) : 0.f;
+    // ---- lean classes (EM = the launch's exact operand set): what the set does not hold is compiled out, what it holds is there ----
+    constexpr bool LEAN = EM != W4E_GENERIC;
+    constexpr bool E_SC = LEAN && (EM & W4E_OUT_SCALE), E_NZ = LEAN && (EM & W4E_NOISE), E_OM = LEAN && (EM & W4E_OUT_MASK);
+    constexpr bool E_RES = LEAN && (EM & W4E_RESIDUAL), E_RS = LEAN && (EM & W4E_RES_SUB), E_RM = LEAN && (EM & W4E_RES_MASK), E_LRELU = LEAN && (EM & W4E_LRELU);
+    constexpr bool E_RELU = LEAN && (EM & W4E_RELU), E_OG = LEAN && (EM & W4E_OUT_GAIN), E_ACC = LEAN && (EM & W4E_ACCUM), E_POOL = LEAN && (EM & W4E_POOL);
+    constexpr bool E_SQ = LEAN && (EM & W4E_SQ);
+    static_assert(!LEAN || (SCALE == bool(EM & W4E_IN_SCALE) && RELU == bool(EM & W4E_IN_RELU)), "a lean class names its prologue too");
+    // The values leave the inverse transform as (pixel; channel pair) register pairs and are stored as (channel; pixel pair): the first stage that is
+    // single-lane anyway (a select, the residual sum, a max) moves them over for free; without one, the last stage present runs single-lane.
+    constexpr int TR = E_OM ? 3 : E_RES ? 5 : (E_LRELU || E_RELU) ? 6 : E_OG ? 8 : 4;
+    f32x2 nzw[4][2];                                   // noise_w * the four noise rows, as pixel pairs
+    if constexpr (E_NZ) {
+        const f32x2 knw = {p.noise_w, p.noise_w};
+#pragma unroll
+        for (int ry = 0; ry < 4; ++ry) {
+            nzw[ry][0] = w4_mulk(f32x2{nz_h[ry].x, nz_h[ry].y}, knw);
+            nzw[ry][1] = w4_mulk(f32x2{nz_h[ry].z, nz_h[ry].w}, knw);
+        }
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                      // accumulator rows (2 h, 2 h + 1) = two channels as one register pair
         const int co0 = m0 + 16 * H + 4 * kq + 2 * h;
+        // lean: element offset of (row ry, channel co0 + q) = a base per channel pair + whole strides; a lane without that element reads element 0 of
+        // every operand (always there, never used) so that the loads need no branch.  Row 0's operands are requested before the column pass.
+        const bool cokq[2] = {co0 < p.Cout, co0 + 1 < p.Cout};
+        const size_t ob = ((size_t)b * p.Cout + co0) * plane_o + (size_t)(oyb + p.oy_off) * p.OWf + ox + p.ox_off;
+        auto has = [&](int ry, int q) { return xok && (oyb + ry < p.OH) && cokq[q]; };
+        auto fetch = [&](int ry, int q, W4Ops& t) {
+            const size_t i = has(ry, q) ? ob + (size_t)q * plane_o + (size_t)ry * p.OWf : (size_t)0;
+            if constexpr (E_OM) t.mk = w4_ld4(p.out_mask + i);
+            if constexpr (E_RES) t.rv = w4_ld4(p.residual + i);
+            if constexpr (E_RS) t.sb = w4_ld4(p.res_sub + i);
+            if constexpr (E_RM) t.rm = w4_ld4(p.res_mask + i);
+            if constexpr (E_ACC) t.o = w4_ld4(p.y + i);
+            if constexpr (E_SQ) t.rf = w4_ld4(p.sq_ref + i);
+        };
+        W4Ops cur[2], nxt[2];
+        if constexpr (LEAN) { fetch(0, 0, cur[0]); fetch(0, 1, cur[1]); }
         f32x2 yv[4][6];                                // A^T M: rows 0..3, columns 0..5
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
@@ -776,6 +876,7 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
             yv[2][j] = w4_fmak(rr, k4, pp);
             yv[3][j] = pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5]);
         }
+        if constexpr (!LEAN) {
         float scv[2], bv[2];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -859,8 +960,131 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
                 }
             }
         }
+        } else {
+#pragma clang fp contract(off)                                     // every value keeps the generic body's sequence of roundings: no mul + add may fuse here
+            const f32x2 scp = {scv_h[h][0], scv_h[h][1]}, bp = {bv_h[h][0], bv_h[h][1]};
+            const f32x2 kun = {W4_RELU_UNSCALE, W4_RELU_UNSCALE}, ksl = {p.act_slope, p.act_slope}, kag = {p.act_gain, p.act_gain};
+            const f32x2 kog = {p.out_gain, p.out_gain}, krc = {rc, rc};
+            const f32x2 tb = pk_add(f32x2{0.f, 0.f}, bp);          // without noise: the generic body's (0 + bias)
+            const f32x2 bb[2] = {f32x2{bp.x, bp.x}, f32x2{bp.y, bp.y}}, tbb[2] = {f32x2{tb.x, tb.x}, f32x2{tb.y, tb.y}};
+            float4 prow[2];                            // pool_out: the even row of the current window pair, per channel of the register pair
+            bool pvalid[2] = {false, false};
+#pragma unroll
+            for (int ry = 0; ry < 4; ++ry) {
+                if (ry < 3) { fetch(ry + 1, 0, nxt[0]); fetch(ry + 1, 1, nxt[1]); }
+                const f32x2* m = yv[ry];
+                const f32x2 pp = pk_add(m[1], m[2]), qq = pk_sub(m[1], m[2]), rr = pk_add(m[3], m[4]), ss = pk_sub(m[3], m[4]);
+                f32x2 Ya[4] = {pk_add(pk_add(m[0], pp), rr), w4_fmak(ss, k2, qq), w4_fmak(rr, k4, pp), pk_add(w4_fmak(ss, f32x2{8.f, 8.f}, qq), m[5])};
+                f32x2 Yb[2][2];                        // [channel][pixel pair]
+                if constexpr (RELU) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) Ya[i] = w4_mulk(Ya[i], kun);
+                }
+                if constexpr (E_SC) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) Ya[i] = pk_mul(Ya[i], scp);
+                }
+                if constexpr (E_OM) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            Yb[q][j] = f32x2{w4_f4(cur[q].mk, 2 * j) > 0.f ? Ya[2 * j][q] : 0.f, w4_f4(cur[q].mk, 2 * j + 1) > 0.f ? Ya[2 * j + 1][q] : 0.f};
+                }
+                if constexpr (TR >= 4) {               // + (noise + bias), pairs still (pixel; channel pair)
+                    f32x2 t[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) t[i] = E_NZ ? ((i & 1) ? w4_hi_add(nzw[ry][i >> 1], bp) : w4_lo_add(nzw[ry][i >> 1], bp)) : tb;
+                    if constexpr (TR == 4) {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) Yb[q][j] = f32x2{Ya[2 * j][q] + t[2 * j][q], Ya[2 * j + 1][q] + t[2 * j + 1][q]};
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) Ya[i] = pk_add(Ya[i], t[i]);
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) Yb[q][j] = pk_add(Yb[q][j], E_NZ ? pk_add(nzw[ry][j], bb[q]) : tbb[q]);
+                }
+                if constexpr (E_RES) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            f32x2 r = {w4_f4(cur[q].rv, 2 * j), w4_f4(cur[q].rv, 2 * j + 1)};
+                            if constexpr (E_RS) r = w4_mulk(pk_sub(r, f32x2{w4_f4(cur[q].sb, 2 * j), w4_f4(cur[q].sb, 2 * j + 1)}), krc);
+                            if constexpr (E_RM) r = f32x2{w4_f4(cur[q].rm, 2 * j) > 0.f ? r.x : 0.f, w4_f4(cur[q].rm, 2 * j + 1) > 0.f ? r.y : 0.f};
+                            if constexpr (TR == 5) Yb[q][j] = f32x2{Ya[2 * j][q] + r.x, Ya[2 * j + 1][q] + r.y};
+                            else Yb[q][j] = pk_add(Yb[q][j], r);
+                        }
+                }
+                if constexpr (E_LRELU) {               // max(v, slope v) * gain
+                    if constexpr (TR == 6) {
+                        f32x2 m4[4];
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) m4[i] = w4_mulk(Ya[i], ksl);
+#pragma unroll
+                        for (int q = 0; q < 2; ++q)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) Yb[q][j] = f32x2{w4_max(Ya[2 * j][q], m4[2 * j][q]), w4_max(Ya[2 * j + 1][q], m4[2 * j + 1][q])};
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 2; ++q)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) {
+                                const f32x2 sv = w4_mulk(Yb[q][j], ksl);
+                                Yb[q][j] = f32x2{w4_max(Yb[q][j].x, sv.x), w4_max(Yb[q][j].y, sv.y)};
+                            }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) Yb[q][j] = w4_mulk(Yb[q][j], kag);
+                } else if constexpr (E_RELU) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            Yb[q][j] = TR == 6 ? f32x2{w4_max0(Ya[2 * j][q]), w4_max0(Ya[2 * j + 1][q])} : f32x2{w4_max0(Yb[q][j].x), w4_max0(Yb[q][j].y)};
+                }
+                if constexpr (E_OG) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            Yb[q][j] = TR == 8 ? f32x2{Ya[2 * j][q] * p.out_gain, Ya[2 * j + 1][q] * p.out_gain} : w4_mulk(Yb[q][j], kog);
+                }
+                if constexpr (E_ACC) {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        Yb[q][0] = pk_add(Yb[q][0], f32x2{cur[q].o.x, cur[q].o.y});
+                        Yb[q][1] = pk_add(Yb[q][1], f32x2{cur[q].o.z, cur[q].o.w});
+                    }
+                }
+                const int oy = oyb + ry;
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    if (!has(ry, q)) { pvalid[q] = false; continue; }
+                    const float4 v = make_float4(Yb[q][0].x, Yb[q][0].y, Yb[q][1].x, Yb[q][1].y);
+                    const size_t oidx = ob + (size_t)q * plane_o + (size_t)ry * p.OWf;
+                    *reinterpret_cast<float4*>(p.y + oidx) = v;
+                    if constexpr (E_POOL) {
+                        if ((ry & 1) == 0) { prow[q] = v; pvalid[q] = true; }
+                        else if (pvalid[q])
+                            w4s_pool_pair(prow[q], v, p.pool_out, p.pool_idx,
+                                          (((size_t)b * p.Cout + co0 + q) * (size_t)(p.OHf >> 1) + (size_t)(oy >> 1)) * (size_t)(p.OWf >> 1) + (size_t)(ox >> 1));
+                    }
+                    if constexpr (E_SQ) sq += w4s_sq_term(v, cur[q].rf);
+                }
+                cur[0] = nxt[0]; cur[1] = nxt[1];
+            }
+        }
     }
-    if (p.sq_ref) {                                                // (kernel argument: uniform branch) one atomic per block, 1024 slots
+    if (LEAN ? E_SQ : (p.sq_ref != nullptr)) {                     // (kernel argument: uniform branch) one atomic per block, 1024 slots
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
         __syncthreads();                                           // every wave has read its partner's exchange area: the partial sums may overwrite it
@@ -874,19 +1098,19 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
     }
 }
 
-template <bool SCALE, bool RELU, int VAR = 0>
+template <bool SCALE, bool RELU, int VAR = 0, unsigned EM = W4E_GENERIC>
 __global__ __launch_bounds__(VAR == 2 ? 512 : 256, VAR == 2 ? 1 : 2) void conv_wino4s_kernel(const l2i_conv_params p, const Wino4sLaunch L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (a wave-uniform branch: the two halves run the same number of barriers)
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino4s_body<SCALE, RELU, 1, VAR>(p, L, smem);
-    else wino4s_body<SCALE, RELU, 0, VAR>(p, L, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino4s_body<SCALE, RELU, 1, VAR, EM>(p, L, smem);
+    else wino4s_body<SCALE, RELU, 0, VAR, EM>(p, L, smem);
 }
 
 static int launch_wino4s(const l2i_conv_params& p, hipStream_t st) {
     Wino4sLaunch L;
     const bool narrow = p.OW < 64;                     // maps 32 .. 63 wide: the 32 x 16-pixel tile
     // TALL (64 x 16 pixels, eight waves): only where the caller asks for it with tile_hint == 2 (the A/B: DESIGN.md section 4.0)
-    const bool tall = !narrow && p.OH >= 16 && p.tile_hint == 2;
+    const bool tall = w4s_tall(p);
     L.tiles_x = narrow ? (p.OW + 31) / 32 : (p.OW + 63) / 64;
     L.tiles_y = (narrow || tall) ? (p.OH + 15) / 16 : (p.OH + 7) / 8;
     L.mblocks = p.CoutP / w4s::BM;
@@ -905,15 +1129,26 @@ static int launch_wino4s(const l2i_conv_params& p, hipStream_t st) {
         lds = ring > xch ? ring : xch;
     }
     if (lds > (tall ? 160u : 80u) * 1024) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino4: too many input channels for the style-scale table");
-#define L2I_WINO4S_(S_, R_, V_)                                                                                                         \
+#define L2I_WINO4S_(S_, R_, V_, E_)                                                                                                     \
     do {                                                                                                                                \
-        L2I_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4s_kernel<S_, R_, V_>),                    \
+        L2I_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino4s_kernel<S_, R_, V_, E_>),                \
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (V_ == 2 ? 160 : 80) * 1024));       \
-        hipLaunchKernelGGL((conv_wino4s_kernel<S_, R_, V_>), dim3(grid), dim3(V_ == 2 ? 512 : 256), lds, st, p, L);                      \
+        hipLaunchKernelGGL((conv_wino4s_kernel<S_, R_, V_, E_>), dim3(grid), dim3(V_ == 2 ? 512 : 256), lds, st, p, L);                  \
     } while (0)
-#define L2I_WINO4S(S_, R_) do { if (narrow) L2I_WINO4S_(S_, R_, 1); else if (tall) L2I_WINO4S_(S_, R_, 2); else L2I_WINO4S_(S_, R_, 0); } while (0)
-    if (relu_in) { if (scale) L2I_WINO4S(true, true); else L2I_WINO4S(false, true); }
-    else { if (scale) L2I_WINO4S(true, false); else L2I_WINO4S(false, false); }
+#define L2I_WINO4S(S_, R_, E_) do { if (narrow) L2I_WINO4S_(S_, R_, 1, E_); else if (tall) L2I_WINO4S_(S_, R_, 2, E_); else L2I_WINO4S_(S_, R_, 0, E_); } while (0)
+    // a lean class is one exact operand set, its prologue (style scale / ReLU-on-load) included; everything else takes the generic body
+#define L2I_WINO4S_LEAN(C_)                                                                                                             \
+    case C_:                                                                                                                            \
+        if (narrow) L2I_WINO4S_(bool(W4S_CLASS_SET[C_] & W4E_IN_SCALE), bool(W4S_CLASS_SET[C_] & W4E_IN_RELU), 1, W4S_CLASS_SET[C_]);     \
+        else L2I_WINO4S_(bool(W4S_CLASS_SET[C_] & W4E_IN_SCALE), bool(W4S_CLASS_SET[C_] & W4E_IN_RELU), 0, W4S_CLASS_SET[C_]);            \
+        break
+    switch (w4s_epilogue_class(p)) {
+        W4S_LEAN_CASES
+        default:
+            if (relu_in) { if (scale) L2I_WINO4S(true, true, W4E_GENERIC); else L2I_WINO4S(false, true, W4E_GENERIC); }
+            else { if (scale) L2I_WINO4S(true, false, W4E_GENERIC); else L2I_WINO4S(false, false, W4E_GENERIC); }
+    }
+#undef L2I_WINO4S_LEAN
 #undef L2I_WINO4S
 #undef L2I_WINO4S_
     L2I_CHECK_LAUNCH();
@@ -950,6 +1185,8 @@ static int launch_wino4(const l2i_conv_params& p, hipStream_t st) {
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }
+
+extern "C" int l2i_wino4s_epilogue_class(const l2i_conv_params* pp) { return pp ? w4s_epilogue_class(*pp) : -1; }
 
 extern "C" int l2i_conv2d_wino4_f32(const l2i_conv_params* pp, void* stream) {
     if (!pp) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: null params");
