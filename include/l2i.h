@@ -221,7 +221,11 @@ int l2i_conv_img_h8(const l2i_conv_params* p, void* stream);
  * ToRGB (x h8 -> rgb fp32 [B,3,HW]); the fused activation backward of a styled conv (dz h8; gin h8; grgb fp32; reductions fp32, zeroed by the caller);
  * out[b,c] += sum_p a * b; MaxPool2d forward (idx: [planes][OH][OW][8] bytes; relu = 1: y = max(pool, 0)) and backward (optionally + coef *
  *   coef_dev[0] * (b - a): the ContentLoss term of the pooled tap); the ContentLoss difference; y[2oy, 2ox] += c[oy, ox]; and the per-sample
- *   weight planes of a modulated conv: planes[b] = bf16(w32 * s[b, input channel]) with w32 = the fp32 weights in plane order. */
+ *   weight planes of a modulated conv: planes[b] = bf16(w32 * s[b, input channel]) with w32 = the fp32 weights in plane order.
+ * Operand sets: the same as the fp32 twins (l2i_torgb_fwd_f32, l2i_sg2_act_bwd_f32 below: which operands may be NULL, which pairs go together,
+ * what is refused with L2I_E_ARG).  What the layout forces on top: C % 8 == 0 (and C <= 4096 for ToRGB, whose weights sit in LDS), any HW >= 1
+ * (a pixel slot is one 16-byte access: no HW % 4 rule), h8 maps on 16-byte boundaries (every slot of a tensor the allocator returned is); the
+ * fp32 operands (grgb, noise, bias, wmod, the sums) are read as scalars and need only their natural 4-byte alignment. */
 int l2i_cast_f32_to_h8(void* y, const float* x, int B, int C, int Cpad, int64_t HW, void* stream);
 int l2i_cast_h8_to_f32(float* y, const void* x, int B, int C, int Cpad, int64_t HW, void* stream);
 int l2i_upfirdn2d_h8(void* y, const void* x, const float* k, int64_t planes, int channels, int in_h, int in_w, int kh, int kw, int up, int down,
@@ -313,7 +317,9 @@ int l2i_upfirdn2d_f16(void* y, const void* x, const void* k, int64_t major, int 
                       int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1, void* stream);
 
 /* ToRGB 1x1 modulated conv without demodulation (networks.py:346-351):
- *   rgb[b,o,p] = sum_c x[b,c,p] * wmod[b,o,c] + bias[o],  wmod = scale*W[o,c]*s[b,c] prepared by the caller [B,3,C] */
+ *   rgb[b,o,p] = sum_c x[b,c,p] * wmod[b,o,c] + bias[o],  wmod = scale*W[o,c]*s[b,c] prepared by the caller [B,3,C]
+ * bias may be NULL (= zeros), in the h8 twin too.  HW % 4 == 0, and rgb / x on 16-byte boundaries (they are accessed as float4): anything else
+ * returns L2I_E_ARG before a launch. */
 int l2i_torgb_fwd_f32(float* rgb, const float* x, const float* wmod, const float* bias, int B, int C, int64_t HW,
                       void* stream);
 
@@ -326,16 +332,25 @@ int l2i_torgb_fwd_f32(float* rgb, const float* x, const float* wmod, const float
  *   [r5] red_gin_y[b,c] += sum_p gin*y  (NULL: not formed) — y is the INPUT of the next layer and gin the gradient w.r.t. that layer's modulated input,
  *   so this is the next layer's style gradient d s (networks.py:234-235: x * s), formed while both maps pass through registers instead of by a
  *   l2i_dot_reduce pass that reads them again.
- * Reduction buffers must be zeroed by the caller. */
+ * Reduction buffers must be zeroed by the caller (the kernel adds to them).
+ * Operand sets, the same for this entry and l2i_sg2_act_bwd_h8:
+ *   gin and / or grgb must be given; gin_scale NULL = 1; grgb and wmod_rgb go together (either without the other is refused, not ignored);
+ *   bias / noise NULL = zeros; red_dz_z, red_x_grgb, red_gin_y may each be NULL (that sum is not formed); red_x_grgb without grgb and red_gin_y
+ *   without gin are not touched; gain and slope must be non-zero (zpre divides by them).
+ * Here HW % 4 == 0 and dz, y, gin, grgb, noise on 16-byte boundaries (accessed as float4; a view that starts one float into a buffer is refused).
+ * Every violation returns L2I_E_ARG before a launch. */
 int l2i_sg2_act_bwd_f32(float* dz, const float* gin, const float* gin_scale, const float* grgb, const float* wmod_rgb,
                         const float* y, const float* bias, const float* noise, float noise_w, float slope, float gain,
                         float* red_dz_z, float* red_x_grgb, float* red_gin_y, int B, int C, int64_t HW, void* stream);
 
-/* out[r] (+)= sum_p a[r,p] * (b ? b[r,p] : 1), r < rows (rows = B*C).  `out` must be zeroed by the caller. */
+/* out[r] (+)= sum_p a[r,p] * (b ? b[r,p] : 1), r < rows (rows = B*C).  `out` must be zeroed by the caller.  No alignment rule: a row whose
+ * base is not on a 16-byte boundary, or cols % 4 != 0, is read with scalar loads. */
 int l2i_dot_reduce_f32(float* out, const float* a, const float* b, int64_t rows, int64_t cols, void* stream);
 
 /* MaxPool2d(k, s, pad) on [N, H, W] planes; idx holds the window-local argmax (first maximum in row-major order, like
- * ATen) so that the backward is exact under ties. */
+ * ATen; a NaN in the window is the result and its position the index) so that the backward is exact under ties.  k <= 15.  No alignment
+ * or shape rule: the 16-byte kernels of (k, s, pad) = (2, 2, 0) and (3, 2, 1) are taken where W == 2 OW, OW % 4 == 0 (forward) / W % 4 == 0
+ * (backward) and the pointers allow, odd H included for (3, 2, 1); every other call takes the scalar kernels. */
 int l2i_maxpool2d_fwd_f32(float* y, uint8_t* idx, const float* x, int64_t planes, int H, int W, int k, int s, int pad,
                           int OH, int OW, void* stream);
 int l2i_maxpool2d_bwd_f32(float* gx, const float* gy, const uint8_t* idx, int64_t planes, int H, int W, int k, int s,

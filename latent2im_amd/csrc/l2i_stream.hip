@@ -566,6 +566,8 @@ __global__ __launch_bounds__(256) void torgb_fwd_kernel(float* __restrict__ rgb,
 extern "C" int l2i_torgb_fwd_f32(float* rgb, const float* x, const float* wmod, const float* bias, int B, int C, int64_t HW, void* stream) {
     if (!rgb || !x || !wmod) return l2i_set_error(L2I_E_ARG, "torgb_fwd: null tensor");
     if (B <= 0 || C <= 0 || HW <= 0 || (HW % 4) != 0) return l2i_set_error(L2I_E_ARG, "torgb_fwd: HW must be a positive multiple of 4");
+    // the kernel reads x and writes rgb as float4 (HW % 4 == 0 keeps every row on the base's alignment); wmod / bias are read as scalars
+    if (((uintptr_t)rgb | (uintptr_t)x) % 16) return l2i_set_error(L2I_E_ARG, "torgb_fwd: rgb and x must be 16-byte aligned");
     int bpb = (int)((HW / 4 + 255) / 256);
     const int cap = (256 * 8 + B - 1) / B;
     if (bpb > cap) bpb = cap;
@@ -654,9 +656,12 @@ extern "C" int l2i_sg2_act_bwd_f32(float* dz, const float* gin, const float* gin
                                    float* red_dz_z, float* red_x_grgb, float* red_gin_y, int B, int C, int64_t HW, void* stream) {
     if (!dz || !y) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: null tensor");
     if (!gin && !grgb) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: need gin and/or grgb");
-    if (grgb && !wmod_rgb) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: grgb needs wmod_rgb");
+    if ((grgb != nullptr) != (wmod_rgb != nullptr)) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: grgb and wmod_rgb go together");
     if (B <= 0 || C <= 0 || HW <= 0 || (HW % 4) != 0) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: HW must be a positive multiple of 4");
     if (gain == 0.f || slope == 0.f) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: gain and slope must be non-zero");
+    // every map is walked as float4 (HW % 4 == 0 keeps every row on the base's alignment); the per-channel vectors and the sums are scalars
+    if (((uintptr_t)dz | (uintptr_t)y | (uintptr_t)gin | (uintptr_t)grgb | (uintptr_t)noise) % 16)
+        return l2i_set_error(L2I_E_ARG, "sg2_act_bwd: dz, y, gin, grgb and noise must be 16-byte aligned");
     ActBwdParams p;
     p.dz = dz; p.gin = gin; p.gin_scale = gin_scale; p.grgb = grgb; p.wmod_rgb = wmod_rgb; p.y = y; p.bias = bias; p.noise = noise;
     p.noise_w = noise_w; p.slope = slope; p.gain = gain; p.red_dz_z = red_dz_z; p.red_x_grgb = red_x_grgb; p.red_gin_y = red_gin_y; p.B = B; p.C = C; p.HW = HW;

@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void torgb_fwd_h8_kernel(float* __restrict__ r
     const float4* wl4 = reinterpret_cast<const float4*>(wl);
     const int C4 = C / 4;
     for (long long pix = (long long)blk * 256 + threadIdx.x; pix < HW; pix += (long long)blocks_per_sample * 256) {
-        float a0 = bias[0], a1 = bias[1], a2 = bias[2];
+        float a0 = bias ? bias[0] : 0.f, a1 = bias ? bias[1] : 0.f, a2 = bias ? bias[2] : 0.f;
         const u32x4* xp = x + (size_t)b * G8 * HW + pix;
         int g = 0;
         for (; g + 4 <= G8; g += 4) {
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(256) void torgb_fwd_h8_kernel(float* __restrict__ r
     }
 }
 extern "C" int H8_NAME(l2i_torgb_fwd_h8)(float* rgb, const void* x, const float* wmod, const float* bias, int B, int C, int64_t HW, void* stream) {
-    if (!rgb || !x || !wmod || !bias || B <= 0 || C <= 0 || (C % 8) != 0 || C > 4096 || HW <= 0) return l2i_set_error(L2I_E_ARG, "torgb_fwd_h8: bad arguments");
+    if (!rgb || !x || !wmod || B <= 0 || C <= 0 || (C % 8) != 0 || C > 4096 || HW <= 0) return l2i_set_error(L2I_E_ARG, "torgb_fwd_h8: bad arguments");
     int bps = (int)((HW + 255) / 256);
     if (bps > 512) bps = 512;
     hipLaunchKernelGGL(torgb_fwd_h8_kernel, dim3((unsigned)(B * bps)), dim3(256), (size_t)3 * C * sizeof(float), (hipStream_t)stream, rgb, (const u32x4*)x, wmod, bias, C, (long long)HW, bps);
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256) void sg2_act_bwd_h8_kernel(u32x4* __restrict__
     __syncthreads();
     if (threadIdx.x < 8) {
         const int e = threadIdx.x;
-        atomicAdd(red_dz_z + (size_t)b * C + 8 * g + e, part[0][e] + part[1][e] + part[2][e] + part[3][e]);
+        if (red_dz_z) atomicAdd(red_dz_z + (size_t)b * C + 8 * g + e, part[0][e] + part[1][e] + part[2][e] + part[3][e]);
     } else if (threadIdx.x < 32 && red_x_grgb) {
         const int i = threadIdx.x;                              // 8 + 3 e + o
         atomicAdd(red_x_grgb + ((size_t)b * C + 8 * g) * 3 + (i - 8), part[0][i] + part[1][i] + part[2][i] + part[3][i]);
@@ -606,7 +606,9 @@ __global__ __launch_bounds__(256) void sg2_act_bwd_h8_kernel(u32x4* __restrict__
 }
 extern "C" int H8_NAME(l2i_sg2_act_bwd_h8)(void* dz, const void* gin, const float* gin_scale, const float* grgb, const float* wmod_rgb, const void* y, const float* bias,
                                   const float* noise, float noise_w, float slope, float gain, float* red_dz_z, float* red_x_grgb, float* red_gin_y, int B, int C, int64_t HW, void* stream) {
-    if (!dz || !y || !red_dz_z || B <= 0 || C <= 0 || (C % 8) != 0 || HW <= 0) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd_h8: bad arguments");
+    if (!dz || !y || B <= 0 || C <= 0 || (C % 8) != 0 || HW <= 0) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd_h8: bad arguments");
+    if (!gin && !grgb) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd_h8: need gin and/or grgb");
+    if (gain == 0.f || slope == 0.f) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd_h8: gain and slope must be non-zero");
     if ((grgb != nullptr) != (wmod_rgb != nullptr)) return l2i_set_error(L2I_E_ARG, "sg2_act_bwd_h8: grgb and wmod_rgb go together");
     const int strips = h8_strips(B * (C / 8), HW);
     hipLaunchKernelGGL(sg2_act_bwd_h8_kernel, dim3((unsigned)(B * (C / 8) * strips)), dim3(256), 0, (hipStream_t)stream, (u32x4*)dz, (const u32x4*)gin, gin_scale, grgb, wmod_rgb,

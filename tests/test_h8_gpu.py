@@ -262,40 +262,51 @@ def test_h8_upfirdn2d_all_path_geometries():
         close16(conv.from_h8(y2, 16), ref2, 'upfirdn epilogue + mask + addend')
 
 
-def test_h8_torgb_act_bwd_reductions_sqdiff():
+def test_h8_torgb_act_bwd_reductions_sqdiff(elem):
+    """The Python wrappers of the h8 streaming kernels for both element types: what they allocate, pass (None as NULL) and return, each call held to
+    the float64 model of tests/stream_ref.py at that module's bounds (half an ulp of the element type for a 16-bit output, not 2e-3 of the largest
+    value).  The kernels behind them are walked operand by operand and launch path by launch path by tests/test_stream_contract_gpu.py."""
     from latent2im_amd import kernels16 as K16
+    from tests import stream_ref as sr
     rs = np.random.RandomState(2)
     B, C, H = 2, 24, 20
+    rnd, n_lane = sr.rnd_for(elem), sr.h8_red_geom(B * C // 8, H * H)['n_lane']
+
+    def inside(got, want_m, k=None, n_lane=None, h8=False):
+        want, M = want_m
+        got = conv.from_h8(got, C) if h8 else got
+        assert tuple(got.shape) == tuple(want.shape)
+        err, bound, ratio = sr.worst(got, want, sr.bound_red(M, n_lane) if n_lane else (sr.bound16(want, M, k, elem) if h8 else sr.bound_elem(M, k)))
+        assert ratio <= 1.0, (err, bound)
+
     x, wm, bias = T(rs.randn(B, C, H, H)), T(rs.randn(B, 3, C)), T(rs.randn(3))
     g = lambda t: t.to(DEV)
     H8 = lambda t: conv.to_h8(g(t))
     rgb = K16.torgb_fwd(H8(x), g(wm), g(bias))
-    ref = torch.einsum('bchw,boc->bohw', rb(x).double(), wm.double()) + bias.double()[None, :, None, None]
-    assert float((rgb.double().cpu() - ref).abs().max()) < 1e-4 * float(ref.abs().max())
+    inside(rgb, sr.torgb_fwd(x, wm, bias, rnd=rnd)['rgb'], k=sr.k_torgb(C))
     y, gin, gs, grgb = T(rs.randn(B, C, H, H)), T(rs.randn(B, C, H, H)), T(rs.rand(B, C) + 0.5), T(rs.randn(B, 3, H, H))
     cb, nz = T(rs.randn(C)), T(rs.randn(B, 1, H, H))
     red, red_rgb, red_q = torch.zeros(B, C, device=DEV), torch.zeros(B, C, 3, device=DEV), torch.zeros(B * C, device=DEV)
     dz = K16.sg2_act_bwd(H8(y), H8(gin), g(gs), g(grgb), g(wm), g(cb), g(nz), 0.3, 0.2, 2 ** 0.5, red, red_rgb, red_q=red_q)
-    yb, gb = rb(y).double(), rb(gin).double()
-    # [r5] red_gin_y: the next layer's style gradient sum_p gin * y (what l2i_dot_reduce_h8 formed in a separate pass)
-    assert float((red_q.view(B, C).double().cpu() - (gb * yb).sum((2, 3))).abs().max()) < 1e-4 * float((gb * yb).abs().sum((2, 3)).max())
-    gg = gb * gs.double()[:, :, None, None] + torch.einsum('bohw,boc->bchw', grgb.double(), wm.double())
-    dz_ref = gg * torch.where(yb > 0, torch.tensor(2 ** 0.5, dtype=torch.float64), torch.tensor(0.2 * 2 ** 0.5, dtype=torch.float64))
-    zpre = torch.where(yb > 0, yb / 2 ** 0.5, yb / (0.2 * 2 ** 0.5)) - cb.double()[None, :, None, None] - 0.3 * nz.double()
-    close16(conv.from_h8(dz, C), dz_ref, 'dz')
-    assert float((red.double().cpu() - (dz_ref * zpre).sum((2, 3))).abs().max()) < 1e-4 * float((dz_ref * zpre).abs().sum((2, 3)).max())
-    want = torch.einsum('bchw,bohw->bco', yb, grgb.double())
-    assert float((red_rgb.double().cpu() - want).abs().max()) < 1e-4 * float(torch.einsum('bchw,bohw->bco', yb.abs(), grgb.double().abs()).max())
-    # without the ToRGB branch / without an incoming gradient
+    assert dz.shape == (B, C // 8, H, H, 8) and dz.dtype == conv.h8_dtype()
+    m = sr.sg2_act_bwd(y, gin, gs, grgb, wm, cb, nz, 0.3, 0.2, 2 ** 0.5, rnd=rnd)
+    inside(dz, m['dz'], k=sr.K_OPS['dz'], h8=True)
+    inside(red, m['red_dz_z'], n_lane=n_lane)
+    inside(red_rgb, m['red_x_grgb'], n_lane=n_lane)
+    inside(red_q.view(B, C), m['red_gin_y'], n_lane=n_lane)          # [r5] the next layer's style gradient sum_p gin * y
+    # without the ToRGB branch and without noise: None reaches the library as NULL
     red2 = torch.zeros(B, C, device=DEV)
     dz2 = K16.sg2_act_bwd(H8(y), H8(gin), g(gs), None, None, g(cb), None, 0.0, 0.2, 2 ** 0.5, red2, None)
-    close16(conv.from_h8(dz2, C), gb * gs.double()[:, :, None, None] * torch.where(yb > 0, 2 ** 0.5, 0.2 * 2 ** 0.5), 'dz without rgb')
-    d = K16.dot_reduce(H8(x), H8(y))
-    want = (rb(x).double() * yb).sum((2, 3))
-    assert float((d.double().cpu() - want).abs().max()) < 1e-4 * float((rb(x).double() * yb).abs().sum((2, 3)).max())
+    m2 = sr.sg2_act_bwd(y, gin, gs, None, None, cb, None, 0.0, 0.2, 2 ** 0.5, rnd=rnd)
+    inside(dz2, m2['dz'], k=sr.K_OPS['dz'], h8=True)
+    inside(red2, m2['red_dz_z'], n_lane=n_lane)
+    inside(K16.dot_reduce(H8(x), H8(y)), sr.dot_reduce(x, y, rnd=rnd)['out'], n_lane=n_lane)
     s, gr = K16.sqdiff(H8(x), H8(y), coef=0.25, want_grad=True)
-    assert abs(float(s) - float(((yb - rb(x).double()) ** 2).sum())) < 1e-4 * float(s)
-    close16(conv.from_h8(gr, C), 0.25 * (yb - rb(x).double()), 'sqdiff grad')
+    m = sr.sqdiff(x, y, 0.25, rnd=rnd)
+    slots = x.numel() // 8
+    inside(s, m['sum'], n_lane=8 * sr.cdiv(slots, sr.grid_for(slots, 256, 256 * 8) * 256))
+    assert gr.shape == dz.shape and gr.dtype == conv.h8_dtype()
+    inside(gr, m['grad'], k=sr.K_OPS['sqdiff_grad'], h8=True)
 
 
 @pytest.mark.parametrize('k,s,pad,h,w', [(3, 2, 1, 16, 16), (2, 2, 0, 16, 24), (3, 2, 1, 15, 21), (2, 2, 0, 40, 8), (3, 2, 1, 9, 72)])

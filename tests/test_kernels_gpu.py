@@ -545,31 +545,55 @@ def test_upfirdn2d_fused_epilogue():
         close(y, sg2.upfirdn2d(x, k, up=2, pad=(2, 1)) + add, 1e-5, 1e-6)
 
 
+def inside(got, want_m, k=None, n_lane=None):
+    """``got`` is inside the bound tests/stream_ref.py derives for it: 2^-23 k M for an elementwise output, 2^-23 (n_lane + 16) M for a sum."""
+    from tests import stream_ref as sr
+    want, M = want_m
+    assert tuple(got.shape) == tuple(want.shape)
+    err, bound, ratio = sr.worst(got, want, sr.bound_red(M, n_lane) if n_lane else sr.bound_elem(M, k))
+    assert ratio <= 1.0, (err, bound)
+
+
 def test_torgb_and_act_bwd_and_reductions():
+    """The Python wrappers of the streaming kernels: what they allocate, default (slope 0.2, gain sqrt 2, NULL for None) and return, each call held
+    to the float64 model of tests/stream_ref.py at that module's bounds.  The kernels behind them are walked operand by operand and launch path by
+    launch path by tests/test_stream_contract_gpu.py, which calls the library with its own guarded buffers."""
+    from tests import stream_ref as sr
     rs = np.random.RandomState(2)
     B, C, H = 2, 24, 12
+    n_lane = sr.rows_geom_f32(B * C, H * H)['n_lane']
     x, wm, bias = T(rs.randn(B, C, H, H)), T(rs.randn(B, 3, C)), T(rs.randn(3))
     rgb = kernels.torgb_fwd(x.to(DEV), wm.to(DEV), bias.to(DEV))
-    close(rgb, torch.einsum('bchw,boc->bohw', x, wm) + bias[None, :, None, None], 1e-4, 1e-5)
-    # fused backward pass
+    inside(rgb, sr.torgb_fwd(x, wm, bias)['rgb'], k=sr.k_torgb(C))
     y, gin, gs, grgb = T(rs.randn(B, C, H, H)), T(rs.randn(B, C, H, H)), T(rs.rand(B, C) + 0.5), T(rs.randn(B, 3, H, H))
     cb, nz = T(rs.randn(C)), T(rs.randn(B, 1, H, H))
     red_q = torch.zeros(B * C, device=DEV)
     dz, red, red_rgb = kernels.sg2_act_bwd(y.to(DEV), gin.to(DEV), gs.to(DEV), grgb.to(DEV), wm.to(DEV), cb.to(DEV), nz.to(DEV), 0.3, red_q=red_q)
-    close(red_q.view(B, C), (gin * y).sum((2, 3)), 1e-4, 1e-3)          # [r5] red_gin_y: the next layer's style gradient, formed in the same pass
-    g = gin * gs[:, :, None, None] + torch.einsum('bohw,boc->bchw', grgb, wm)
-    dz_ref = g * torch.where(y > 0, torch.tensor(2 ** 0.5), torch.tensor(0.2 * 2 ** 0.5))
-    zpre = torch.where(y > 0, y / 2 ** 0.5, y / (0.2 * 2 ** 0.5)) - cb[None, :, None, None] - 0.3 * nz
-    close(dz, dz_ref, 1e-5, 1e-5)
-    close(red, (dz_ref * zpre).sum((2, 3)), 1e-4, 1e-3)
-    close(red_rgb, torch.einsum('bchw,bohw->bco', y, grgb), 1e-4, 1e-3)
-    close(kernels.dot_reduce(x.to(DEV), y.to(DEV)), (x * y).sum((2, 3)), 1e-4, 1e-3)
-    close(kernels.dot_reduce(x.to(DEV)), x.sum((2, 3)), 1e-4, 1e-3)
+    m = sr.sg2_act_bwd(y, gin, gs, grgb, wm, cb, nz, 0.3)                          # the wrapper's defaults are the model's: slope 0.2, gain sqrt 2
+    inside(dz, m['dz'], k=sr.K_OPS['dz'])
+    inside(red, m['red_dz_z'], n_lane=n_lane)
+    inside(red_rgb, m['red_x_grgb'], n_lane=n_lane)
+    inside(red_q.view(B, C), m['red_gin_y'], n_lane=n_lane)                        # [r5] the next layer's style gradient, formed in the same pass
+    # the reductions the wrapper allocates are zeroed; without want_rgb_red (or without grgb) no ToRGB sum is formed or returned
+    dz2, red2, none = kernels.sg2_act_bwd(y.to(DEV), gin.to(DEV), gs.to(DEV), grgb.to(DEV), wm.to(DEV), cb.to(DEV), nz.to(DEV), 0.3, want_rgb_red=False)
+    assert none is None and torch.equal(dz2, dz) and torch.equal(red2, red)
+    # every optional operand left out reaches the library as NULL
+    dz3, red3, none = kernels.sg2_act_bwd(y.to(DEV), gin.to(DEV))
+    m3 = sr.sg2_act_bwd(y, gin)
+    assert none is None
+    inside(dz3, m3['dz'], k=sr.K_OPS['dz'])
+    inside(red3, m3['red_dz_z'], n_lane=n_lane)
+    inside(kernels.dot_reduce(x.to(DEV), y.to(DEV)), sr.dot_reduce(x, y)['out'], n_lane=n_lane)
+    inside(kernels.dot_reduce(x.to(DEV).view(B * C, -1)).view(B, C), sr.dot_reduce(x)['out'], n_lane=n_lane)
     s, gr = kernels.sqdiff(x.to(DEV), y.to(DEV), coef=0.25, want_grad=True)
-    close(s, ((y - x) ** 2).sum().reshape(1), 1e-4, 1e-3)
-    close(gr, 0.25 * (y - x), 1e-6, 1e-6)
+    m = sr.sqdiff(x, y, 0.25)
+    inside(s, m['sum'], n_lane=sr.cdiv(x.numel(), sr.grid_for(x.numel(), 256 * 8) * 256))
+    inside(gr, m['grad'], k=sr.K_OPS['sqdiff_grad'])
+    s2, gr2 = kernels.sqdiff(x.to(DEV), y.to(DEV), want_sum=False)
+    assert s2 is None and gr2 is None
     close(kernels.relu_mask(x.to(DEV), y.to(DEV)), x * (y > 0), 0, 0)
-    close(kernels.axpby(x.to(DEV), y.to(DEV), 0.5, -2.0), 0.5 * x - 2 * y, 1e-6, 1e-6)
+    inside(kernels.axpby(x.to(DEV), y.to(DEV), 0.5, -2.0), sr.axpby(x, y, 0.5, -2.0)['y'], k=sr.K_OPS['axpby'])
+    inside(kernels.axpby(x.to(DEV), alpha=0.5), sr.axpby(x, None, 0.5)['y'], k=sr.K_OPS['axpby'])
 
 
 @pytest.mark.parametrize('k,s,pad,h', [(3, 2, 1, 16), (2, 2, 0, 16), (3, 2, 1, 15), (3, 2, 1, 72), (2, 2, 0, 40), (3, 2, 1, 8), (2, 2, 0, 6)])      # W = 2 OW with OW % 4 == 0: the vectorised kernels
