@@ -476,10 +476,28 @@ int l2i_face_resize_f32(float* y, const float* x, int64_t planes, int H, int W, 
 int l2i_face_head_f32(float* emb, double* dist, const float* feat, const float* w_t, const float* bias, int B, int C, int HW, int E, int npairs,
                       void* stream);
 
+/* [ABI 10] The Gram-matrix term of BP.py's inversion loss and its gradient (csrc/l2i_gram.hip; BP.py:68-73, :173-184).
+ * l2i_gram_loss_f32: c [B, C, HW] is a tap's PRE-ReLU conv output.  G[b] = relu(c[b]) relu(c[b])^T / (C HW) -> G [B, C, C] (the ReLU is applied on
+ *   load; only tile pairs i <= j are contracted, on v_mfma_f32_32x32x2_f32, and the lower triangle is the mirror of the upper one, so G is
+ *   symmetric to the bit).  Gt [B, C, C] given: also D[b] = G[b] - Gt[b] -> D [B, C, C] and loss[b] += C^2 * sum(D[b]^2) (loss [B] is
+ *   accumulated into: one call per tap).  Gt NULL: only G is written (D, loss may be NULL): the target image's Grams, once per image.
+ *   HW is cut into `nslices` slices of whole 256-pixel chunks (1 <= nslices <= ceil(HW / 256)), one block per (slice, tile pair, sample); the
+ *   partial tiles go to ws and are added in slice order by a second pass that also forms D and the loss: no floating-point atomics, equal inputs
+ *   and equal nslices give equal bits.  ws: B * P * (1024 * nslices + 1) floats of scratch, P = (C / 32)(C / 32 + 1) / 2.
+ * l2i_gram_bwd_f32: g[b] (+)= coef * scale[b * scale_stride] * (c[b] > 0) * (D[b] relu(c[b])), g [B, C, HW]; D [B, C, C] must be symmetric (it is read as its own
+ *   K-major form).  For the loss above coef = 4 C / HW.  scale: optional device tensor (the upstream gradient: no host synchronisation), one
+ *   element for every sample (scale_stride 0) or one per sample (scale_stride 1: a [B] loss takes its whole batch in one launch);
+ *   accumulate != 0 adds into g (the trunk gradient arriving from the deeper taps), else g is overwritten.
+ * Both: C % 32 == 0, C <= 512, any HW >= 1 with C * HW * 4 bytes < 4 GiB, any B; other shapes return L2I_E_UNSUPPORTED.  HW % 4 == 0 with a
+ * 16-byte aligned c takes the LDS-DMA path, anything else a scalar-load path of the same arithmetic. */
+int l2i_gram_loss_f32(float* G, float* D, float* loss, const float* c, const float* Gt, float* ws, int B, int C, int HW, int nslices, void* stream);
+int l2i_gram_bwd_f32(float* g, const float* c, const float* D, const float* scale, float coef, int B, int C, int HW, int accumulate, int scale_stride,
+                     void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
- * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
-#define L2I_ABI_VERSION 9
+ * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
+#define L2I_ABI_VERSION 10
 int l2i_abi_version(void);
 int l2i_sizeof_conv_params(void);       /* sizeof(struct l2i_conv_params) of THIS build */
 

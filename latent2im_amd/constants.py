@@ -16,6 +16,8 @@ reg_json = None
 reg_path = '/path/003_dict.model'
 g_path = '/path/550000.pt'
 vgg_path = ''
+# BP.py's VGG-16 (torchvision vgg16 state dict: features.N.weight / .bias; the reference downloads it)
+vgg16_path = ''
 # eval.py's face network (facenet_pytorch InceptionResnetV1; the reference downloads its vggface2 weights): that plain state_dict file.  eval
 # --identity auto runs the identity half only when it exists; --facenet_ckpt overrides it
 facenet_path = ''

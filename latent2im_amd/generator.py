@@ -229,6 +229,10 @@ class Generator:
             x = fused_leaky_relu(torch.mm(x, wt), b)
         return x
 
+    def mean_latent(self, n):
+        """The mean of ``n`` mapped N(0, 1) draws, [1, 512] (networks.py:449-455): where BP.py starts its W+ from."""
+        return self.style(torch.randn(n, self.style_dim, device=self.device)).mean(0, keepdim=True)
+
     # -- synthesis -----------------------------------------------------------------------------------------------
     def synthesis(self, latent, noise=None):
         """latent [B, n_latent, 512] -> image [B,3,size,size].  ``noise``: list of [B,1,r,r] maps, or None: fresh

@@ -137,6 +137,57 @@ def sqdiff(a, b, coef=0.0, want_grad=False, coef_dev=None, want_sum=True):
     return s, g
 
 
+def gram_slices(B, C, HW):
+    """How many HW slices l2i_gram_loss_f32 is launched with: whole 256-pixel chunks, two chunks a slice where the map has them, and no
+    more slices than fill the chip about three times over with B * (tile pairs) blocks each.  A function of the shape alone: the Gram of a
+    target and of an image of the same shape are summed in the same order."""
+    t = C // 32
+    chunks = -(-HW // 256)
+    n = max(1, min(chunks, 768 // max(1, B * t * (t + 1) // 2), max(1, chunks // 2)))
+    sl = -(-(-(-HW // n)) // 256) * 256
+    return -(-HW // sl)
+
+
+def gram_loss(c, target=None, loss=None):
+    """l2i_gram_loss_f32: c [B, C, H, W] (or [B, C, HW]), a tap's pre-ReLU conv output -> G [B, C, C] = relu(c) relu(c)^T / (C HW).  With
+    ``target`` [B, C, C] returns (G, D, loss): D = G - target and loss [B] += C^2 * sum(D^2) (``loss``: the accumulator of the taps, zeros when
+    absent).  Without it returns G alone."""
+    b, ch = c.shape[:2]
+    hw = c[0, 0].numel()
+    t = ch // 32
+    ns = gram_slices(b, ch, hw)
+    g = torch.empty(b, ch, ch, device=c.device, dtype=torch.float32)
+    ws = torch.empty(max(1, b * (t * (t + 1) // 2) * (1024 * ns + 1)), device=c.device, dtype=torch.float32)
+    d = None
+    if target is not None:
+        assert tuple(target.shape) == (b, ch, ch), (target.shape, (b, ch, ch))
+        d = torch.empty_like(g)
+        if loss is None:
+            loss = torch.zeros(b, device=c.device, dtype=torch.float32)
+        assert loss.numel() == b
+    _lib.call('l2i_gram_loss_f32', _lib.fptr(g), _lib.fptr(d), _lib.fptr(loss if target is not None else None), _lib.fptr(c), _lib.fptr(target),
+              _lib.fptr(ws), b, ch, hw, ns)
+    return g if target is None else (g, d, loss)
+
+
+def gram_bwd(c, d, scale=None, out=None, accumulate=False, coef=None):
+    """l2i_gram_bwd_f32: out (+)= coef * scale * (c > 0) * (d relu(c)); d [B, C, C] symmetric, coef = 4 C / HW (the gradient of gram_loss's
+    term) when absent, ``scale`` a device tensor of 1 element (every sample) or B elements (one per sample).  ``accumulate`` adds into ``out``
+    (the trunk gradient from the deeper taps)."""
+    b, ch = c.shape[:2]
+    hw = c[0, 0].numel()
+    assert tuple(d.shape) == (b, ch, ch)
+    assert out is not None or not accumulate
+    if out is None:
+        out = torch.empty_like(c)
+    assert out.shape == c.shape
+    assert scale is None or scale.numel() in (1, b), (scale.shape, b)
+    per_sample = scale is not None and scale.numel() == b and b > 1
+    _lib.call('l2i_gram_bwd_f32', _lib.fptr(out), _lib.fptr(c), _lib.fptr(d), _lib.fptr(scale), float(4.0 * ch / hw if coef is None else coef),
+              b, ch, hw, int(bool(accumulate)), int(per_sample))
+    return out
+
+
 def axpby(a, b=None, alpha=1.0, beta=1.0, out=None):
     y = torch.empty_like(a) if out is None else out
     _lib.call('l2i_axpby_f32', _lib.fptr(y), _lib.fptr(a), _lib.fptr(b), float(alpha), float(beta), a.numel())

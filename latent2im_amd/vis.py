@@ -38,6 +38,16 @@ class VisOptions:
         return self.opt, self.data
 
 
+def load_given_w(path, device):
+    """One ``*_w.npy`` of BP.py ([B, n_latent, 512]) or a directory of them (sorted) -> one [N, n_latent, 512] tensor."""
+    import numpy as np
+    import torch
+    files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.endswith('_w.npy')) if os.path.isdir(path) else [path]
+    if not files:
+        raise FileNotFoundError('no *_w.npy in %r' % path)
+    return torch.from_numpy(np.concatenate([np.load(f).astype(np.float32) for f in files], 0)).to(device)
+
+
 def main(argv=None):
     from . import graph as graph_mod
     v = VisOptions()
@@ -49,6 +59,9 @@ def main(argv=None):
     v.parser.add_argument('--layers', type=str, default=None)
     v.parser.add_argument('--trainEmbed', action='store_true')
     v.parser.add_argument('--updateGAN', action='store_true')
+    v.parser.add_argument('--given_w', type=str, default=None,
+                          help='a *_w.npy written by BP.py, or a directory of them: edit these inverted images instead of sampled ones '
+                               '(--num_samples becomes the number of files)')
     opt, conf = v.parse(argv)
     dist.select_gpu(opt.gpu)                         # before the first torch.cuda call (vis_w.py / eval.py set CUDA_VISIBLE_DEVICES)
     dist.init_from_env()
@@ -62,6 +75,10 @@ def main(argv=None):
     os.makedirs(output_dir, exist_ok=True)
     g = graph_mod.find_model_using_name(conf.model, conf.transform)(**hostutil.set_graph_kwargs(conf))
     g.load_multi_models(opt.save_path_w, None, trainEmbed=opt.trainEmbed, updateGAN=opt.updateGAN)
+    given = None
+    if opt.given_w:
+        given = load_given_w(opt.given_w, g.device)
+        opt.num_samples = given.shape[0]
     graph_inputs = hostutil.graph_input(g, opt.num_samples, seed=opt.noise_seed)
     epochs = opt.save_path_w.split('/')[-1].split('_')[2]
     filename = os.path.join(output_dir, 'w_{}_seed{}'.format(epochs, opt.noise_seed))
@@ -73,11 +90,13 @@ def main(argv=None):
         s = slice(batch_start, min(opt.num_samples, batch_start + bs))
         batch = hostutil.batch_input(graph_inputs, s)
         new_filename = filename + '_{}_max{}_min{}'.format(name, opt.max_alpha, opt.min_alpha)
+        # the per-layer list get_w returns, of this batch's saved latents
+        given_w = None if given is None else [given[s][:, i].contiguous() for i in range(given.shape[1])]
         ag, at = g.vis_image_batch(batch, new_filename, s.start, num_panels=opt.num_panels, max_alpha=opt.max_alpha,
                                    min_alpha=opt.min_alpha, wgt=True)
         written += g.vis_multi_image_batch_alphas(batch, new_filename, alphas_to_graph=ag, alphas_to_target=at, layers=layers,
                                                   batch_start=s.start, name=name, wgt=False, wmask=False, trainEmbed=opt.trainEmbed,
-                                                  computeL2=False, given_w=None)
+                                                  computeL2=False, given_w=given_w)
     with open(os.path.join(output_dir, 'index.html'), 'w') as f:      # utils/html.make_html
         f.write('<html><body>' + ''.join('<p>%s<br><img src="%s"></p>' % (os.path.basename(w), os.path.basename(w)) for w in written)
                 + '</body></html>')

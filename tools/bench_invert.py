@@ -1,0 +1,132 @@
+"""Timing of the inversion path (BP.py) on one GPU.  HIP events, warm-up, median of repeats.
+
+(a) l2i_gram_loss_f32 + l2i_gram_bwd_f32 per launch at BP's four tap shapes for 256^2 (C x HW = 64 x 65536, 128 x 16384, 256 x 4096,
+    512 x 1024), batch 1 and 8, beside the composite they replace — relu, torch.bmm (rocBLAS), the loss, autograd's backward — in three
+    alternating runs, on inputs rotated through more than the last-level cache holds; algorithmic GB/s = (read c for the forward, read c +
+    write g for the backward) / time against 6.3 TB/s achievable.  Then Vgg16Gram.loss with its image gradient at 256^2, batch 1 and 8.
+(b) inversion iterations/s at 256^2, batch 1 and 8, synthetic weights, noise drawn per iteration.
+
+    python tools/bench_invert.py [--out profiles/invert_bench.txt] [--skip_step]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TAPS = ((64, 65536), (128, 16384), (256, 4096), (512, 1024))
+HBM = 6.3e12
+
+
+def timed(fn, warmup=5, reps=20):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return statistics.median(ts)
+
+
+def composite(c, gt):
+    x = c.detach().requires_grad_()
+    f = torch.relu(x).flatten(2)
+    g = f.bmm(f.transpose(1, 2)) / (f.shape[1] * f.shape[2])
+    loss = (torch.sum((gt - g).pow(2), [1, 2]) * (f.shape[1] ** 2)).sum()
+    loss.backward()
+    return x.grad
+
+
+def kernels_row(b, ch, hw, lines):
+    from latent2im_amd import kernels as K
+    # cold inputs: the calls rotate through enough copies of c that one round is over 512 MiB, twice the 256 MiB of last-level cache
+    copies = max(3, min(256, -(-(512 << 20) // (b * ch * hw * 4))))
+    cs = [torch.randn(b, ch, hw, device='cuda') for _ in range(copies)]
+    gt = K.gram_loss(torch.randn(b, ch, hw, device='cuda'))
+    one = torch.ones(b, device='cuda')
+    out = torch.empty_like(cs[0])
+    turn = [0]
+
+    def nxt():
+        turn[0] = (turn[0] + 1) % copies
+        return cs[turn[0]]
+
+    def fused():                                         # as the product calls them: the wrappers allocate G, D and the partials per call
+        c = nxt()
+        _, d, _ = K.gram_loss(c, gt)
+        K.gram_bwd(c, d, scale=one, out=out)
+
+    mine, theirs = [], []
+    for _ in range(3):                                   # alternating runs: the spread of each side is its run-to-run noise
+        mine.append(timed(fused))
+        theirs.append(timed(lambda: composite(nxt(), gt)))
+    bytes_alg = 3.0 * cs[0].numel() * 4                  # the least traffic: c read by each kernel, g written once (partials, G, D not counted)
+    m, t = statistics.median(mine), statistics.median(theirs)
+    lines.append('B %d  C %4d  HW %6d   fused %8.1f us (runs %s)  %6.0f GB/s = %4.1f %% of 6.3 TB/s   rocBLAS composite %8.1f us (runs %s)   fused / composite %.2f'
+                 % (b, ch, hw, m * 1e6, ' '.join('%.1f' % (v * 1e6) for v in mine), bytes_alg / m / 1e9, 100 * bytes_alg / m / HBM, t * 1e6,
+                    ' '.join('%.1f' % (v * 1e6) for v in theirs), m / t))
+    print(lines[-1], flush=True)
+
+
+def vgg_row(b, lines, size=256):
+    """Vgg16Gram.loss and its image gradient as the inversion calls them: ten convs, three pools, four Gram terms each way."""
+    from latent2im_amd import vgg16_specs
+    from latent2im_amd.perceptual16 import Vgg16Gram
+    net = Vgg16Gram(vgg16_specs.vgg16_state(), device='cuda')
+    grams = net.target_grams(torch.rand(b, 3, size, size, device='cuda') * 2 - 1)
+    x = (torch.rand(b, 3, size, size, device='cuda') * 2 - 1).requires_grad_()
+    coef = torch.linspace(0.5, 1.5, b, device='cuda')
+
+    def both():
+        x.grad = None
+        (net.loss(x, grams) * coef).sum().backward()
+
+    runs = [timed(both) for _ in range(3)]
+    lines.append('Vgg16Gram loss + image gradient %d^2  batch %d   %.2f ms (runs %s)' % (size, b, 1e3 * statistics.median(runs), ' '.join('%.2f' % (1e3 * v) for v in runs)))
+    print(lines[-1], flush=True)
+
+
+def step_row(b, lines, size=256):
+    from latent2im_amd import synth, vgg16_specs
+    from latent2im_amd.generator import Generator
+    from latent2im_amd.invert import Inverter
+    from latent2im_amd.perceptual16 import Vgg16Gram
+    gen = Generator(synth.generator_state(size, seed=100, noise_strength=0.5), size, device='cuda')
+    inv = Inverter(gen, Vgg16Gram(vgg16_specs.vgg16_state(), device='cuda'), lr=0.01, optim='Adam', n_mean_latent=256)
+    batch = torch.rand(b, 3, size, size, device='cuda') * 2 - 1
+    n = 10
+    t = timed(lambda: inv.invert(batch, n), warmup=1, reps=5)
+    lines.append('inversion %d^2  batch %d   %.2f iterations/s (%.1f ms per iteration, median of 5 runs of %d)' % (size, b, n / t, 1e3 * t / n, n))
+    print(lines[-1], flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--skip_step', action='store_true')
+    args = ap.parse_args()
+    lines = ['# tools/bench_invert.py on %s' % torch.cuda.get_device_name(0)]
+    for b in (1, 8):
+        for ch, hw in TAPS:
+            kernels_row(b, ch, hw, lines)
+    for b in (1, 8):
+        vgg_row(b, lines)
+    if not args.skip_step:
+        for b in (1, 8):
+            step_row(b, lines)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
