@@ -216,8 +216,9 @@ int l2i_conv_img_h8(const l2i_conv_params* p, void* stream);
 
 /* Streaming companions on h8 maps (csrc/l2i_stream_h8.hip; same functions as the fp32 entry points below, arithmetic in fp32 registers):
  * layout casts fp32 NCHW <-> bf16 h8 (Cpad = channel count of the h8 tensor, a multiple of 8, zero filled above C);
- * the reference's upfirdn2d on h8 planes (kernels up to 4x4, up / down in {1, 2}) with the generator's fused epilogue
- *   y = act(fir(x) + noise[b,oy,ox] * noise_w + bias[c]) * act_gain;
+ * the reference's upfirdn2d on h8 planes (kernels up to 4x4, up / down in {1, 2}) with the generator's fused epilogue, in this order:
+ *   v = act(fir(x) + noise[b,oy,ox] * noise_w + bias[c]) * act_gain   (act_gain under EVERY act, L2I_ACT_NONE included),
+ *   v *= (mask > 0 ? mask_pos : mask_neg),   y = v + addend           (the addend is NOT inside the activation: the fp32 entry differs);
  * ToRGB (x h8 -> rgb fp32 [B,3,HW]); the fused activation backward of a styled conv (dz h8; gin h8; grgb fp32; reductions fp32, zeroed by the caller);
  * out[b,c] += sum_p a * b; MaxPool2d forward (idx: [planes][OH][OW][8] bytes; relu = 1: y = max(pool, 0)) and backward (optionally + coef *
  *   coef_dev[0] * (b - a): the ContentLoss term of the pooled tap); the ContentLoss difference; y[2oy, 2ox] += c[oy, ox]; and the per-sample
@@ -248,6 +249,7 @@ int l2i_add_zero_insert_h8(void* y, const void* c, const void* mask, int64_t pla
 int l2i_mask_mul_h8(void* y, const void* g, const void* ref, float pos, float neg, int64_t slots, void* stream);                     /* y = g * (ref > 0 ? pos : neg) */
 int l2i_mask_mul_bits_h8(void* y, const void* g, const void* bits, float pos, float neg, int64_t slots, void* stream);               /* [ABI 6] the same with ref's sign plane (one byte per slot) */
 int l2i_modulate_planes_h8(void* planes, const float* w32, const float* s, int B, int Cs, int CinP, int KK, int CoutP, void* stream);
+/* CinP % 16 == 0, Cs == CinP, planes and w32 on 16-byte boundaries (16-byte accesses); anything else: L2I_E_ARG. */
 /* [r5] l2i_modulate_planes_h8 for every modulated conv of a generator pass in one launch.  `table` (device): nseg rows of eight int64 — w32 offset
  * (floats from `w32`), scale offset (floats from `s`: the layer's [B, Cs] block), output offset (16-byte slots from `planes`: the layer's
  * [B][slots per sample] block), slots per sample (= CinP/16 * KK * 2 * CoutP), KK, CoutP, Cs (= CinP), first block of the segment (ascending,
@@ -296,7 +298,11 @@ int l2i_fused_bias_act_f16(void* y, const void* x, const void* b, const void* re
 
 /* The reference op on [major, in_h, in_w] maps (minor_dim == 1, the only layout the path uses:
  * op/upfirdn2d.py:98) with an optional fused epilogue (all NULL/0 = the plain reference op):
- *   y = act( fir(x) + noise[b,oy,ox]*noise_w + bias[c] + addend[idx] ) * act_gain,   major = b*channels + c */
+ *   v = fir(x) + noise[b,oy,ox]*noise_w + bias[c] + addend[idx],   major = b*channels + c   (the addend is INSIDE the activation),
+ *   L2I_ACT_LRELU: y = (v > 0 ? v : v*act_slope) * act_gain;  L2I_ACT_RELU: y = max(v, 0);  L2I_ACT_NONE: y = v
+ *   (act_gain is applied under L2I_ACT_LRELU ONLY; the h8 entry applies it under every act), then the mask of l2i_upfirdn2d_masked_f32, last.
+ * kh * kw <= 64, up / down >= 1; pads may be negative (a crop).  major need not be a multiple of channels: b = major / channels, c = major %
+ * channels, so the last sample is partial and noise holds ceil(major / channels) maps; channels <= 0 reads as 1. */
 int l2i_upfirdn2d_f32(float* y, const float* x, const float* k, int64_t major, int in_h, int in_w, int kh, int kw,
                       int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                       int channels, const float* noise, float noise_w, const float* bias, const float* addend,

@@ -393,15 +393,18 @@ extern "C" int H8_NAME(l2i_upfirdn2d_h8)(void* y, const void* x, const float* k,
                                 float act_gain, const void* mask, float mask_pos, float mask_neg, const void* addend, const float* k1y, const float* k1x, int mask_bits,
                                 void* stream) {
     if (!y || !x || !k) return l2i_set_error(L2I_E_ARG, "upfirdn2d_h8: null tensor");
-    if (mask_bits && !(mask && k1y && k1x && kh == 4 && kw == 4 && up == 1 && down == 1))
+    const bool plane32 = (long long)in_h * in_w * 16 < 0x7fffffffLL;       // the separable kernels address a plane with 32-bit byte offsets
+    if (mask_bits && !(mask && k1y && k1x && kh == 4 && kw == 4 && up == 1 && down == 1 && plane32))
         return l2i_set_error(L2I_E_UNSUPPORTED, "upfirdn2d_h8: a sign-plane mask rides on the separable 4x4 blur without resampling only");
     if (planes <= 0 || channels <= 0 || (channels % 8) != 0 || in_h <= 0 || in_w <= 0 || kh <= 0 || kw <= 0 || kh > 4 || kw > 4 || (up != 1 && up != 2) || (down != 1 && down != 2))
         return l2i_set_error(L2I_E_ARG, "upfirdn2d_h8: kernels up to 4x4, up / down in {1, 2}, channels % 8 == 0");
     const int out_h = (in_h * up + pad_y0 + pad_y1 - kh) / down + 1, out_w = (in_w * up + pad_x0 + pad_x1 - kw) / down + 1;
     if (out_h <= 0 || out_w <= 0) return l2i_set_error(L2I_E_ARG, "upfirdn2d_h8: empty output");
     const long long total = (long long)planes * out_h * out_w;
-    if (k1y && k1x && kh == 4 && kw == 4 && up == 1 && down == 1) {
-        // the caller vouches that k = outer(k1y, k1x) (the path's blurs: [1,3,3,1] x [1,3,3,1] * gain); taps of the flipped kernel
+    if (k1y && k1x && kh == 4 && kw == 4 && up == 1 && down == 1 && plane32) {
+        // the caller vouches that k = outer(k1y, k1x) (the path's blurs: [1,3,3,1] x [1,3,3,1] * gain); taps of the flipped kernel.  Like its
+        // down = 2 and up = 2 siblings below, the kernel addresses a plane with 32-bit byte offsets inside a 32-bit descriptor range: a larger plane
+        // goes to the generic kernel
         constexpr int RB = 16;
         const float4 ty = make_float4(k1y[3], k1y[2], k1y[1], k1y[0]), tx = make_float4(k1x[3], k1x[2], k1x[1], k1x[0]);
         const long long waves = (long long)planes * ((out_h + RB - 1) / RB) * ((out_w + 60) / 61);
@@ -417,7 +420,7 @@ extern "C" int H8_NAME(l2i_upfirdn2d_h8)(void* y, const void* x, const float* k,
         return L2I_OK;
     }
     const bool plain = !noise && !bias && act == L2I_ACT_NONE && act_gain == 1.f && !mask;
-    if (k1y && k1x && kh == 4 && kw == 4 && plain && up == 1 && down == 2 && !addend && pad_x0 == 1 && pad_y0 == 1 && (long long)in_h * in_w * 16 < 0x7fffffffLL) {
+    if (k1y && k1x && kh == 4 && kw == 4 && plain && up == 1 && down == 2 && !addend && pad_x0 == 1 && pad_y0 == 1 && plane32) {
         constexpr int RB = 8;                              // the discriminator's skip blur, evaluated where the stride-2 1x1 samples it
         const float4 ty = make_float4(k1y[3], k1y[2], k1y[1], k1y[0]), tx = make_float4(k1x[3], k1x[2], k1x[1], k1x[0]);
         const long long waves = (long long)planes * ((out_h + RB - 1) / RB) * ((out_w + 61) / 62);
@@ -426,8 +429,7 @@ extern "C" int H8_NAME(l2i_upfirdn2d_h8)(void* y, const void* x, const float* k,
         L2I_CHECK_LAUNCH();
         return L2I_OK;
     }
-    if (k1y && k1x && kh == 4 && kw == 4 && plain && up == 2 && down == 1 && pad_x0 == 2 && pad_y0 == 2 && out_h == 2 * in_h && out_w == 2 * in_w &&
-        (long long)in_h * in_w * 16 < 0x7fffffffLL) {
+    if (k1y && k1x && kh == 4 && kw == 4 && plain && up == 2 && down == 1 && pad_x0 == 2 && pad_y0 == 2 && out_h == 2 * in_h && out_w == 2 * in_w && plane32) {
         constexpr int RB = 8;                              // its adjoint (zero insertion + blur), with the skip sum as addend
         const float4 ty = make_float4(k1y[3], k1y[2], k1y[1], k1y[0]), tx = make_float4(k1x[3], k1x[2], k1x[1], k1x[0]);
         const long long waves = (long long)planes * ((in_h + RB - 1) / RB) * ((in_w + 61) / 62);
@@ -844,6 +846,7 @@ __global__ __launch_bounds__(256) void modulate_planes_kernel(u32x4* __restrict_
 extern "C" int H8_NAME(l2i_modulate_planes_h8)(void* planes, const float* w32, const float* s, int B, int Cs, int CinP, int KK, int CoutP, void* stream) {
     if (!planes || !w32 || !s || B <= 0 || CinP <= 0 || (CinP % 16) != 0 || Cs > CinP || KK <= 0 || CoutP <= 0) return l2i_set_error(L2I_E_ARG, "modulate_planes_h8: bad arguments");
     if (Cs != CinP) return l2i_set_error(L2I_E_ARG, "modulate_planes_h8: the scale vector must cover the padded channel count");
+    if (((uintptr_t)planes | (uintptr_t)w32) % 16) return l2i_set_error(L2I_E_ARG, "modulate_planes_h8: planes and w32 must be 16-byte aligned");
     const long long sps = (long long)(CinP / 16) * KK * 2 * CoutP, total = sps * B;
     hipLaunchKernelGGL(modulate_planes_kernel, dim3(l2i_grid_for(total, 256, 256 * 8)), dim3(256), 0, (hipStream_t)stream, (u32x4*)planes, w32, s, Cs, sps, KK, CoutP, total);
     L2I_CHECK_LAUNCH();

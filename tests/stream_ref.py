@@ -482,7 +482,7 @@ POOL_H8_KSP = [(2, 2, 0), (3, 2, 1), (3, 1, 1), (2, 1, 0), (3, 3, 0)]          #
 ADD_DIFF_GEOMS = [('oh3_ow4', 3, 4), ('oh5_ow6', 5, 6)]
 CAST_GEOMS = [('c3_pad16', 2, 3, 16, 5, 7), ('hw1', 1, 8, 8, 1, 1), ('c13_pad16_hw1', 1, 13, 16, 1, 1)]          # (id, B, C, Cpad, H, W)
 
-# __global__ kernels of the two files: the ones a row above claims, and the ones out of scope by name (a new kernel has to be placed)
+# __global__ kernels of the two files: the ones a row above claims (tests/fir_ref.py claims the others), and the ones out of scope by name (a new kernel has to be placed)
 CLAIMED_KERNELS = {
     'torgb_fwd_kernel': 'TORGB_F32_GEOMS', 'sg2_act_bwd_kernel': 'SG2_F32_GEOMS', 'dot_reduce_kernel': 'DOT_F32_GEOMS',
     'maxpool_fwd_kernel': 'POOL_F32_GEOMS', 'maxpool_fwd_vec_kernel': 'POOL_F32_GEOMS', 'maxpool_bwd_kernel': 'POOL_F32_GEOMS',
@@ -494,9 +494,7 @@ CLAIMED_KERNELS = {
     'mask_mul_h8_kernel': 'ELEMWISE_N', 'mask_mul_bits_h8_kernel': 'ELEMWISE_N',
 }
 ZERO_INSERT_GEOMS = [('odd_9x13', 2, 16, 9, 13), ('even_4x6', 1, 8, 4, 6)]          # (id, B, C, H, W): OH = ceil(H / 2), OW = ceil(W / 2)
-OUT_OF_SCOPE_KERNELS = ('fba_kernel', 'upfirdn2d_kernel', 'upfirdn2d_k4_kernel', 'upfirdn2d_k4_down2_stream_kernel', 'upfirdn2d_up2k4_kernel',
-                        'upfirdn2d_k4_stream_kernel', 'upfirdn2d_h8_kernel', 'upfirdn2d_h8_sep4_kernel', 'upfirdn2d_h8_sep4_down2_kernel',
-                        'upfirdn2d_h8_sep4_up2_kernel', 'modulate_planes_kernel', 'modulate_planes_multi_kernel')
+OUT_OF_SCOPE_KERNELS = ()          # the FIR, bias-activation and weight-plane kernels are claimed by the rows of tests/fir_ref.py
 
 
 # ---- rows: operation x operand case x geometry ------------------------------------------------------------------------------------------------------

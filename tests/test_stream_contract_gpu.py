@@ -11,9 +11,9 @@ import torch
 
 from latent2im_amd import _lib, conv, kernels, kernels16 as K16
 from tests import stream_ref as sr
+from tests.contract_gpu import DEV, compare as _compare, dev, guarded, keep, refused, release, untouched
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
 ROWS = sr.all_rows()
 PARAMS = [(r, e) for r in ROWS for e in (('f32',) if r.kind == 'f32' else ('bf16', 'f16'))]
 PREFILL = 3.5
@@ -36,65 +36,14 @@ def precision():
     conv.PRECISION = old
 
 
-def guarded(shape, dtype=torch.float32, off=0):
-    """(buffer, view): ``view`` of ``shape`` inside a sentinel-filled buffer, GUARD (+ off) elements from its start."""
-    n = 1
-    for s in shape:
-        n *= s
-    fill = sr.SENTINEL_U8 if dtype == torch.uint8 else sr.SENTINEL
-    buf = torch.full((n + 2 * sr.GUARD + 4,), fill, dtype=dtype, device=DEV)
-    return buf, buf[sr.GUARD + off:sr.GUARD + off + n].view(shape)
-
-
-def untouched(buf, view=None):
-    """The guards of ``buf`` around ``view`` (the whole buffer when ``view`` is None) still hold the sentinel."""
-    fill = sr.SENTINEL_U8 if buf.dtype == torch.uint8 else sr.SENTINEL
-    if view is None:
-        return bool((buf == fill).all())
-    lo = (view.data_ptr() - buf.data_ptr()) // buf.element_size()
-    return bool((buf[:lo] == fill).all()) and bool((buf[lo + view.numel():] == fill).all())
-
-
-_KEEP = []          # the device operands of the running test: a pointer handed to _lib.call has to outlive the launch that reads it
-
-
 @pytest.fixture(autouse=True)
 def _operands_outlive_the_launch():
     yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
-
-
-def keep(t):
-    if t is not None:
-        _KEEP.append(t)
-    return t
-
-
-def dev(t):
-    return None if t is None else keep(t.to(DEV))
-
-
-def same(got, want):
-    got, want = got.cpu(), want.cpu()
-    if got.dtype.is_floating_point:
-        return torch.equal(torch.isnan(got), torch.isnan(want)) and torch.equal(torch.nan_to_num(got.double()), torch.nan_to_num(want.double()))
-    return torch.equal(got, want)
+    release()
 
 
 def compare(row, elem, got, exp, add_m=None):
-    bad = []
-    for name, (want, bound) in exp.items():
-        if bound is None:
-            ok = same(got[name], want)
-            _LOG.append('%s %s %s exact %s' % (row.id, elem, name, 'equal' if ok else 'DIFFERENT'))
-        else:
-            err, bnd, ratio = sr.worst(got[name], want, bound)
-            ok = ratio <= 1.0
-            _LOG.append('%s %s %s err %.3e bound %.3e ratio %.3f' % (row.id, elem, name, err, bnd, ratio))
-        if not ok:
-            bad.append(_LOG[-1])
-    assert not bad, bad
+    _compare(row, elem, got, exp, _LOG)
 
 
 def h8in(row, elem):
@@ -297,13 +246,6 @@ def test_streaming_kernel_against_the_model(row, elem, precision):
 
 
 # ---- refusals: the error code, and outputs that still hold the sentinel ---------------------------------------------------------------------------------
-def refused(code, name, *args, outs=(), dtype=None):
-    with pytest.raises(_lib.L2IError, match=r'failed \(%d\)' % code):
-        _lib.call(name, *args, dtype=dtype)
-    torch.cuda.synchronize()
-    assert all(untouched(b) for b in outs), name
-
-
 def _f32_maps(B, C, HW, off=0):
     """A [B, C, HW] float map of ones that starts ``off`` floats into its (16-byte aligned) buffer."""
     buf = torch.ones(B * C * HW + 8, device=DEV)
