@@ -500,10 +500,27 @@ int l2i_gram_loss_f32(float* G, float* D, float* loss, const float* c, const flo
 int l2i_gram_bwd_f32(float* g, const float* c, const float* D, const float* scale, float coef, int B, int C, int HW, int accumulate, int scale_stride,
                      void* stream);
 
+/* [ABI 11] The same two on 16-bit h8 taps (csrc/l2i_gram_h8.hip; bf16 elements, and IEEE fp16 with the suffix _f16).  c, g: [B][C/8][HW][8];
+ * G, D, Gt [B, C, C], loss [B], scale, ws (same size) stay fp32.
+ * l2i_gram_loss_h8: the semantics, the slicing, the fixed summation order and the bit-symmetric G of l2i_gram_loss_f32.  The products run on
+ *   v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulation (a product of two 16-bit elements is exact in fp32); the contraction index is the pixel,
+ *   which h8 strides, so both operands are staged [pixel][channels] in LDS and read transposed (ds_read_b64_tr_b16).
+ * l2i_gram_bwd_h8: g (+)= coef * scale[b * scale_stride] * (c > 0) * (D relu(c)) with g in h8.  D is multiplied by coef * scale[b] in fp32 and THEN
+ *   rounded to the element type (the gradient scale protects it from fp16 underflow); the sum is fp32; accumulate != 0 adds the h8 gradient
+ *   already in g in fp32, so the store is the only rounding of the sum.  D need not be symmetric here.
+ * Both: C % 32 == 0, C <= 512, any HW >= 1 with C * HW * 2 bytes < 4 GiB, any B; other shapes return L2I_E_UNSUPPORTED.  c or g off a 16-byte
+ * boundary returns L2I_E_ARG (an h8 slot is 16 bytes: there is no unaligned path). */
+int l2i_gram_loss_h8(float* G, float* D, float* loss, const void* c, const float* Gt, float* ws, int B, int C, int HW, int nslices, void* stream);
+int l2i_gram_loss_h8_f16(float* G, float* D, float* loss, const void* c, const float* Gt, float* ws, int B, int C, int HW, int nslices, void* stream);
+int l2i_gram_bwd_h8(void* g, const void* c, const float* D, const float* scale, float coef, int B, int C, int HW, int accumulate, int scale_stride,
+                    void* stream);
+int l2i_gram_bwd_h8_f16(void* g, const void* c, const float* D, const float* scale, float coef, int B, int C, int HW, int accumulate, int scale_stride,
+                        void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
- * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
-#define L2I_ABI_VERSION 10
+ * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
+#define L2I_ABI_VERSION 11
 int l2i_abi_version(void);
 int l2i_sizeof_conv_params(void);       /* sizeof(struct l2i_conv_params) of THIS build */
 

@@ -119,6 +119,8 @@ _SIGNATURES = {
     'l2i_adam_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
     'l2i_gram_loss_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'l2i_gram_loss_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'l2i_gram_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
     'l2i_sizeof_conv_params': (c_i, []),
@@ -129,7 +131,7 @@ _F16_TWINS = frozenset(k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i
 for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
-ABI_VERSION = 10         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
+ABI_VERSION = 11         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 
 EXPORTS = tuple(_SIGNATURES)
 

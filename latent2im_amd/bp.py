@@ -81,13 +81,23 @@ def build_parser():
     p.add_argument('--lr', type=float, default=0.01)
     p.add_argument('--synthetic_weights', action='store_true',
                    help='run on seeded random-init G / VGG-16 when the checkpoint paths of constants.py do not exist')
+    p.add_argument('--precision', type=str, choices=['f32', 'f16', 'bf16'], default='f32',
+                   help='element type of the feature maps: f32, or the 16-bit h8 path with IEEE fp16 (loss-scaled, Adam only) or bf16 maps; latents and images are saved as fp32 either way')
     return p
 
 
-def load_networks(resolution, device):
-    from . import graph, synth, vgg16_specs
-    from .generator import Generator
-    from .perceptual16 import Vgg16Gram
+def load_networks(resolution, device, precision='f32'):
+    """The generator and the VGG-16 Gram network of one precision: the fp32 pair, or ('f16' / 'bf16') the 16-bit pair (conv.PRECISION is set: the
+    16-bit classes and kernels16 read their element type from it)."""
+    from . import conv, graph, synth, vgg16_specs
+    if precision == 'f32':
+        from .generator import Generator
+        from .perceptual16 import Vgg16Gram
+    else:
+        assert precision in conv.H8_PRECISIONS, precision
+        conv.PRECISION = precision
+        from .nets16 import Generator
+        from .perceptual16 import Vgg16Gram16 as Vgg16Gram
     if graph._checkpoint_or_synthetic('generator (g_path)', constants.g_path):
         g_state = graph._to_numpy_state(torch.load(constants.g_path, map_location='cpu')['g_ema'])
     else:
@@ -107,8 +117,8 @@ def main(argv=None):
     if args.synthetic_weights:
         constants.ALLOW_SYNTHETIC_WEIGHTS = True
     device = 'cuda'
-    gen, vgg = load_networks(args.resolution, device)
-    inv = Inverter(gen, vgg, lr=args.lr, optim=args.optimizer)
+    gen, vgg = load_networks(args.resolution, device, args.precision)
+    inv = Inverter(gen, vgg, lr=args.lr, optim=args.optimizer, batch=args.batch_size)
     files = image_folder(args.path)
     os.makedirs(os.path.join(args.save_path, 'latent'), exist_ok=True)
     curve = np.zeros(0)

@@ -10,7 +10,7 @@
 //                         global -> LDS by DMA, ONE staged image feeds both MFMA operands (A[row][k] and B[k][col] are the same lane map on
 //                         v_mfma_f32_32x32x2_f32: lane = row, half = k), the four waves take 64 pixels of the chunk each and their four
 //                         32x32 accumulators are added in wave order into the slice's partial tile.
-//   gram_reduce_kernel    block (tile pair, sample): partial tiles added in slice order, / (C HW), G and its mirror written, D = G - Gt and the
+//   gram_reduce_kernel    (l2i_gram_common.h, shared with the h8 file, as is gram_finish_kernel) block (tile pair, sample): partial tiles added in slice order, / (C HW), G and its mirror written, D = G - Gt and the
 //                         pair's sum of D^2 (off-diagonal entries counted twice).
 //   gram_finish_kernel    block (sample): the pair sums in pair order, loss[b] += C^2 * sum.
 // Backward: g[b] (+)= coef * scale[b * scale_stride] * (c[b] > 0) * (D[b] relu(c[b])), a [C, C] x [C, HW] product per sample with the K loop of l2i_gemm.hip
@@ -21,19 +21,12 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_gram_common.h"      // gram_pair, gram_reduce_kernel, gram_finish_kernel
 
 namespace gr {
-constexpr int KC = 256;                    // pixels per staged chunk: one row of a chunk = 1 KiB = one wave DMA
+// (KC = 256 pixels per staged chunk, l2i_gram_common.h: one row of a chunk = 1 KiB = one wave DMA)
 constexpr int RS = KC + 4;                 // LDS row stride in floats: 65 sixteen-byte units, odd, so the 16 lanes of a ds_read_b128 group (distinct rows) hit distinct banks
-constexpr int TILE = 32 * 32;
 constexpr int CK = 16, CKh = 8, BN = 256;  // backward: channels per chunk, pixels per block
-}
-
-// pair index -> (i, j), i <= j, row-major over the upper triangle of T x T tiles
-__device__ __forceinline__ void gram_pair(int pair, int T, int& i, int& j) {
-    int row = 0, left = pair;
-    while (left >= T - row) { left -= T - row; ++row; }
-    i = row; j = row + left;
 }
 
 template <bool VEC>
@@ -100,47 +93,6 @@ __global__ __launch_bounds__(256, 2) void gram_partial_kernel(float* __restrict_
         const int e = tid + 256 * n;
         out[e] = (smem[e] + smem[TILE + e]) + (smem[2 * TILE + e] + smem[3 * TILE + e]);
     }
-}
-
-__global__ __launch_bounds__(256) void gram_reduce_kernel(float* __restrict__ G, float* __restrict__ D, float* __restrict__ pair_loss, const float* __restrict__ ws,
-                                                          const float* __restrict__ Gt, int C, float norm, int nslices, int npairs) {
-    __shared__ float red[4];
-    const int tid = threadIdx.x, pair = blockIdx.x, b = blockIdx.y;
-    int ti, tj;
-    gram_pair(pair, C / 32, ti, tj);
-    const float* part = ws + ((size_t)b * npairs + pair) * nslices * gr::TILE;
-    const size_t base = (size_t)b * C * C;
-    float sq = 0.f;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int e = tid + 256 * n, row = e >> 5, col = e & 31;
-        if (ti == tj && row > col) continue;   // a diagonal tile writes its own lower triangle as the mirror of the upper one
-        float s = 0.f;
-        for (int k = 0; k < nslices; ++k) s += part[(size_t)k * gr::TILE + e];
-        const float g = s / norm;
-        const size_t up = base + (size_t)(ti * 32 + row) * C + tj * 32 + col, lo = base + (size_t)(tj * 32 + col) * C + ti * 32 + row;
-        G[up] = g;
-        G[lo] = g;
-        if (Gt) {
-            const float d = g - Gt[up];
-            D[up] = d;
-            D[lo] = d;
-            sq += (up == lo ? 1.f : 2.f) * (d * d);
-        }
-    }
-    if (Gt) {
-        sq = block_sum(sq, red);
-        if (tid == 0) pair_loss[(size_t)b * npairs + pair] = sq;
-    }
-}
-
-__global__ __launch_bounds__(256) void gram_finish_kernel(float* __restrict__ loss, const float* __restrict__ pair_loss, int npairs, float c2) {
-    __shared__ float red[4];
-    const int tid = threadIdx.x, b = blockIdx.x;
-    float s = 0.f;
-    for (int k = tid; k < npairs; k += 256) s += pair_loss[(size_t)b * npairs + k];
-    s = block_sum(s, red);
-    if (tid == 0) loss[b] += c2 * s;
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------------------

@@ -128,6 +128,45 @@ def sqdiff(a, b, coef=0.0, want_grad=False, coef_dev=None, want_sum=True):
     return s, g
 
 
+def gram_loss(c, target=None, loss=None):
+    """l2i_gram_loss_h8: kernels.gram_loss on an h8 tap c [B, C/8, H, W, 8] (pre-ReLU).  G, ``target``, D [B, C, C] and ``loss`` [B] are fp32;
+    the slicing is kernels.gram_slices, a function of the shape alone, so a target's Grams and an image's are summed in the same order."""
+    from .kernels import gram_slices
+    b, g8, h, w, _ = c.shape
+    ch, hw = g8 * 8, h * w
+    t = ch // 32
+    ns = gram_slices(b, ch, hw)
+    g = torch.empty(b, ch, ch, device=c.device, dtype=torch.float32)
+    ws = torch.empty(max(1, b * (t * (t + 1) // 2) * (1024 * ns + 1)), device=c.device, dtype=torch.float32)
+    d = None
+    if target is not None:
+        assert tuple(target.shape) == (b, ch, ch), (target.shape, (b, ch, ch))
+        d = torch.empty_like(g)
+        if loss is None:
+            loss = torch.zeros(b, device=c.device, dtype=torch.float32)
+        assert loss.numel() == b
+    _lib.call('l2i_gram_loss_h8', _lib.fptr(g), _lib.fptr(d), _lib.fptr(loss if target is not None else None), _h8(c), _lib.fptr(target),
+              _lib.fptr(ws), b, ch, hw, ns, dtype=c.dtype)
+    return g if target is None else (g, d, loss)
+
+
+def gram_bwd(c, d, scale=None, out=None, accumulate=False, coef=None):
+    """l2i_gram_bwd_h8: kernels.gram_bwd with c and ``out`` in h8: out (+)= coef * scale * (c > 0) * (d relu(c)); d [B, C, C] fp32 is scaled by
+    coef * scale in fp32 before it is rounded to the element type.  ``accumulate`` adds into ``out`` (the trunk gradient from the deeper taps)."""
+    b, g8, h, w, _ = c.shape
+    ch, hw = g8 * 8, h * w
+    assert tuple(d.shape) == (b, ch, ch)
+    assert out is not None or not accumulate
+    if out is None:
+        out = torch.empty_like(c)
+    assert out.shape == c.shape and out.dtype == c.dtype
+    assert scale is None or scale.numel() in (1, b), (scale.shape, b)
+    per_sample = scale is not None and scale.numel() == b and b > 1
+    _lib.call('l2i_gram_bwd_h8', _h8(out), _h8(c), _lib.fptr(d), _lib.fptr(scale), float(4.0 * ch / hw if coef is None else coef),
+              b, ch, hw, int(bool(accumulate)), int(per_sample), dtype=c.dtype)
+    return out
+
+
 def add_zero_insert(y, c, mask=None):
     """y[.., 2oy, 2ox, :] += c[.., oy, ox, :] * (mask[.., 2oy, 2ox, :] > 0 if a mask is given) in place (h8)."""
     B, G8, H, W, _ = y.shape

@@ -92,6 +92,28 @@ F16_SCALE_RES = dict(R=2, V=2, D=0, G=0)
 F16_D_BLOCK_GAIN = 2.0
 
 
+def invert_scale_for(resolution, batch):
+    """log2 of the STATIC gradient scales of the fp16 inversion (invert.Inverter): P = the VGG-16 Gram branch (perceptual16.Vgg16Gram16), G = the
+    generator.  The rule is loss_scale_for's — the largest gradient map of a branch near 2^5 — but the sign is the other one: the inversion loss is a
+    SUM over samples of Gram terms weighted C^2, its gradients are LARGE (the generator's 4^2 map reaches 2^14 at 256^2, 2^16 = fp16's largest number
+    at 1024^2, in the first iteration from the mean latent), so the exponents scale DOWN.  Measured with tools/probe_invert16.py on synthetic weights
+    (profiles/invert16_gradient_ranges.txt) at 32^2, 64^2, 256^2 (batch 1 and 8) and 1024^2 (batch 1); resolutions between them interpolate.
+    ``batch`` does not enter: every sample's term is its own (no mean over the batch), and the batch-8 maxima are those of the largest sample
+    (0 .. 2 octaves above batch 1), which the table's choice of the more negative of the two covers."""
+    lr = math.log2(resolution)
+    pts = sorted(F16_INVERT_LOG2)
+    lo = max([p for p in pts if p <= lr] or pts[:1])
+    hi = min([p for p in pts if p >= lr] or pts[-1:])
+    t = 0.0 if hi == lo else (lr - lo) / (hi - lo)
+    return {k: int(math.floor(F16_INVERT_LOG2[lo][k] * (1 - t) + F16_INVERT_LOG2[hi][k] * t)) for k in ('P', 'G')}
+
+
+# log2(resolution) -> exponents: 5 - round(log2 of the branch's largest gradient map), the lower of batch 1 and batch 8 (measured largest maps, log2, batch
+# 1 / 8: P 7.3 / 8.2, 5.9 / 7.5, 6.9 / 7.0, 4.2; G 9.2 / 10.3, 9.2 / 11.0, 14.3 / 14.3, 15.8).  The smallest maps keep normal numbers: the median of the Gram
+# branch's conv1_2 gradient is 2^-9.2 at 1024^2 (2^-8.2 scaled), of the generator's image-end map 2^-1.7 (2^-12.7 scaled; fp16 normals end at 2^-14).
+F16_INVERT_LOG2 = {5: dict(P=-3, G=-5), 6: dict(P=-3, G=-6), 8: dict(P=-2, G=-9), 10: dict(P=1, G=-11)}
+
+
 # [r6] The scales live on the NETWORK objects (`net.scaler`, an optim.LossScaler shared by the four networks of one graph; None = unscaled: bf16
 # elements, or an fp16 network driven directly by a test) — round 5 kept them in a module-global dict that every load_networks() call overwrote, so two
 # live graphs of different resolution or batch shared whichever was built last.  On top of the static exponents the scaler carries ONE dynamic power

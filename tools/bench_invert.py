@@ -7,6 +7,13 @@
 (b) inversion iterations/s at 256^2, batch 1 and 8, synthetic weights, noise drawn per iteration.
 
     python tools/bench_invert.py [--out profiles/invert_bench.txt] [--skip_step]
+
+``--precision f16`` / ``bf16`` (or a list: ``f32,f16,bf16``) times the 16-bit path instead:
+(a) l2i_gram_loss_h8 + l2i_gram_bwd_h8 beside the fp32 pair at the same eight tap shapes, same protocol; GB/s against the least traffic of the
+    16-bit pair, which is half the fp32 bytes for c and g.  Then Vgg16Gram16.loss with its image gradient.
+(b) inversion iterations/s per precision at 256^2 (batch 1 and 8) and 1024^2 (batch 1), with the library calls of one iteration counted.
+
+    python tools/bench_invert.py --precision f32,f16,bf16 --out profiles/invert16_bench.txt
 """
 import argparse
 import os
@@ -77,8 +84,90 @@ def kernels_row(b, ch, hw, lines):
     print(lines[-1], flush=True)
 
 
-def vgg_row(b, lines, size=256):
+def kernels16_row(b, ch, hw, prec, lines):
+    """The h8 pair of ``prec`` beside the fp32 pair on the same values, alternating runs, cold inputs (each side rotates through > 512 MiB)."""
+    from latent2im_amd import conv, kernels as K, kernels16 as K16
+    dtype = torch.float16 if prec == 'f16' else torch.bfloat16
+    h, w = (hw // 256, 256) if hw >= 256 else (1, hw)
+    copies32 = max(3, min(256, -(-(512 << 20) // (b * ch * hw * 4))))
+    copies16 = max(3, min(512, -(-(512 << 20) // (b * ch * hw * 2))))
+    c32 = [torch.randn(b, ch, hw, device='cuda') for _ in range(copies32)]
+    c16 = [conv.to_h8(torch.randn(b, ch, h, w, device='cuda'), dtype=dtype) for _ in range(copies16)]
+    gt = K.gram_loss(torch.randn(b, ch, hw, device='cuda'))
+    one = torch.ones(b, device='cuda')
+    out32, out16 = torch.empty_like(c32[0]), torch.empty_like(c16[0])
+    turn = [0, 0]
+
+    def f32():
+        turn[0] = (turn[0] + 1) % copies32
+        _, d, _ = K.gram_loss(c32[turn[0]], gt)
+        K.gram_bwd(c32[turn[0]], d, scale=one, out=out32)
+
+    def h8():
+        turn[1] = (turn[1] + 1) % copies16
+        _, d, _ = K16.gram_loss(c16[turn[1]], gt)
+        K16.gram_bwd(c16[turn[1]], d, scale=one, out=out16)
+
+    mine, theirs = [], []
+    for _ in range(3):
+        mine.append(timed(h8))
+        theirs.append(timed(f32))
+    bytes_alg = 3.0 * c16[0].numel() * 2                  # c read by each kernel, g written once, two bytes an element
+    m, t = statistics.median(mine), statistics.median(theirs)
+    lines.append('%-4s B %d  C %4d  HW %6d   h8 pair %8.1f us (runs %s)  %6.0f GB/s = %4.1f %% of 6.3 TB/s   fp32 pair %8.1f us (runs %s)   h8 / fp32 %.2f'
+                 % (prec, b, ch, hw, m * 1e6, ' '.join('%.1f' % (v * 1e6) for v in mine), bytes_alg / m / 1e9, 100 * bytes_alg / m / HBM, t * 1e6,
+                    ' '.join('%.1f' % (v * 1e6) for v in theirs), m / t))
+    print(lines[-1], flush=True)
+
+
+def _networks(size, prec):
+    """(generator, VGG-16 Gram network) of one precision on synthetic weights (conv.PRECISION is set for the 16-bit classes)."""
+    from latent2im_amd import conv, synth, vgg16_specs
+    if prec == 'f32':
+        from latent2im_amd.generator import Generator
+        from latent2im_amd.perceptual16 import Vgg16Gram
+    else:
+        conv.PRECISION = prec
+        from latent2im_amd.nets16 import Generator
+        from latent2im_amd.perceptual16 import Vgg16Gram16 as Vgg16Gram
+    return Generator(synth.generator_state(size, seed=100, noise_strength=0.5), size, device='cuda'), Vgg16Gram(vgg16_specs.vgg16_state(), device='cuda')
+
+
+def count_calls(fn):
+    """Library entry-point calls (latent2im_amd._lib.call and the conv launches) made by one run of ``fn``."""
+    from latent2im_amd import _lib, conv
+    n = [0]
+    real_call, real_launch = _lib.call, conv._launch
+
+    def call(*a, **k):
+        n[0] += 1
+        return real_call(*a, **k)
+
+    def launch(*a, **k):
+        n[0] += 1
+        return real_launch(*a, **k)
+    _lib.call, conv._launch = call, launch
+    try:
+        fn()
+    finally:
+        _lib.call, conv._launch = real_call, real_launch
+    return n[0]
+
+
+def vgg_row(b, lines, size=256, prec='f32'):
     """Vgg16Gram.loss and its image gradient as the inversion calls them: ten convs, three pools, four Gram terms each way."""
+    if prec != 'f32':
+        net = _networks(32, prec)[1]
+        grams = net.target_grams(torch.rand(b, 3, size, size, device='cuda') * 2 - 1)
+        x = (torch.rand(b, 3, size, size, device='cuda') * 2 - 1).requires_grad_()
+
+        def both16():
+            x.grad = None
+            net.loss(x, grams).sum().backward()
+        runs = [timed(both16) for _ in range(3)]
+        lines.append('%-4s Vgg16Gram16 loss + image gradient %d^2  batch %d   %.2f ms (runs %s)' % (prec, size, b, 1e3 * statistics.median(runs), ' '.join('%.2f' % (1e3 * v) for v in runs)))
+        print(lines[-1], flush=True)
+        return
     from latent2im_amd import vgg16_specs
     from latent2im_amd.perceptual16 import Vgg16Gram
     net = Vgg16Gram(vgg16_specs.vgg16_state(), device='cuda')
@@ -109,12 +198,51 @@ def step_row(b, lines, size=256):
     print(lines[-1], flush=True)
 
 
+def step16_row(size, b, prec, lines, n=10):
+    """Iterations/s of one precision (noise drawn per iteration), three runs of the median-of-5 timing, and the library calls of one iteration."""
+    from latent2im_amd import conv
+    from latent2im_amd.invert import Inverter
+    gen, vgg = _networks(size, prec)
+    inv = Inverter(gen, vgg, lr=0.01, optim='Adam', n_mean_latent=256, batch=b)
+    batch = torch.rand(b, 3, size, size, device='cuda') * 2 - 1
+    runs = [timed(lambda: inv.invert(batch, n), warmup=1, reps=5) for _ in range(3)]
+    calls = (count_calls(lambda: inv.invert(batch, 3)) - count_calls(lambda: inv.invert(batch, 1))) // 2
+    t = statistics.median(runs)
+    lines.append('%-4s inversion %4d^2  batch %d   %7.2f iterations/s (%.1f ms per iteration; runs %s iterations/s)   %d library calls per iteration%s'
+                 % (prec, size, b, n / t, 1e3 * t / n, ' '.join('%.2f' % (n / v) for v in runs), calls,
+                    '' if inv.scaler is None else '   scaler %s' % inv.scaler.stats()))
+    print(lines[-1], flush=True)
+    conv.PRECISION = 'f32'
+
+
+def main16(precs, args, lines):
+    for prec in [p for p in precs if p != 'f32']:
+        for b in (1, 8):
+            for ch, hw in TAPS:
+                kernels16_row(b, ch, hw, prec, lines)
+        for b in (1, 8):
+            vgg_row(b, lines, prec=prec)
+    if not args.skip_step:
+        for size, b in ((256, 1), (256, 8), (1024, 1)):
+            for prec in precs:
+                step16_row(size, b, prec, lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--skip_step', action='store_true')
+    ap.add_argument('--precision', default='f32', help='f32 (the fp32 pair against the rocBLAS composite), or f16 / bf16 / a comma list with f32: the 16-bit path against fp32')
     args = ap.parse_args()
-    lines = ['# tools/bench_invert.py on %s' % torch.cuda.get_device_name(0)]
+    precs = args.precision.split(',')
+    assert all(p in ('f32', 'f16', 'bf16') for p in precs), precs
+    lines = ['# tools/bench_invert.py --precision %s on %s' % (args.precision, torch.cuda.get_device_name(0))]
+    if precs != ['f32']:
+        main16(precs, args, lines)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     for b in (1, 8):
         for ch, hw in TAPS:
             kernels_row(b, ch, hw, lines)
