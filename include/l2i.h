@@ -455,6 +455,16 @@ int l2i_nonfinite_flag_f32(const float* g, int64_t n, int32_t* state, void* stre
 int l2i_adam_guarded_f32(float* p, const float* g, float* m, float* v, float* step, int64_t n, float lr, float beta1, float beta2, float eps,
                          int32_t check_self, int32_t* state, float* scale, float growth, float backoff, int32_t interval, float max_scale,
                          int32_t last, void* stream);
+/* [ABI 12] The momentum-SGD twin (BP.py:140: torch.optim.SGD(lr, momentum), dampening 0, no Nesterov, no weight decay), same single 1024-thread block.
+ * With t = step[0] (a float counter on the device): t == 0: buf = g; otherwise buf = fl(fl(momentum * buf) + g); then p = fl(p - fl(lr * buf)) and
+ * step[0] = t + 1 — every product and sum rounded to float32 on its own, no contraction.  "First step" is read from the device, so a captured graph
+ * replays the call; a skipped first step leaves the counter at 0 and the next applied one initialises buf.  The guard is l2i_adam_guarded_f32's,
+ * word for word: SKIPPED — p, buf, step untouched — when state[L2I_LS_FOUND] is set or (check_self) g itself holds an inf / NaN (which then sets
+ * the flag for the next tensor); last != 0 advances the scale state as above and clears the flag; scale may be NULL.  Refused with L2I_E_ARG
+ * before any launch: a null p, g, buf, step or state, n <= 0, momentum outside [0, 1), lr negative or non-finite, a scale with growth < 1 or
+ * backoff outside (0, 1]. */
+int l2i_sgd_guarded_f32(float* p, const float* g, float* buf, float* step, int64_t n, float lr, float momentum, int32_t check_self, int32_t* state,
+                        float* scale, float growth, float backoff, int32_t interval, float max_scale, int32_t last, void* stream);
 
 /* [ABI 7] The regressor head and its BCE term in one launch (csrc/l2i_loss.hip) — transform_base.py:416-424: pred = fc(feat)[:, cols]; loss =
  * -mean(y log(max(pred, eps)) + (1 - y) log(max(1 - pred, eps))) (fp32 logs, float64 sum, like the torch expression on an fp32 pred and a float64 y).
@@ -519,8 +529,8 @@ int l2i_gram_bwd_h8_f16(void* g, const void* c, const float* D, const float* sca
 
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
- * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
-#define L2I_ABI_VERSION 11
+ * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins; 12: l2i_sgd_guarded_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */
+#define L2I_ABI_VERSION 12
 int l2i_abi_version(void);
 int l2i_sizeof_conv_params(void);       /* sizeof(struct l2i_conv_params) of THIS build */
 

@@ -117,6 +117,7 @@ _SIGNATURES = {
     'l2i_face_head_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_nonfinite_flag_f32': (c_i, [c_p, c_l, c_p, c_p]),
     'l2i_adam_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
+    'l2i_sgd_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
     'l2i_gram_loss_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_loss_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
@@ -131,7 +132,7 @@ _F16_TWINS = frozenset(k for k in _SIGNATURES if k.endswith('_h8') or k in ('l2i
 for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
-ABI_VERSION = 11         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
+ABI_VERSION = 12         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -82,7 +82,9 @@ def build_parser():
     p.add_argument('--synthetic_weights', action='store_true',
                    help='run on seeded random-init G / VGG-16 when the checkpoint paths of constants.py do not exist')
     p.add_argument('--precision', type=str, choices=['f32', 'f16', 'bf16'], default='f32',
-                   help='element type of the feature maps: f32, or the 16-bit h8 path with IEEE fp16 (loss-scaled, Adam only) or bf16 maps; latents and images are saved as fp32 either way')
+                   help='element type of the feature maps: f32, or the 16-bit h8 path with IEEE fp16 (loss-scaled; Adam only on the eager loop, Adam or GD with --hipgraph) or bf16 maps; latents and images are saved as fp32 either way')
+    p.add_argument('--hipgraph', action='store_true',
+                   help='replay the iteration (forward, backward, optimiser update, loss record) from one hipGraph per batch size; off: the eager loop')
     return p
 
 
@@ -118,7 +120,7 @@ def main(argv=None):
         constants.ALLOW_SYNTHETIC_WEIGHTS = True
     device = 'cuda'
     gen, vgg = load_networks(args.resolution, device, args.precision)
-    inv = Inverter(gen, vgg, lr=args.lr, optim=args.optimizer, batch=args.batch_size)
+    inv = Inverter(gen, vgg, lr=args.lr, optim=args.optimizer, batch=args.batch_size, capture=args.hipgraph)
     files = image_folder(args.path)
     os.makedirs(os.path.join(args.save_path, 'latent'), exist_ok=True)
     curve = np.zeros(0)

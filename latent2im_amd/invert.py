@@ -11,8 +11,13 @@ The 16-bit path: ``Inverter`` takes nets16.Generator with perceptual16.Vgg16Gram
 optim.LossScaler built from nets16.invert_scale_for and attached to both networks: the Gram branch multiplies the gradient it receives by its static
 exponent times the dynamic factor and hands the image gradient on divided by the static one, the fp32 pixel term's gradient is multiplied by the
 dynamic factor here, and the generator divides it out of the latent gradient.  The optimiser is then optim.GuardedAdam: an iteration whose
-gradient overflowed is skipped and the dynamic factor halves.  There is no guarded SGD, so fp16 with 'GD' is refused; bf16 needs no scale and
-takes both torch optimisers.
+gradient overflowed is skipped and the dynamic factor halves.  The eager loop has no guarded SGD, so there fp16 with 'GD' is refused; bf16 needs no
+scale and takes both torch optimisers.
+
+``capture=True`` replays the iteration from a hipGraph: forward, backward, the optimiser's update and the loss record are ONE ``graph.replay()``
+with no host read (the eager iteration is 157-160 library calls from Python and bound by them).  What makes the update replayable is that the
+guarded optimisers (optim.GuardedAdam, optim.GuardedSGD) keep their step counter on the device, so every precision takes them there, and fp16
+takes 'GD' as well.  One graph per batch size, recorded on the first ``invert`` of that size and refilled per image (``_Replay``).
 """
 import numpy as np
 import torch
@@ -44,17 +49,20 @@ class _PixelFn(torch.autograd.Function):
 class Inverter:
     """``Inverter(gen, vgg, lr, optim).invert(batch, n_loops, noise=None)`` -> (W+ [B, n_latent, 512], loss curve [n_loops])."""
 
-    def __init__(self, gen, vgg, lr=0.01, optim='Adam', n_mean_latent=4096, batch=1):
+    def __init__(self, gen, vgg, lr=0.01, optim='Adam', n_mean_latent=4096, batch=1, capture=False):
         assert optim in ('Adam', 'GD'), optim
         self.gen, self.vgg, self.lr, self.optim = gen, vgg, lr, optim
+        self.capture = bool(capture)
+        self.graphs = {}                                                       # batch size -> _Replay (capture=True)
         self.dtype = getattr(gen, 'dtype', torch.float32)                      # element type of the feature maps: both networks on the same path
         if getattr(vgg, 'dtype', torch.float32) != self.dtype:
             raise ValueError('generator maps are %s, VGG-16 maps %s: build both networks for one precision' % (self.dtype, getattr(vgg, 'dtype', torch.float32)))
         self.scaler = None
         if self.dtype == torch.float16:
-            if optim == 'GD':
+            if optim == 'GD' and not self.capture:
                 raise NotImplementedError('fp16 inversion needs an optimiser that skips an overflowed iteration; only Adam has one '
-                                          '(optim.GuardedAdam): there is no guarded SGD.  Use --optimizer Adam, or --precision bf16 / f32 with GD')
+                                          '(optim.GuardedAdam): there is no guarded SGD on the eager loop.  Use --optimizer Adam, --hipgraph (capture=True), '
+                                          'or --precision bf16 / f32 with GD')
             from . import nets16
             from .optim import LossScaler
             self.scaler = nets16.attach_scaler((gen, vgg), LossScaler(nets16.invert_scale_for(gen.size, batch), gen.device))
@@ -77,6 +85,8 @@ class Inverter:
         generator call draws it (BP.py:144).  ``w``: another starting point than the mean latent."""
         batch = batch.detach().contiguous().float()
         grams = self.vgg.target_grams(batch)
+        if self.capture:
+            return self._invert_replayed(batch, grams, n_loops, noise, w)
         w = (self.start_latent(batch.shape[0]) if w is None else w.detach().clone().contiguous()).requires_grad_()
         if self.scaler is not None:
             from .optim import GuardedAdam
@@ -95,3 +105,100 @@ class Inverter:
         self.last_image = None if out is None else out.detach()                   # the image of the last iteration's W+ BEFORE its update, as BP.py:168 saves it
         curve = torch.cat(curve).cpu().numpy().astype(np.float64) if curve else np.zeros(0)
         return w.detach(), curve
+
+    def _invert_replayed(self, batch, grams, n_loops, noise, w):
+        b = batch.shape[0]
+        start = self.start_latent(b) if w is None else w.detach()
+        r = self.graphs.get(b)
+        if r is not None and r.fixed_noise != (noise is not None):           # drawn or given noise is part of the recording
+            r = None
+        if r is None:
+            r = self.graphs[b] = _Replay(self, batch, grams, start, noise, n_loops)
+        else:
+            r.load(batch, grams, start, noise)
+        curve = r.run(n_loops)
+        self.last_image = r.out.detach().clone() if n_loops > 0 else None      # the image of the last iteration's W+ BEFORE its update, as eager
+        return r.w.detach().clone(), curve
+
+
+class _Replay:
+    """One inversion iteration of one batch size as a hipGraph, after capture.CapturedStep: synthesis, pixel term + VGG-16 Gram loss, backward, the
+    guarded optimiser's update, ``curve[idx] = loss`` and ``idx += 1`` on ONE stream.  Static inputs, refilled per image outside the graph: the
+    batch, its four target Grams, W+, the optimiser's buffers and step counter, the curve index and (when given) the noise maps; without a noise
+    list the maps are drawn inside the graph from torch's graph-safe Philox stream, fresh on every replay.  The fp16 scaler is the Inverter's and
+    carries over from image to image, as on the eager loop.  The warm-up before capture runs the loss and its backward only, never the update:
+    W+, the optimiser state and the scaler are what an eager run starts from."""
+
+    MIN_CAPACITY = 1024
+
+    def __init__(self, inv, batch, grams, start, noise, n_loops, warmup=2):
+        from . import conv
+        from .optim import GuardedAdam, GuardedSGD
+        self.fixed_noise = noise is not None
+        self.batch = batch.clone()
+        self.grams = [g.clone() for g in grams]
+        self.noise = None if noise is None else [None if t is None else t.detach().float().contiguous().clone() for t in noise]
+        self.w = start.clone().contiguous().requires_grad_()
+        if inv.optim == 'Adam':
+            self.opt = GuardedAdam([self.w], lr=inv.lr, betas=(0.5, 0.9), scaler=inv.scaler)      # BP.py:138
+        else:
+            self.opt = GuardedSGD([self.w], lr=inv.lr, momentum=0.9, scaler=inv.scaler)           # BP.py:140
+        self.opt.init_state()                                                  # state and guard words outside the graph's pool
+        self.capacity = max(int(n_loops), self.MIN_CAPACITY)
+        self.curve = torch.zeros(self.capacity, dtype=torch.float32, device=batch.device)
+        self.idx = torch.zeros(1, dtype=torch.int64, device=batch.device)
+        # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights), as stream capture requires
+        s = torch.cuda.Stream(device=batch.device)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(max(warmup, 1)):
+                self._forward_backward(inv)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self.opt.zero_grad(set_to_none=True)                                   # w.grad becomes a static tensor of the graph's pool
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            loss, self.out = self._forward_backward(inv)
+            self.opt.step()
+            self.curve.index_copy_(0, self.idx, loss.reshape(1))
+            self.idx += 1
+        # the graph's kernel nodes hold raw pointers into the split-K workspaces of conv._WS: they live as long as the graph
+        self._ws_keep = list(conv._WS.values())
+
+    def _forward_backward(self, inv):
+        """Loss and backward of one iteration -> (loss, image), both detached: no reference to the autograd graph survives the call.  One that did
+        would keep W+'s gradient accumulator on the warm-up's stream, and the capture would fork to that stream to run it."""
+        loss, out = inv.loss(self.w, self.batch, self.grams, self.noise)
+        self.w.grad = None
+        loss.backward()
+        return loss.detach(), out.detach()
+
+    @torch.no_grad()
+    def load(self, batch, grams, start, noise):
+        """Another image into the recorded graph: every static input refilled, the optimiser back at its first step."""
+        self.batch.copy_(batch)
+        for dst, src in zip(self.grams, grams):
+            dst.copy_(src)
+        self.w.copy_(start)
+        for st in self.opt.state.values():
+            for t in st.values():
+                t.zero_()
+        if self.noise is not None:
+            assert len(noise) == len(self.noise), (len(noise), len(self.noise))
+            for dst, src in zip(self.noise, noise):
+                if dst is not None:
+                    dst.copy_(src)
+
+    def run(self, n_loops):
+        """``n_loops`` replays -> the loss curve (float64 numpy).  The curve buffer is drained every ``capacity`` replays: the only host read."""
+        self.idx.zero_()
+        parts, filled = [], 0
+        for _ in range(n_loops):
+            if filled == self.capacity:
+                parts.append(self.curve.cpu())
+                self.idx.zero_()
+                filled = 0
+            self.graph.replay()
+            filled += 1
+        parts.append(self.curve[:filled].cpu())
+        return torch.cat(parts).numpy().astype(np.float64) if n_loops > 0 else np.zeros(0)

@@ -13,6 +13,8 @@ the only sync of the reference loop, and the hipGraph replay of config 5 has non
                   true gradient, or non-finite if anything overflowed on the way.
 ``GuardedAdam`` — torch.optim.Adam whose step() is one launch of l2i_adam_guarded_f32 per parameter tensor: finite check, update or skip,
                   scale-state update.  Same state layout as torch's (exp_avg, exp_avg_sq, step) so state_dict() round-trips.
+``GuardedSGD``  — torch.optim.SGD(lr, momentum) the same way on l2i_sgd_guarded_f32 (BP.py:140, the inversion's 'GD'): torch's momentum_buffer plus a
+                  device-side ``step`` that tells the kernel whether the buffer is still to be initialised, so a captured graph replays the step.
 """
 import torch
 
@@ -42,6 +44,50 @@ class LossScaler:
         return dict(scale=float(self.scale[0]), tracker=st[1], skipped=st[2], steps=st[3])
 
 
+def _guard_flags(self, device):
+    """(state words, scale pair or None) of a guarded optimiser: the scaler's, or four words of its own."""
+    if self.scaler is not None:
+        return self.scaler.state, self.scaler.scale
+    if self._own_state is None or self._own_state.device != device:
+        self._own_state = torch.zeros(4, dtype=torch.int32, device=device)
+    return self._own_state, None
+
+
+def _init_state(self):
+    """Allocate every parameter's state and the guard's own words now and not in the first step(): before a graph capture, whose pool they
+    must not come from."""
+    for group in self.param_groups:
+        for p in group['params']:
+            _check_param(p, type(self).__name__)
+            self._state_of(p)
+            self._flags(p.device)
+
+
+def _check_param(p, who):
+    if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or (p.grad is not None and p.grad.dtype != torch.float32):
+        raise _lib.L2IError('%s updates contiguous float32 GPU parameters only' % who)
+
+
+def _guarded_step(opt, todo, launch):
+    """The launches of one guarded step over ``todo`` = [(p, group, state)]: multi-tensor steps flag every gradient first, the last launch advances
+    the scale state.  ``launch(p, g, group, st, guard, stream)`` enqueues one update; ``guard`` is the entry point's tail from check_self to last."""
+    if not todo:
+        return None
+    state, scale = opt._flags(todo[0][0].device)
+    sc = opt.scaler
+    single = len(todo) == 1
+    stream = _lib.stream_ptr()
+    if not single:
+        for p, _, _ in todo:
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            _lib.call('l2i_nonfinite_flag_f32', _lib.fptr(g), g.numel(), _lib.ptr(state), stream=stream)
+    for i, (p, group, st) in enumerate(todo):
+        g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+        launch(p, g, group, st, (1 if single else 0, _lib.ptr(state), _lib.ptr(scale), float(sc.GROWTH if sc else 2.0), float(sc.BACKOFF if sc else 0.5),
+                                 int(sc.growth_interval if sc else 0), float(sc.max_scale if sc else 1.0), 1 if i == len(todo) - 1 else 0), stream)
+    return None
+
+
 class GuardedAdam(torch.optim.Adam):
     """torch.optim.Adam(params, lr, betas) for float32 CUDA parameters with the update on l2i_adam_guarded_f32: skipped as a whole when any gradient
     of the step is non-finite; ``scaler`` (a LossScaler or None) is advanced by the last launch of the step."""
@@ -51,12 +97,19 @@ class GuardedAdam(torch.optim.Adam):
         self.scaler = scaler
         self._own_state = None
 
-    def _flags(self, device):
-        if self.scaler is not None:
-            return self.scaler.state, self.scaler.scale
-        if self._own_state is None or self._own_state.device != device:
-            self._own_state = torch.zeros(4, dtype=torch.int32, device=device)
-        return self._own_state, None
+    _flags = _guard_flags
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if len(st) == 0:
+            st['step'] = torch.zeros((), dtype=torch.float32, device=p.device)
+            st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        elif not st['step'].is_cuda:                           # a state_dict saved by torch's own Adam keeps the counter on the host
+            st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
+        return st
+
+    init_state = _init_state
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -69,32 +122,59 @@ class GuardedAdam(torch.optim.Adam):
             for p in group['params']:
                 if p.grad is None:
                     continue
-                if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or p.grad.dtype != torch.float32:
-                    raise _lib.L2IError('GuardedAdam updates contiguous float32 GPU parameters only')
-                st = self.state[p]
-                if len(st) == 0:
-                    st['step'] = torch.zeros((), dtype=torch.float32, device=p.device)
-                    st['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                elif not st['step'].is_cuda:                           # a state_dict saved by torch's own Adam keeps the counter on the host
-                    st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
-                todo.append((p, group, st))
-        if not todo:
-            return None
-        state, scale = self._flags(todo[0][0].device)
-        sc = self.scaler
-        single = len(todo) == 1
-        stream = _lib.stream_ptr()
-        if not single:
-            for p, _, _ in todo:
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                _lib.call('l2i_nonfinite_flag_f32', _lib.fptr(g), g.numel(), _lib.ptr(state), stream=stream)
-        for i, (p, group, st) in enumerate(todo):
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                _check_param(p, 'GuardedAdam')
+                todo.append((p, group, self._state_of(p)))
+
+        def launch(p, g, group, st, guard, stream):
             b1, b2 = group['betas']
             _lib.call('l2i_adam_guarded_f32', _lib.fptr(p), _lib.fptr(g), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']),
-                      p.numel(), float(group['lr']), float(b1), float(b2), float(group['eps']), 1 if single else 0,
-                      _lib.ptr(state), _lib.ptr(scale), float(sc.GROWTH if sc else 2.0), float(sc.BACKOFF if sc else 0.5),
-                      int(sc.growth_interval if sc else 0), float(sc.max_scale if sc else 1.0),
-                      1 if i == len(todo) - 1 else 0, stream=stream)
-        return None
+                      p.numel(), float(group['lr']), float(b1), float(b2), float(group['eps']), *guard, stream=stream)
+        return _guarded_step(self, todo, launch)
+
+
+class GuardedSGD(torch.optim.SGD):
+    """torch.optim.SGD(params, lr, momentum) — dampening 0, no Nesterov, no weight decay: BP.py:140 — for float32 CUDA parameters with the update on
+    l2i_sgd_guarded_f32, guarded and scaled as GuardedAdam's.  State per parameter: torch's ``momentum_buffer`` and ``step``, a 0-dim float32 device
+    tensor (0: the next applied step sets the buffer to the gradient, as torch's first step does)."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, scaler=None):
+        super().__init__(params, lr=lr, momentum=momentum)
+        self.scaler = scaler
+        self._own_state = None
+
+    _flags = _guard_flags
+
+    def _state_of(self, p):
+        st = self.state[p]
+        buf = st.get('momentum_buffer')
+        if buf is None:
+            st['momentum_buffer'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st['step'] = torch.zeros((), dtype=torch.float32, device=p.device)
+        elif 'step' not in st:                                     # a state_dict saved by torch's own SGD: its buffer is already initialised
+            st['step'] = torch.ones((), dtype=torch.float32, device=p.device)
+        elif not st['step'].is_cuda:
+            st['step'] = st['step'].to(device=p.device, dtype=torch.float32)
+        if not st['momentum_buffer'].is_contiguous():
+            st['momentum_buffer'] = st['momentum_buffer'].contiguous()
+        return st
+
+    init_state = _init_state
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise NotImplementedError('GuardedSGD.step takes no closure (the reference calls optimizer.step() bare, BP.py:155)')
+        todo = []
+        for group in self.param_groups:
+            if group.get('nesterov', False) or group.get('dampening', 0) or group.get('weight_decay', 0) or group.get('maximize', False):
+                raise NotImplementedError('GuardedSGD: lr and momentum only (BP.py:140): no Nesterov, dampening, weight decay or maximize')
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                _check_param(p, 'GuardedSGD')
+                todo.append((p, group, self._state_of(p)))
+
+        def launch(p, g, group, st, guard, stream):
+            _lib.call('l2i_sgd_guarded_f32', _lib.fptr(p), _lib.fptr(g), _lib.fptr(st['momentum_buffer']), _lib.fptr(st['step']), p.numel(),
+                      float(group['lr']), float(group['momentum']), *guard, stream=stream)
+        return _guarded_step(self, todo, launch)

@@ -14,6 +14,12 @@
 (b) inversion iterations/s per precision at 256^2 (batch 1 and 8) and 1024^2 (batch 1), with the library calls of one iteration counted.
 
     python tools/bench_invert.py --precision f32,f16,bf16 --out profiles/invert16_bench.txt
+
+``--hipgraph`` times the replayed iteration (Inverter(capture=True)) against the eager loop of the same build instead: iterations/s per precision
+at the same three shapes, three alternating runs a side (5 warm-up calls, median of 20 calls of 10 iterations each), the ratio with all runs, and
+the library calls and graph launches of one iteration on each side.
+
+    python tools/bench_invert.py --precision f32,f16,bf16 --hipgraph --out profiles/invert_graph_bench.txt
 """
 import argparse
 import os
@@ -215,6 +221,57 @@ def step16_row(size, b, prec, lines, n=10):
     conv.PRECISION = 'f32'
 
 
+def count_replays(fn):
+    """hipGraph launches (torch.cuda.CUDAGraph.replay) made by one run of ``fn``."""
+    n = [0]
+    real = torch.cuda.CUDAGraph.replay
+
+    def replay(self):
+        n[0] += 1
+        return real(self)
+    torch.cuda.CUDAGraph.replay = replay
+    try:
+        fn()
+    finally:
+        torch.cuda.CUDAGraph.replay = real
+    return n[0]
+
+
+def graph_row(size, b, prec, lines, n=10):
+    """Iterations/s of the eager loop and of the replayed one (noise drawn per iteration on both), alternating, and what one iteration issues."""
+    from latent2im_amd import conv
+    from latent2im_amd.invert import Inverter
+    batch = torch.rand(b, 3, size, size, device='cuda') * 2 - 1
+    sides = {}
+    for name, cap in (('eager', False), ('replayed', True)):                 # a pair of networks a side: an fp16 Inverter attaches its scaler to them
+        gen, vgg = _networks(size, prec)
+        sides[name] = Inverter(gen, vgg, lr=0.01, optim='Adam', n_mean_latent=256, batch=b, capture=cap)
+    sides['replayed'].invert(batch, 1)                                       # the capture, outside every timing
+    runs = {k: [] for k in sides}
+    for _ in range(3):                                                       # alternating runs: the spread of each side is its run-to-run noise
+        for k, inv in sides.items():
+            runs[k].append(timed(lambda: inv.invert(batch, n)))
+    med = {k: statistics.median(v) for k, v in runs.items()}
+    its = {k: [n / v for v in vs] for k, vs in runs.items()}
+    ratios = [e / r for e, r in zip(runs['eager'], runs['replayed'])]        # replayed / eager in iterations/s, run by run
+    lo, hi = min(its['eager']) / max(its['eager']), max(its['eager']) / min(its['eager'])
+    r_lo, r_hi = min(its['replayed']) / max(its['replayed']), max(its['replayed']) / min(its['replayed'])
+    ratio = med['eager'] / med['replayed']
+    inside = lo * r_lo <= ratio <= hi * r_hi
+    calls, launches = {}, {}
+    for k, inv in sides.items():
+        calls[k] = (count_calls(lambda: inv.invert(batch, 3)) - count_calls(lambda: inv.invert(batch, 1))) // 2
+        launches[k] = (count_replays(lambda: inv.invert(batch, 3)) - count_replays(lambda: inv.invert(batch, 1))) // 2
+    lines.append('%-4s inversion %4d^2  batch %d   eager %7.2f it/s (%.2f ms; runs %s)   replayed %7.2f it/s (%.2f ms; runs %s)   replayed / eager %.2f (runs %s)%s'
+                 '   per iteration: eager %d library calls + %d graph launches, replayed %d + %d%s'
+                 % (prec, size, b, n / med['eager'], 1e3 * med['eager'] / n, ' '.join('%.2f' % v for v in its['eager']), n / med['replayed'],
+                    1e3 * med['replayed'] / n, ' '.join('%.2f' % v for v in its['replayed']), ratio, ' '.join('%.2f' % v for v in ratios),
+                    '  INSIDE the two sides\' spread' if inside else '', calls['eager'], launches['eager'], calls['replayed'], launches['replayed'],
+                    '' if sides['replayed'].scaler is None else '   scaler %s' % sides['replayed'].scaler.stats()))
+    print(lines[-1], flush=True)
+    conv.PRECISION = 'f32'
+
+
 def main16(precs, args, lines):
     for prec in [p for p in precs if p != 'f32']:
         for b in (1, 8):
@@ -233,10 +290,23 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--skip_step', action='store_true')
     ap.add_argument('--precision', default='f32', help='f32 (the fp32 pair against the rocBLAS composite), or f16 / bf16 / a comma list with f32: the 16-bit path against fp32')
+    ap.add_argument('--hipgraph', action='store_true', help='iterations/s of the replayed iteration (Inverter(capture=True)) against the eager loop')
+    ap.add_argument('--shapes', default='256x1,256x8,1024x1', help='--hipgraph: comma list of SIZExBATCH')
     args = ap.parse_args()
     precs = args.precision.split(',')
     assert all(p in ('f32', 'f16', 'bf16') for p in precs), precs
-    lines = ['# tools/bench_invert.py --precision %s on %s' % (args.precision, torch.cuda.get_device_name(0))]
+    lines = ['# tools/bench_invert.py --precision %s%s on %s' % (args.precision, ' --hipgraph' if args.hipgraph else '', torch.cuda.get_device_name(0))]
+    if args.hipgraph:
+        lines.append('# eager = Inverter(capture=False), replayed = Inverter(capture=True): HIP events around invert(batch, 10), 5 warm-up calls, median of 20, '
+                     'three alternating runs a side; ms = per iteration')
+        shapes = [tuple(int(v) for v in t.split('x')) for t in args.shapes.split(',')]
+        for size, b in shapes:
+            for prec in precs:
+                graph_row(size, b, prec, lines)
+                if args.out:                                                 # row by row: a long run leaves what it measured
+                    with open(args.out, 'w') as f:
+                        f.write('\n'.join(lines) + '\n')
+        return
     if precs != ['f32']:
         main16(precs, args, lines)
         if args.out:
