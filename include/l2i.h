@@ -527,6 +527,23 @@ int l2i_gram_bwd_h8(void* g, const void* c, const float* D, const float* scale, 
 int l2i_gram_bwd_h8_f16(void* g, const void* c, const float* D, const float* scale, float coef, int B, int C, int HW, int accumulate, int scale_stride,
                         void* stream);
 
+/* PixelNorm + LeakyReLU of the PGGAN-256 generator on 16-bit h8 maps (csrc/l2i_pggan_h8.hip; bf16 elements, and IEEE fp16 with the suffix _f16;
+ * additive to ABI 12).  x [B][C/8][H][W][8]; the function, eps and slope of l2i_pixelnorm_act_f32 / _bwd_f32; the mean divides by C.
+ * l2i_pixelnorm_act_h8: up = 1: y is shaped like x.  up = 2: y is [B][C/8][2H][2W][8] and every result is written to its four positions (the
+ *   nearest 2x upsample that follows every block but the last).  y_low (may be NULL): the 1x map as well, bit-identical to y where they coincide.
+ * l2i_pixelnorm_act_bwd_h8: dx = r g' - x r^3 sum_c(g' x) / C with r = 1 / sqrt(mean_c x^2 + eps), g' = g (x > 0 ? 1 : slope); pool = 1: g = gy
+ *   (shaped like x); pool = 2: gy is [B][C/8][2H][2W][8] and g is the fp32 sum of its 2x2 window (the upsample's adjoint; no pooled map is
+ *   stored).  addend (may be NULL; h8, shaped like x) is added to g in fp32.
+ * Both: fp32 arithmetic, one rounding at the store, fixed summation order (no atomics: equal inputs give equal bits).  An all-zero column gives
+ * y = 0 and dx = g' / sqrt(eps).  C % 8 != 0, C > 512 or up / pool outside {1, 2} return L2I_E_UNSUPPORTED; a NULL y, x, dx or gy, a
+ * non-positive dimension or a map off a 16-byte boundary returns L2I_E_ARG; nothing is launched then. */
+int l2i_pixelnorm_act_h8(void* y, void* y_low, const void* x, int B, int C, int H, int W, float eps, float slope, int up, void* stream);
+int l2i_pixelnorm_act_h8_f16(void* y, void* y_low, const void* x, int B, int C, int H, int W, float eps, float slope, int up, void* stream);
+int l2i_pixelnorm_act_bwd_h8(void* dx, const void* gy, const void* x, const void* addend, int B, int C, int H, int W, float eps, float slope, int pool,
+                             void* stream);
+int l2i_pixelnorm_act_bwd_h8_f16(void* dx, const void* gy, const void* x, const void* addend, int B, int C, int H, int W, float eps, float slope, int pool,
+                                 void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
  * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins; 12: l2i_sgd_guarded_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */

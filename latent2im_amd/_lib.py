@@ -122,6 +122,8 @@ _SIGNATURES = {
     'l2i_gram_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_loss_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'l2i_pixelnorm_act_h8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p]),
+    'l2i_pixelnorm_act_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
     'l2i_sizeof_conv_params': (c_i, []),

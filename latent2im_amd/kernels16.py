@@ -1,4 +1,4 @@
-"""Python call wrappers for the streaming kernels of the 16-bit path (csrc/l2i_stream_h8.hip, include/l2i.h): bf16 tensors in the
+"""Python call wrappers for the streaming kernels of the 16-bit path (csrc/l2i_stream_h8.hip, l2i_gram_h8.hip, l2i_pggan_h8.hip; include/l2i.h): bf16 tensors in the
 channel-blocked h8 layout [B, C/8, H, W, 8] in, out; fp32 for images, noise, bias, per-sample vectors and reductions.  No autograd here."""
 import ctypes
 
@@ -165,6 +165,31 @@ def gram_bwd(c, d, scale=None, out=None, accumulate=False, coef=None):
     _lib.call('l2i_gram_bwd_h8', _h8(out), _h8(c), _lib.fptr(d), _lib.fptr(scale), float(4.0 * ch / hw if coef is None else coef),
               b, ch, hw, int(bool(accumulate)), int(per_sample), dtype=c.dtype)
     return out
+
+
+def pixelnorm_act(x, slope, up=1, low=False, eps=1e-8):
+    """l2i_pixelnorm_act_h8: lrelu(x / sqrt(mean_c x^2 + eps), slope) on an h8 map (PGGAN's PixelNorm + LeakyReLU).  ``up`` = 2 writes every result
+    to its four positions of the [B, C/8, 2H, 2W, 8] map (the nearest upsample that follows the block); ``low`` returns (y, the 1x map) from
+    the same pass."""
+    B, G8, H, W, _ = x.shape
+    up = int(up)
+    y = torch.empty(B, G8, max(up, 1) * H, max(up, 1) * W, 8, device=x.device, dtype=x.dtype)
+    y_low = torch.empty_like(x) if low else None
+    _lib.call('l2i_pixelnorm_act_h8', _lib.ptr(y), _lib.ptr(y_low), _h8(x), B, G8 * 8, H, W, float(eps), float(slope), up, dtype=x.dtype)
+    return (y, y_low) if low else y
+
+
+def pixelnorm_act_bwd(gy, x, slope, pool=1, addend=None, eps=1e-8):
+    """l2i_pixelnorm_act_bwd_h8: dx of the above given the saved pre-norm map ``x``.  ``pool`` = 2: ``gy`` is the [B, C/8, 2H, 2W, 8] gradient of the
+    upsampled map, its 2x2 windows are summed while it is read; ``addend`` (h8, shaped like x) is added to that sum."""
+    B, G8, H, W, _ = x.shape
+    pool = int(pool)
+    assert tuple(gy.shape) == (B, G8, max(pool, 1) * H, max(pool, 1) * W, 8) and gy.dtype == x.dtype, (gy.shape, x.shape, pool)
+    assert addend is None or (addend.shape == x.shape and addend.dtype == x.dtype)
+    dx = torch.empty_like(x)
+    _lib.call('l2i_pixelnorm_act_bwd_h8', _lib.ptr(dx), _h8(gy), _h8(x), None if addend is None else _h8(addend), B, G8 * 8, H, W, float(eps), float(slope), pool,
+              dtype=x.dtype)
+    return dx
 
 
 def add_zero_insert(y, c, mask=None):

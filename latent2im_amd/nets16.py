@@ -90,6 +90,17 @@ def loss_scale_for(resolution, batch):
 F16_SCALE_BASE = dict(R=14, V=26, D=16, G=12)
 F16_SCALE_RES = dict(R=2, V=2, D=0, G=0)
 F16_D_BLOCK_GAIN = 2.0
+# The PGGAN-256 generator's G exponent at 256^2, batch 1 (pggan_scale_for).  Measured on the float32 CPU oracle with autograd hooks on every map the
+# generator stores a gradient for (tools/probe_pggan16.py, profiles/pggan16_gradient_ranges.txt; synthetic weights, one attribute): the largest map
+# of the config-1 step is the 4^2 end's, 2^-11.5 / 2^-12.4 / 2^-13.3 / 2^-14.2 at batch 1 / 2 / 4 / 8: it falls 0.9 octaves per doubling of the batch, so
+# the data alone give 5 - round(.) = 17 / 17 / 18 / 19.  The table is NOT fitted to that: it keeps loss_scale_for's form, BASE + lb = 17 / 18 / 19 / 20,
+# one exponent rule for every branch of a graph.  That is deliberately up to one octave above the data for every batch above 1: the largest map
+# sits at 2^5.5 / 2^5.6 / 2^5.7 / 2^5.8, ten octaves under fp16's largest number, and the extra octave goes to the small end (the smallest map's
+# median, 2^-22 .. 2^-25, is stored at 2^-5 .. 2^-6: normal numbers throughout).  A GPU pass with PROBE on (tools/probe_pggan16.py --gpu, same
+# file) confirms the figures on the stored h8 maps.  The in-repo generator exists at 256^2 only (constants.PG_RESOLUTION): no other resolution
+# was measured, and none is extrapolated (RES = 0).
+F16_PG_SCALE_BASE = 17
+F16_PG_SCALE_RES = 0
 
 
 def invert_scale_for(resolution, batch):
@@ -662,3 +673,165 @@ class _Synthesis16Fn(torch.autograd.Function):
         if _dyn(gen) is not None:
             g_lat = g_lat * _dyn(gen, inverse=True)
         return g_lat, None, None
+
+
+# =====================================================================================================================================
+# PGGAN-256 generator (pggan.py; BASELINE config 1)
+# =====================================================================================================================================
+PG_MIN_CHANNELS = 32        # H8Conv reads its input in 32-channel chunks: block 8 (32 -> 16 -> 16 channels) is not built
+
+
+def pggan_scale_for(resolution, batch):
+    """log2 of the STATIC gradient scales of the fp16 config-1 step (pggan.TransformGraph) at a ``resolution``^2 generator output and PER-GPU ``batch``:
+    R and V by loss_scale_for at the HALF resolution the regressor and VGG-19 see (get_logits halves the image), G by the same rule — the branch's
+    largest gradient map near 2^5 — from the magnitudes tools/probe_pggan16.py measured on the float32 CPU oracle
+    (profiles/pggan16_gradient_ranges.txt).  L2I_F16_SCALES overrides all of them, as in loss_scale_for."""
+    if os.environ.get('L2I_F16_SCALES'):
+        return loss_scale_for(resolution, batch)
+    out = loss_scale_for(max(resolution // 2, 1), batch)
+    lb = int(round(math.log2(max(batch, 1))))
+    lr = int(round(math.log2(resolution)))
+    out['G'] = F16_PG_SCALE_BASE + lb + F16_PG_SCALE_RES * (lr - 8)
+    return out
+
+
+class _PGConv16:
+    """EqualConv2d (model_256.py:53-68,96-104) on the 16-bit path: weight_orig * sqrt(2 / fan_in) rounded to the element type, fp32 bias; frozen."""
+
+    def __init__(self, P, name, padding, device):
+        w = torch.as_tensor(np.asarray(P[name + '.conv.weight_orig']), dtype=torch.float32)
+        fan_in = w.shape[1] * w.shape[2] * w.shape[3]
+        self.conv = C.H8Conv(w * math.sqrt(2.0 / fan_in), stride=1, padding=padding, device=device)
+        self.bias = _t(P[name + '.conv.bias'], device)
+
+
+class PGGenerator:
+    """pggan.Generator (the frozen ``model_256.Generator(511, 1)``) on h8 maps: ``netG(z511, step=6, alpha=0)`` -> fp32 [B, 3, 4 * 2**step, 4 * 2**step].
+    Same constructor, call contract and restructurings as the fp32 class (to_rgb before the upsample it commutes with; the block that alpha = 0
+    multiplies by zero is not evaluated).  The latent side (code_norm, the GEMM of the 4x4 stage) and the image side (to_rgb's output, the
+    nearest upsample / pooling / blend of 3-channel images) stay fp32; every map between them is h8, and PixelNorm + LeakyReLU, the nearest
+    upsample after it and that upsample's adjoint are csrc/l2i_pggan_h8.hip.  Steps whose maps have fewer than 32 channels (step 8) raise."""
+
+    def __init__(self, state, device='cuda'):
+        from .pggan import PG_CHANNELS
+        P = state
+        self.device = device
+        self.dtype = K16.h8_dtype()
+        self.channels = PG_CHANNELS
+        self.label = _t(P['label_embed.weight'], device)[0:1]
+        self.code_dim = 512 - self.label.shape[1]
+        w0 = torch.as_tensor(np.asarray(P['progression.0.conv.0.conv.weight_orig']), dtype=torch.float32)
+        w0 = w0 * math.sqrt(2.0 / (w0.shape[1] * 16))
+        self.w0 = torch.flip(w0, [2, 3]).permute(1, 0, 2, 3).reshape(w0.shape[1], -1).contiguous().to(device)       # pggan.Generator: the 4x4 stage is one GEMM
+        self.b0 = _t(P['progression.0.conv.0.conv.bias'], device)
+        self.n_blocks = len(PG_CHANNELS)
+        self.convs, self.rgb = [], []
+        for i, (cin, cout) in enumerate(PG_CHANNELS):
+            if min(cin, cout) < PG_MIN_CHANNELS:
+                self.convs.append(None)
+                self.rgb.append(None)
+                continue
+            first = None if i == 0 else _PGConv16(P, 'progression.%d.conv.0' % i, 1, device)
+            self.convs.append((first, _PGConv16(P, 'progression.%d.conv.3' % i, 1, device)))
+            self.rgb.append((C.H8Conv(np.asarray(P['to_rgb.%d.weight' % i]), 1, 0, device=device), _t(P['to_rgb.%d.bias' % i], device)))
+
+    def __call__(self, input, label=None, step=6, alpha=0):
+        if not 0 <= step < self.n_blocks:
+            raise IndexError('step %r outside the %d progression blocks' % (step, self.n_blocks))
+        if input.shape[1] != self.code_dim:
+            raise RuntimeError('model_256.Generator(%d, %d) takes a %d-d code, got %d' % (self.code_dim, self.label.shape[1], self.code_dim, input.shape[1]))
+        if any(self.convs[i] is None for i in range(step + 1)):
+            raise NotImplementedError('step %d has maps of fewer than %d channels: the 16-bit convs read 32-channel chunks (the graph runs step 6; use '
+                                      '--precision f32 beyond step 7)' % (step, PG_MIN_CHANNELS))
+        return _PG16Fn.apply(input, self, int(step), float(alpha))
+
+    def eval(self):
+        return self
+
+
+class _PG16Fn(torch.autograd.Function):
+    """pggan._PGFn on h8 maps.  Saved for the backward: the two pre-norm maps of every block, in h8."""
+
+    @staticmethod
+    def forward(ctx, z, gen, step, alpha):
+        keep = z.requires_grad
+        zc = z.detach().contiguous()
+        B = zc.shape[0]
+        code = K.pixelnorm_act(zc, slope=1.0)                                       # code_norm (model_256.py:230), fp32
+        x = torch.cat([code, gen.label.expand(B, -1)], 1)
+        blend = step > 0 and 0 <= alpha < 1
+        last = step - 1 if (blend and alpha == 0) else step
+        two = blend and alpha != 0                                                 # block last - 1's output feeds to_rgb[step - 1] at 1x and block `last` at 2x
+        saved = []
+        out = prev = None
+        for i in range(last + 1):
+            if i == 0:
+                a1 = K16.cast_to_h8(torch.addmm(gen.b0.repeat_interleave(16), x, gen.w0).reshape(B, -1, 4, 4), dtype=gen.dtype)
+            else:
+                a1 = gen.convs[i][0].conv.forward(out, bias=gen.convs[i][0].bias)    # `out`: the previous block's output, already upsampled
+            h1 = K16.pixelnorm_act(a1, 0.2)
+            a2 = gen.convs[i][1].conv.forward(h1, bias=gen.convs[i][1].bias)
+            del h1
+            if i == last:
+                out = K16.pixelnorm_act(a2, 0.2)
+            elif two and i == last - 1:
+                out, prev = K16.pixelnorm_act(a2, 0.2, up=2, low=True)
+            else:
+                out = K16.pixelnorm_act(a2, 0.2, up=2)
+            saved.append((a1, a2) if keep else None)
+            if PROBE is not None:
+                _probe('PG.fwd.a2@%d' % a2.shape[2], a2)
+        rgb = lambda i, t: gen.rgb[i][0].forward(t, bias=gen.rgb[i][1], out_f32=True)
+        if not blend:
+            img = rgb(step, out)
+        elif alpha == 0:
+            img = K.upsample2x_nearest(rgb(step - 1, out))                          # to_rgb commutes with the nearest upsample
+        else:
+            img = K.axpby(K.upsample2x_nearest(rgb(step - 1, prev)), rgb(step, out), 1.0 - alpha, alpha)
+        ctx.gen, ctx.step, ctx.alpha, ctx.blend, ctx.last = gen, step, alpha, blend, last
+        ctx.saved = saved if keep else None
+        ctx.zc = zc if keep else None
+        return img
+
+    @staticmethod
+    def backward(ctx, g_img):
+        gen, step, alpha, saved = ctx.gen, ctx.step, ctx.alpha, ctx.saved
+        if saved is None:
+            raise RuntimeError('the generator was run without a differentiable latent')
+        S = _gs(gen, 'G')
+        g_img = g_img.contiguous() * S if S != 1.0 else g_img.contiguous()           # (the dynamic factor came in with the loss branches' gradients)
+        B = g_img.shape[0]
+        hw = lambda t: (t.shape[2], t.shape[3])
+        # the to_rgb gradient: the fp32 image gradient as a 32-channel h8 map (3 real channels), one 1x1 conv with the transposed weights
+        rgb_bwd = lambda i, g32, like: gen.rgb[i][0].dgrad(K16.cast_to_h8(g32, cpad=gen.rgb[i][0].coutp_in, dtype=gen.dtype), hw(like))
+        g_prev = None                                                               # gradient reaching block `last - 1`'s output through the skip branch
+        if not ctx.blend:
+            g = rgb_bwd(step, g_img, saved[-1][1])
+        elif alpha == 0:
+            g = rgb_bwd(step - 1, K.pool2x2(g_img, 1.0), saved[-1][1])
+        else:
+            g = rgb_bwd(step, K.axpby(g_img, None, alpha, 0.0), saved[-1][1])
+            g_prev = rgb_bwd(step - 1, K.pool2x2(g_img, 1.0 - alpha), saved[-2][1])
+        _probe('PG.g_out@%d' % g.shape[2], g)
+        for i in range(ctx.last, -1, -1):
+            a1, a2 = saved[i]
+            if i == ctx.last:
+                g = K16.pixelnorm_act_bwd(g, a2, 0.2)
+            else:                                                                   # g: the gradient of the UPSAMPLED output; its 2x2 sums (+ the skip branch's) inside the kernel
+                g = K16.pixelnorm_act_bwd(g, a2, 0.2, pool=2, addend=g_prev if i == ctx.last - 1 else None)
+            _probe('PG.g_a2@%d' % g.shape[2], g)
+            g = gen.convs[i][1].conv.dgrad(g, hw(a1))
+            g = K16.pixelnorm_act_bwd(g, a1, 0.2)
+            _probe('PG.g_a1@%d' % g.shape[2], g)
+            if i == 0:
+                g_x = torch.mm(K16.cast_from_h8(g).reshape(B, -1), gen.w0.t())       # [B, 512]: code (511) | label embedding (frozen)
+                break
+            g = gen.convs[i][0].conv.dgrad(g, hw(a1))
+            saved[i] = None
+        g_z = K.pixelnorm_act_bwd(g_x[:, :gen.code_dim].contiguous(), ctx.zc, slope=1.0)
+        if S != 1.0:
+            g_z = g_z * (1.0 / S)
+        if _dyn(gen) is not None:
+            g_z = g_z * _dyn(gen, inverse=True)
+        ctx.saved = ctx.zc = None
+        return g_z, None, None, None

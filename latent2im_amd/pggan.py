@@ -202,8 +202,24 @@ def load_networks(device, need_vgg=True):
         else:
             v_state = synth.vgg19_prefix_state(seed=constants.SYNTH_SEED_V)
             src['V'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_V
-        vgg = VGG19Prefix(v_state, device=device)
-    return Generator(g_state, device=device), ResNet50(r_state, device=device), vgg, src
+    if C.PRECISION in C.H8_PRECISIONS:                                  # the 16-bit path: h8 feature maps, 16-bit MFMA with fp32 accumulation (nets16.py)
+        from . import nets16
+        GenCls, RegCls, VggCls = nets16.PGGenerator, nets16.ResNet50, nets16.VGG19Prefix
+    else:
+        GenCls, RegCls, VggCls = Generator, ResNet50, VGG19Prefix
+    src['precision'] = C.PRECISION
+    if need_vgg:
+        vgg = VggCls(v_state, device=device)
+    nets = GenCls(g_state, device=device), RegCls(r_state, device=device), vgg
+    if C.PRECISION == 'f16':
+        # gradient scales of the fp16 path (nets16.pggan_scale_for): static exponents for the PER-RANK batch — every rank's losses are means over
+        # its own shard — times one dynamic factor on the device; one scaler per graph, carried by its three networks (graph.load_networks)
+        from . import optim
+        per_rank = max(constants.BATCH_SIZE // dist.world_size(), 1)
+        scaler = optim.LossScaler(nets16.pggan_scale_for(constants.PG_RESOLUTION, per_rank), device, growth_interval=constants.LOSS_SCALE_GROWTH_INTERVAL)
+        nets16.attach_scaler(nets, scaler)
+        src['loss_scale_log2'] = dict(scaler.log2)
+    return nets + (src,)
 
 
 class TransformGraph:
@@ -241,7 +257,13 @@ class TransformGraph:
             self.walk = WalkLinearZ_free(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
         else:
             raise NotImplementedError('WalkMlpZ3 ("MLP", transform_base.py:279-283) is not on the config-1 path')
-        self.optimizer = torch.optim.Adam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99))
+        self.loss_scaler = getattr(netG, 'scaler', None)                # fp16 elements: the gradient scales the three networks share (load_networks)
+        if self.loss_scaler is not None:
+            from . import optim
+            # a non-finite walk gradient skips the update and halves the dynamic scale, on the device (graph.TransformGraph does the same)
+            self.optimizer = optim.GuardedAdam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99), scaler=self.loss_scaler)
+        else:
+            self.optimizer = torch.optim.Adam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99))
         self.walk_type = walk_type
         self.N_f = N_f
         self.eps = eps

@@ -1,0 +1,190 @@
+"""Timing of BASELINE config 1 (the PGGAN-256 z-walk step) per precision on one GPU, in tools/bench_invert.py's protocol: HIP events, 5 warm-up
+calls, median of 20, three alternating runs a side.
+
+(a) l2i_pixelnorm_act_h8 / l2i_pixelnorm_act_bwd_h8 at the generator's own shapes (step 6, alpha 0: blocks 0 .. 5, C x H = 512 x 4, 512 x 8,
+    512 x 16, 512 x 32, 256 x 64, 128 x 128), batch 4 and 8, the four variants the generator launches (forward 1x and with the fused 2x upsample,
+    backward 1x and with the fused 2x2 window sum), on inputs rotated through more than the last-level cache holds; GB/s of the least traffic
+    (every operand once, two bytes an element) against 6.3 TB/s achievable.
+(b) pggan.walk_training_step at 256^2, batch 4 and 8, f32 (the fp32 classes) / f16 / bf16, with and without the content term, synthetic
+    weights: ms per step with all runs, the ratio to f32 and whether it lies inside the two sides' spread, the library calls of one step, and the
+    three parts a step is made of timed alone (generator forward, regressor forward, one generator forward + backward) to say what holds a leg.
+
+    python tools/bench_pggan.py [--out profiles/pggan16_bench.txt] [--skip_step] [--skip_kernels]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM = 6.3e12
+MAPS = ((512, 4), (512, 8), (512, 16), (512, 32), (256, 64), (128, 128))
+PRECS = ('f32', 'f16', 'bf16')
+
+
+def timed(fn, warmup=5, reps=20):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return statistics.median(ts)
+
+
+def count_calls(fn):
+    """Library entry-point calls (latent2im_amd._lib.call and the conv launches) made by one run of ``fn``."""
+    from latent2im_amd import _lib, conv
+    n = [0]
+    real_call, real_launch = _lib.call, conv._launch
+
+    def call(*a, **k):
+        n[0] += 1
+        return real_call(*a, **k)
+
+    def launch(*a, **k):
+        n[0] += 1
+        return real_launch(*a, **k)
+    _lib.call, conv._launch = call, launch
+    try:
+        fn()
+    finally:
+        _lib.call, conv._launch = real_call, real_launch
+    return n[0]
+
+
+def kernel_rows(b, ch, hw, prec, lines):
+    """The four launches of one map shape; cold inputs (each operand rotates through > 512 MiB, twice the last-level cache)."""
+    from latent2im_amd import kernels16 as K16
+    dtype = torch.float16 if prec == 'f16' else torch.bfloat16
+    n = b * ch * hw * hw
+
+    def rot(shape_n, make):
+        copies = max(3, min(256, -(-(512 << 20) // (shape_n * 2))))
+        return [make() for _ in range(copies)]
+    x = rot(n, lambda: torch.randn(b, ch // 8, hw, hw, 8, device='cuda').to(dtype))
+    g1 = rot(n, lambda: torch.randn(b, ch // 8, hw, hw, 8, device='cuda').to(dtype))
+    g2 = rot(4 * n, lambda: torch.randn(b, ch // 8, 2 * hw, 2 * hw, 8, device='cuda').to(dtype))
+    turn = [0]
+
+    def nxt(pool):
+        turn[0] += 1
+        return pool[turn[0] % len(pool)]
+    cases = (('fwd up 1', 2 * n, lambda: K16.pixelnorm_act(nxt(x), 0.2)),
+             ('fwd up 2', 5 * n, lambda: K16.pixelnorm_act(nxt(x), 0.2, up=2)),
+             ('bwd pool 1', 3 * n, lambda: K16.pixelnorm_act_bwd(nxt(g1), nxt(x), 0.2)),
+             ('bwd pool 2', 6 * n, lambda: K16.pixelnorm_act_bwd(nxt(g2), nxt(x), 0.2, pool=2)))
+    for name, elems, fn in cases:
+        runs = [timed(fn) for _ in range(3)]
+        m = statistics.median(runs)
+        lines.append('%-4s B %d  C %3d  %3d^2  %-10s %8.1f us (runs %s)  %6.0f GB/s = %4.1f %% of 6.3 TB/s'
+                     % (prec, b, ch, hw, name, m * 1e6, ' '.join('%.1f' % (v * 1e6) for v in runs), 2.0 * elems / m / 1e9, 100 * 2.0 * elems / m / HBM))
+        print(lines[-1], flush=True)
+
+
+def _graph(prec, batch):
+    from latent2im_amd import constants, conv
+    from latent2im_amd import pggan as pg
+    conv.PRECISION, constants.ALLOW_SYNTHETIC_WEIGHTS, constants.BATCH_SIZE = prec, True, batch
+    np.random.seed(0)
+    return pg.faceGraph(lr=1e-3, walk_type='linear', loss='l2', trainEmbed=False, attrList=['Smiling'], attrTable={'Smiling': 31}, layers=None, pgan_opts=None)
+
+
+def step_rows(batch, lines):
+    from latent2im_amd import conv, synth
+    from latent2im_amd import pggan as pg
+    graphs = {p: _graph(p, batch) for p in PRECS}
+    z = torch.Tensor(synth.z_sample(batch, seed=0)).cuda()
+    ad = torch.full((batch, 1), 0.3, device='cuda')
+
+    def side(p, fn):
+        def run():
+            conv.PRECISION = p
+            return fn(graphs[p])
+        return run
+    for content in (True, False):
+        step = lambda g: pg.walk_training_step(g, z, ad, no_content_loss=not content)
+        runs = {p: [] for p in PRECS}
+        for _ in range(3):                                                   # alternating runs: the spread of each side is its run-to-run noise
+            for p in PRECS:
+                runs[p].append(timed(side(p, step)))
+        med = {p: statistics.median(v) for p, v in runs.items()}
+        calls = {p: count_calls(side(p, step)) for p in PRECS}
+        for p in PRECS:
+            row = '%-4s step 256^2  batch %d  %-15s %8.2f ms (runs %s)   %d library calls' % (
+                p, batch, 'content on' if content else 'content off', 1e3 * med[p], ' '.join('%.2f' % (1e3 * v) for v in runs[p]), calls[p])
+            if p != 'f32':
+                ratio = med['f32'] / med[p]
+                lo = min(runs['f32']) / max(runs['f32']) * min(runs[p]) / max(runs[p])
+                hi = max(runs['f32']) / min(runs['f32']) * max(runs[p]) / min(runs[p])
+                row += '   f32 / %s %.3f%s' % (p, ratio, "  INSIDE the two sides' spread" if lo <= ratio <= hi else '')
+                sc = graphs[p].loss_scaler
+                row += '' if sc is None else '   scaler %s' % sc.stats()
+            lines.append(row)
+            print(row, flush=True)
+    # the parts of a step alone: what holds a leg that is not faster
+    zg = z.clone().requires_grad_(True)
+
+    def gen_both(g):
+        zg.grad = None
+        g.get_logits({'z': zg}).sum().backward()
+    with torch.no_grad():
+        x0 = {p: side(p, lambda g: g.get_logits({'z': z}))() for p in PRECS}
+    parts = (('generator forward (no grad)', lambda g: _nograd(lambda: g.get_logits({'z': z}))),
+             ('generator forward + backward', gen_both),
+             ('regressor forward (no grad)', None))
+    for name, fn in parts:
+        for p in PRECS:
+            f = side(p, fn) if fn is not None else side(p, lambda g, p=p: _nograd(lambda: g.get_reg_preds(x0[p])))
+            runs_p = [timed(f) for _ in range(3)]
+            lines.append('%-4s part 256^2  batch %d  %-30s %8.2f ms (runs %s)   %d library calls'
+                         % (p, batch, name, 1e3 * statistics.median(runs_p), ' '.join('%.2f' % (1e3 * v) for v in runs_p), count_calls(f)))
+            print(lines[-1], flush=True)
+    conv.PRECISION = 'f32'
+
+
+def _nograd(fn):
+    with torch.no_grad():
+        return fn()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--skip_step', action='store_true')
+    ap.add_argument('--skip_kernels', action='store_true')
+    args = ap.parse_args()
+    lines = ['# tools/bench_pggan.py on %s' % torch.cuda.get_device_name(0),
+             '# HIP events, 5 warm-up calls, median of 20, three alternating runs a side; kernels: cold inputs (> 512 MiB rotated per operand), GB/s of '
+             'the least traffic (every operand once, two bytes an element)']
+
+    def flush():
+        if args.out:                                                         # section by section: a long run leaves what it measured
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+    if not args.skip_step:
+        for batch in (4, 8):
+            step_rows(batch, lines)
+            flush()
+            torch.cuda.empty_cache()
+    if not args.skip_kernels:
+        for prec in ('f16', 'bf16'):
+            for b in (4, 8):
+                for ch, hw in MAPS:
+                    kernel_rows(b, ch, hw, prec, lines)
+                flush()
+    flush()
+
+
+if __name__ == '__main__':
+    main()
