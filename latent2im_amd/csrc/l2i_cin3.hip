@@ -14,6 +14,7 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_epilogue.h"
 
 
 namespace c3 {
@@ -110,33 +111,15 @@ __global__ __launch_bounds__(256, 3) void conv_cin3_kernel(const l2i_conv_params
             const int ch = it * 8 + chl, co = m0 + ch;
             float4 v = *reinterpret_cast<const float4*>(&strip[ch * 32 + q8 * 4]);
             if (pok && co < p.Cout) {
-                const float bv = p.bias ? p.bias[co] : 0.f;
-                v.x += bv; v.y += bv; v.z += bv; v.w += bv;
-                if (p.act == L2I_ACT_LRELU) {
-                    v.x = (v.x > 0.f ? v.x : v.x * p.act_slope) * p.act_gain; v.y = (v.y > 0.f ? v.y : v.y * p.act_slope) * p.act_gain;
-                    v.z = (v.z > 0.f ? v.z : v.z * p.act_slope) * p.act_gain; v.w = (v.w > 0.f ? v.w : v.w * p.act_slope) * p.act_gain;
-                } else if (p.act == L2I_ACT_RELU) {
-                    v.x = __builtin_fmaxf(v.x, 0.f); v.y = __builtin_fmaxf(v.y, 0.f); v.z = __builtin_fmaxf(v.z, 0.f); v.w = __builtin_fmaxf(v.w, 0.f);
-                }
-                v.x *= p.out_gain; v.y *= p.out_gain; v.z *= p.out_gain; v.w *= p.out_gain;
+                // bias (0 without one), leaky ReLU by select but ReLU by fmaxf, gain unconditionally
+                v = epi_mul(epi_act_select(p, epi_add(v, p.bias ? p.bias[co] : 0.f), true), p.out_gain);
                 const size_t oidx = ((size_t)b * p.Cout + co) * plane_o + (size_t)oy * p.OWf + ox;
                 *reinterpret_cast<float4*>(p.y + oidx) = v;
-                if (p.sq_ref) {                                    // ContentLoss value of VGG conv_1 (see l2i.h: sq_ref / sq_out)
-                    const float4 rf = *reinterpret_cast<const float4*>(p.sq_ref + oidx);
-                    const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
-                    sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-                }
+                if (p.sq_ref) sq += epi_sq(p, v, oidx);            // ContentLoss value of VGG conv_1 (see l2i.h: sq_ref / sq_out)
             }
         }
     }
-    if (p.sq_ref) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
-        __syncthreads();                                           // the staged tile is no longer read
-        if (lane == 0) tile[wave] = sq;
-        __syncthreads();
-        if (tid == 0) atomicAdd(p.sq_out + (blockIdx.x & (L2I_SQ_SLOTS - 1)), (tile[0] + tile[1]) + (tile[2] + tile[3]));
-    }
+    if (p.sq_ref) epi_sq_commit(p, sq, tile);                                // (after its first barrier the staged tile is no longer read)
 }
 
 bool l2i_cin3_eligible(const l2i_conv_params& p) {

@@ -28,6 +28,7 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_epilogue.h"
 
 
 struct ConvLaunch {
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(256, (WM * WN <= 4) ? 3 : ((WM == 2 && WN == 4) ? 2
             const int bb = b0 + (pi >> (L.tw_log2 + L.th_log2));
             const bool pok = (n0 + nn < WN) && (oy < p.OH) && (ox < p.OW) && (bb < p.B);
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
-            float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);                  // (epi_noise4 inline: see the head of l2i_epilogue.h)
             if (pok && p.noise) {
                 nz = *reinterpret_cast<const float4*>(p.noise + (size_t)bb * plane_o + poff);
                 nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
@@ -318,53 +319,16 @@ __global__ __launch_bounds__(256, (WM * WN <= 4) ? 3 : ((WM == 2 && WN == 4) ? 2
 #pragma unroll
             for (int m = 0; m < WM; ++m) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    if (n0 + q < WN) {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            reg[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + q * 32 + j] = acc[m][(n0 + q) < WN ? (n0 + q) : 0][r];
-                    }
-                }
+                for (int q = 0; q < 2; ++q)
+                    if (n0 + q < WN) epi_strip_store(reg, half, j, q, acc[m][(n0 + q) < WN ? (n0 + q) : 0]);
 #pragma unroll 2
                 for (int i = 0; i < 8; ++i) {
                     const int ch = i * 4 + ch_l;
                     const int co = m0 + m * 32 + ch;
                     const float4 t = *reinterpret_cast<const float4*>(&reg[ch * 64 + px]);
                     if (pok && co < p.Cout) {
-                        float4 v = t;
-                        if (osc) { const float sc = osc[co]; v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc; }
                         const size_t oidx = ((size_t)bb * p.Cout + co) * plane_o + poff;
-                        if (p.out_mask) {
-                            const float4 mk = *reinterpret_cast<const float4*>(p.out_mask + oidx);
-                            v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-                        }
-                        if (p.noise) { v.x += nz.x; v.y += nz.y; v.z += nz.z; v.w += nz.w; }
-                        if (p.bias) { const float bv = p.bias[co]; v.x += bv; v.y += bv; v.z += bv; v.w += bv; }
-                        if (p.residual) {
-                            float4 rv = *reinterpret_cast<const float4*>(p.residual + oidx);
-                            if (p.res_sub) {                                   // residual term = res_coef * (residual - res_sub)
-                                const float4 sb = *reinterpret_cast<const float4*>(p.res_sub + oidx);
-                                const float rc = p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f);
-                                rv.x = rc * (rv.x - sb.x); rv.y = rc * (rv.y - sb.y); rv.z = rc * (rv.z - sb.z); rv.w = rc * (rv.w - sb.w);
-                            }
-                            if (p.res_mask) {
-                                const float4 mk = *reinterpret_cast<const float4*>(p.res_mask + oidx);
-                                rv.x = mk.x > 0.f ? rv.x : 0.f; rv.y = mk.y > 0.f ? rv.y : 0.f; rv.z = mk.z > 0.f ? rv.z : 0.f; rv.w = mk.w > 0.f ? rv.w : 0.f;
-                            }
-                            v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-                        }
-                        if (p.act == L2I_ACT_LRELU) {
-                            v.x = (v.x > 0.f ? v.x : v.x * p.act_slope) * p.act_gain; v.y = (v.y > 0.f ? v.y : v.y * p.act_slope) * p.act_gain;
-                            v.z = (v.z > 0.f ? v.z : v.z * p.act_slope) * p.act_gain; v.w = (v.w > 0.f ? v.w : v.w * p.act_slope) * p.act_gain;
-                        } else if (p.act == L2I_ACT_RELU) {
-                            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                        }
-                        if (p.out_gain != 1.f) { v.x *= p.out_gain; v.y *= p.out_gain; v.z *= p.out_gain; v.w *= p.out_gain; }
-                        if (p.accumulate) {
-                            const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
-                            v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                        }
-                        *reinterpret_cast<float4*>(p.y + oidx) = v;
+                        *reinterpret_cast<float4*>(p.y + oidx) = l2i_epilogue_chain4(p, t, osc, nz, co, oidx);
                     }
                 }
             }
@@ -383,7 +347,7 @@ __global__ __launch_bounds__(256, (WM * WN <= 4) ? 3 : ((WM == 2 && WN == 4) ? 2
         const int oyf = oy * p.oy_step + p.oy_off, oxf = ox * p.ox_step + p.ox_off;
         const size_t poff = (size_t)oyf * p.OWf + oxf;
         float nz = 0.f;
-        if (pok && p.noise) nz = p.noise[(size_t)bb * plane_o + poff] * p.noise_w;
+        if (pok && p.noise) nz = p.noise[(size_t)bb * plane_o + poff] * p.noise_w;    // (inline: see the head of l2i_epilogue.h)
         const int co_lane = m0 + 4 * half;
         const size_t lane_base = ((size_t)bb * p.Cout + co_lane) * plane_o + poff;
         const float* osc = p.out_scale ? p.out_scale + (size_t)bb * p.Cout : nullptr;
@@ -394,23 +358,8 @@ __global__ __launch_bounds__(256, (WM * WN <= 4) ? 3 : ((WM == 2 && WN == 4) ? 2
                 const int cofs = m * 32 + (r & 3) + 8 * (r >> 2);          // compile-time constant
                 const int co = co_lane + cofs;
                 if (pok && co < p.Cout) {
-                    float v = acc[m][n][r];
-                    if (osc) v *= osc[co];
                     const size_t oidx = lane_base + (size_t)cofs * plane_o;
-                    if (p.out_mask) v = (p.out_mask[oidx] > 0.f) ? v : 0.f;
-                    v += nz;
-                    if (p.bias) v += p.bias[co];
-                    if (p.residual) {
-                        float rv = p.residual[oidx];
-                        if (p.res_sub) rv = p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) * (rv - p.res_sub[oidx]);
-                        if (p.res_mask) rv = (p.res_mask[oidx] > 0.f) ? rv : 0.f;
-                        v += rv;
-                    }
-                    if (p.act == L2I_ACT_LRELU) v = (v > 0.f ? v : v * p.act_slope) * p.act_gain;
-                    else if (p.act == L2I_ACT_RELU) v = v > 0.f ? v : 0.f;
-                    v *= p.out_gain;
-                    if (p.accumulate) v += p.y[oidx];
-                    p.y[oidx] = v;
+                    p.y[oidx] = l2i_epilogue_chain1(p, acc[m][n][r], osc, nz, co, oidx);
                 }
             }
         }
@@ -712,17 +661,11 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const l2i_conv_par
         float v = 0.f;
         for (int s = 0; s < p.ksplit; ++s) v += p.ws[(size_t)s * per_split + oidx];
         if (p.out_scale) v *= p.out_scale[(size_t)bb * p.Cout + co];
-        if (p.out_mask) v = (p.out_mask[oidx] > 0.f) ? v : 0.f;
-        if (p.noise) v += p.noise[(size_t)bb * plane_o + poff] * p.noise_w;
+        if (p.out_mask) v = epi_keep(v, p.out_mask[oidx]);
+        if (p.noise) v += epi_noise(p, (size_t)bb * plane_o + poff);            // (only with noise: the conv epilogues add their 0 unconditionally)
         if (p.bias) v += p.bias[co];
-        if (p.residual) {
-            float rv = p.residual[oidx];
-            if (p.res_sub) rv = p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) * (rv - p.res_sub[oidx]);
-            if (p.res_mask) rv = (p.res_mask[oidx] > 0.f) ? rv : 0.f;
-            v += rv;
-        }
-        if (p.act == L2I_ACT_LRELU) v = (v > 0.f ? v : v * p.act_slope) * p.act_gain;
-        else if (p.act == L2I_ACT_RELU) v = v > 0.f ? v : 0.f;
+        if (p.residual) v += epi_residual1(p, oidx);
+        v = epi_act_select(p, v);
         v *= p.out_gain;
         if (p.accumulate) v += p.y[oidx];
         p.y[oidx] = v;
@@ -830,9 +773,7 @@ static bool plan_tile(const l2i_conv_params& p, int wm, int wn, ConvLaunch& L, b
     L.magic_rc = magic_for((unsigned)L.rows_c);
     L.magic_ih = magic_for((unsigned)L.IH);
     lds = per_c * ck + (size_t)(ck << L.tb_log2) * sizeof(float);
-    auto al16 = [](const void* q) { return (((uintptr_t)q) % 16) == 0; };
-    L.vec_epi = (p.ox_step == 1 && p.oy_step == 1 && (p.OWf % 4) == 0 && (p.OW % 4) == 0 && (p.ox_off % 4) == 0 && L.tw_log2 >= 2 &&
-                 al16(p.y) && al16(p.residual) && al16(p.res_mask) && al16(p.res_sub) && al16(p.out_mask) && al16(p.noise)) ? 1 : 0;
+    L.vec_epi = (l2i_epilogue_vec_ok(p) && L.tw_log2 >= 2) ? 1 : 0;
     if (L.vec_epi && lds < 4 * 32 * 64 * sizeof(float)) lds = 4 * 32 * 64 * sizeof(float);      // 8 KiB transpose strip per wave
     grid = (long)L.bgroups * L.tiles_y * L.tiles_x * L.mblocks * L.ksplit;
     if (!(lds <= 64 * 1024 && grid > 0 && grid <= 0x7ffffff0L)) return false;

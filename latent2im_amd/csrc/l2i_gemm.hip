@@ -16,6 +16,7 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_epilogue.h"
 
 
 namespace gm {
@@ -122,39 +123,17 @@ __global__ __launch_bounds__(256, (MASK || NOPS > 0) ? 2 : 3) void gemm1x1_kerne
     const int ch_l = lane >> 4, px = (lane & 15) * 4;
     const size_t pix = (size_t)px0 + wave * 64 + px;
     const bool pok = pix < HW;
-    const float rc = p.res_sub ? p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) : 1.f;
-    float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pok && p.noise) {
-        nz = *reinterpret_cast<const float4*>(p.noise + (size_t)b * HW + pix);
-        nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
-    }
+    const float rc = p.res_sub ? epi_rc(p) : 1.f;
+    const float4 nz = epi_noise4(p, pok, (size_t)b * HW + pix);
+    const float* osc = p.out_scale ? p.out_scale + (size_t)b * p.Cout : nullptr;
     // one output vector: v = 4 pixels of channel co straight from the accumulators; om / rv / sb / rm / yo = the operand vectors (only read
     // when the operand exists)
     auto apply = [&](float4 v, int co, size_t oidx, const float4& om, float4 rv, const float4& sb, const float4& rm, const float4& yo) {
-        if (p.out_scale) { const float sc = p.out_scale[(size_t)b * p.Cout + co]; v.x *= sc; v.y *= sc; v.z *= sc; v.w *= sc; }
-        if (p.out_mask) { v.x = om.x > 0.f ? v.x : 0.f; v.y = om.y > 0.f ? v.y : 0.f; v.z = om.z > 0.f ? v.z : 0.f; v.w = om.w > 0.f ? v.w : 0.f; }
-        if (p.noise) { v.x += nz.x; v.y += nz.y; v.z += nz.z; v.w += nz.w; }
-        if (p.bias) { const float bv = p.bias[co]; v.x += bv; v.y += bv; v.z += bv; v.w += bv; }
-        if (p.residual) {
-            if (p.res_sub) { rv.x = rc * (rv.x - sb.x); rv.y = rc * (rv.y - sb.y); rv.z = rc * (rv.z - sb.z); rv.w = rc * (rv.w - sb.w); }   // res_coef * (residual - res_sub)
-            if (p.res_mask) { rv.x = rm.x > 0.f ? rv.x : 0.f; rv.y = rm.y > 0.f ? rv.y : 0.f; rv.z = rm.z > 0.f ? rv.z : 0.f; rv.w = rm.w > 0.f ? rv.w : 0.f; }
-            v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-        }
-        if (p.act == L2I_ACT_LRELU) {
-            v.x = (v.x > 0.f ? v.x : v.x * p.act_slope) * p.act_gain; v.y = (v.y > 0.f ? v.y : v.y * p.act_slope) * p.act_gain;
-            v.z = (v.z > 0.f ? v.z : v.z * p.act_slope) * p.act_gain; v.w = (v.w > 0.f ? v.w : v.w * p.act_slope) * p.act_gain;
-        } else if (p.act == L2I_ACT_RELU) {
-            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        }
-        if (p.out_gain != 1.f) { v.x *= p.out_gain; v.y *= p.out_gain; v.z *= p.out_gain; v.w *= p.out_gain; }
-        if (p.accumulate) { v.x += yo.x; v.y += yo.y; v.z += yo.z; v.w += yo.w; }
-        *reinterpret_cast<float4*>(p.y + oidx) = v;
+        *reinterpret_cast<float4*>(p.y + oidx) = l2i_epilogue_chain4_ops(p, v, osc, nz, co, om, rv, sb, rm, yo, rc);
     };
     auto to_strip = [&](int m) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) reg[((r & 3) + 8 * (r >> 2) + 4 * half) * 64 + q * 32 + j] = acc[m][q][r];
+        for (int q = 0; q < 2; ++q) epi_strip_store(reg, half, j, q, acc[m][q]);
     };
     if constexpr (NOPS == 0) {
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -237,7 +216,7 @@ bool l2i_gemm1x1_eligible(const l2i_conv_params& p) {
     const size_t HW = (size_t)p.H * p.W;
     return p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad_y == 0 && p.pad_x == 0 && !p.in_scale && p.oy_step == 1 && p.ox_step == 1 &&
            p.oy_off == 0 && p.ox_off == 0 && p.OH == p.H && p.OW == p.W && p.OHf == p.H && p.OWf == p.W && (HW % gm::BN) == 0 && (p.Cin % gm::CK) == 0 &&
-           (p.CoutP % 64) == 0 && al16(p.x) && al16(p.in_mask) && al16(p.y) && al16(p.w) && al16(p.residual) && al16(p.res_mask) && al16(p.res_sub) && al16(p.out_mask) && al16(p.noise) &&
+           (p.CoutP % 64) == 0 && al16(p.x) && al16(p.in_mask) && al16(p.w) && l2i_epilogue_operands_al16(p) &&
            (size_t)p.Cin * HW * sizeof(float) < 0xFFFFFFF0ull;
 }
 

@@ -33,6 +33,7 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_epilogue.h"
 
 
 // (a.lo + b.hi, a.lo - b.hi).  The half selection sits on SRC0 (b first: the sum commutes, the bits are the same), not on src1 as in the first form
@@ -339,11 +340,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
     const int oy = oy0 + 2 * wave + row, ox = ox0 + col;
     const bool pok = (oy < p.OH) && (ox < p.OW);
     const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
-    float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pok && p.noise) {
-        nz = *reinterpret_cast<const float4*>(p.noise + (size_t)b * plane_o + poff);
-        nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
-    }
+    const float4 nz = epi_noise4(p, pok, (size_t)b * plane_o + poff);
     float sq = 0.f;
 #pragma unroll 2
     for (int it = 0; it < 8; ++it) {
@@ -356,22 +353,13 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
             if (p.out_scale) { const f32x2 scp = {sc, sc}; va = pk_mul(va, scp); vb = pk_mul(vb, scp); }
             const size_t oidx = ((size_t)b * p.Cout + co) * plane_o + poff;
             if (p.out_mask) {
-                const float4 mk = *reinterpret_cast<const float4*>(p.out_mask + oidx);
-                va.x = mk.x > 0.f ? va.x : 0.f; va.y = mk.y > 0.f ? va.y : 0.f; vb.x = mk.z > 0.f ? vb.x : 0.f; vb.y = mk.w > 0.f ? vb.y : 0.f;
+                const float4 k = epi_keep(make_float4(va.x, va.y, vb.x, vb.y), epi_ld4(p.out_mask + oidx));
+                va = f32x2{k.x, k.y}; vb = f32x2{k.z, k.w};
             }
-            const f32x2 bvp = {bv, bv};
+            const f32x2 bvp = {bv, bv};                            // (noise + bias) as one term, added unconditionally
             va = pk_add(va, pk_add(f32x2{nz.x, nz.y}, bvp)); vb = pk_add(vb, pk_add(f32x2{nz.z, nz.w}, bvp));
             if (p.residual) {
-                float4 rv = *reinterpret_cast<const float4*>(p.residual + oidx);
-                if (p.res_sub) {                                   // residual term = res_coef * (residual - res_sub)
-                    const float4 sb = *reinterpret_cast<const float4*>(p.res_sub + oidx);
-                    const float rc = p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f);
-                    rv.x = rc * (rv.x - sb.x); rv.y = rc * (rv.y - sb.y); rv.z = rc * (rv.z - sb.z); rv.w = rc * (rv.w - sb.w);
-                }
-                if (p.res_mask) {
-                    const float4 mk = *reinterpret_cast<const float4*>(p.res_mask + oidx);
-                    rv.x = mk.x > 0.f ? rv.x : 0.f; rv.y = mk.y > 0.f ? rv.y : 0.f; rv.z = mk.z > 0.f ? rv.z : 0.f; rv.w = mk.w > 0.f ? rv.w : 0.f;
-                }
+                const float4 rv = epi_residual(p, oidx);
                 va = pk_add(va, f32x2{rv.x, rv.y}); vb = pk_add(vb, f32x2{rv.z, rv.w});
             }
             if (p.act == L2I_ACT_LRELU) {                          // max(v, slope v) == (v > 0 ? v : slope v) for 0 <= slope <= 1
@@ -383,27 +371,12 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(const l2i_conv_params
                 va.x = __builtin_fmaxf(va.x, 0.f); va.y = __builtin_fmaxf(va.y, 0.f); vb.x = __builtin_fmaxf(vb.x, 0.f); vb.y = __builtin_fmaxf(vb.y, 0.f);
             }
             if (p.out_gain != 1.f) { const f32x2 ogp = {p.out_gain, p.out_gain}; va = pk_mul(va, ogp); vb = pk_mul(vb, ogp); }
-            v = make_float4(va.x, va.y, vb.x, vb.y);
-            if (p.accumulate) {
-                const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
-                v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-            }
+            v = epi_accumulate(p, make_float4(va.x, va.y, vb.x, vb.y), oidx);
             *reinterpret_cast<float4*>(p.y + oidx) = v;
-            if (p.sq_ref) {                                        // ContentLoss value of a VGG tap: sum (y - reference)^2 while y is in registers
-                const float4 rf = *reinterpret_cast<const float4*>(p.sq_ref + oidx);
-                const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
-                sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
+            if (p.sq_ref) sq += epi_sq(p, v, oidx);
         }
     }
-    if (p.sq_ref) {                                                // (kernel argument: uniform branch) one atomic per block, 1024 slots
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
-        __syncthreads();                                           // every lane is past its reads of the epilogue tables
-        if (lane == 0) tab[wave] = sq;
-        __syncthreads();
-        if (tid == 0) atomicAdd(p.sq_out + (blockIdx.x & (L2I_SQ_SLOTS - 1)), (tab[0] + tab[1]) + (tab[2] + tab[3]));
-    }
+    if (p.sq_ref) epi_sq_commit(p, sq, tab);                                // (after its first barrier every lane is past its reads of the epilogue tables)
 }
 
 static int launch_wino(const l2i_conv_params& p, hipStream_t st) {
@@ -448,9 +421,7 @@ extern "C" int l2i_conv2d_wino_f32(const l2i_conv_params* pp, void* stream) {
     if (p.CoutP < p.Cout || (p.CoutP % 32) != 0) return l2i_set_error(L2I_E_ARG, "conv2d_wino: CoutP must be Cout rounded up to 32");
     if (p.oy_off < 0 || p.ox_off < 0 || p.OH + p.oy_off > p.OHf || p.OW + p.ox_off > p.OWf)
         return l2i_set_error(L2I_E_ARG, "conv2d_wino: output window exceeds the output tensor");
-    auto al16 = [](const void* q) { return (((uintptr_t)q) % 16) == 0; };
-    if ((p.OWf % 4) != 0 || (p.OW % 4) != 0 || (p.ox_off % 4) != 0 || !al16(p.y) || !al16(p.residual) || !al16(p.res_mask) || !al16(p.res_sub) || !al16(p.out_mask) ||
-        !al16(p.noise) || !al16(p.w))
+    if (!l2i_epilogue_vec_ok(p) || (((uintptr_t)p.w) % 16) != 0)       // (dense output was checked above)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino: output rows must be 16-byte aligned multiples of 4 pixels");
     if ((size_t)p.Cin * p.H * p.W * sizeof(float) >= 0xFFFFFFF0ull || (size_t)p.Cin * 16 * p.CoutP * sizeof(float) >= 0xFFFFFFF0ull)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino: one sample / the weight pack must stay below 4 GiB (32-bit buffer offsets)");

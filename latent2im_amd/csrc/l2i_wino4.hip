@@ -26,6 +26,7 @@
 #include "l2i.h"
 #include "l2i_internal.h"
 #include "l2i_device.h"
+#include "l2i_epilogue.h"
 
 
 namespace w4 {
@@ -102,6 +103,16 @@ __device__ __forceinline__ f32x2 w4_lds_b64(unsigned addr, int off) {
 }
 __device__ __forceinline__ void w4_lds_wait6(f32x2& a, f32x2& b, f32x2& c, f32x2& d, f32x2& e, f32x2& f) {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+}
+
+// the generic epilogue of both F(4x4) kernels on four pixels of one channel: the shared terms (l2i_epilogue.h) with sc / bv read once per channel
+// (1 / 0 without the operand), (noise + bias) formed first and added unconditionally, the fmaxf activation and rc hoisted by the caller
+__device__ __forceinline__ float4 w4_epilogue(const l2i_conv_params& p, float4 v, float sc, float4 nz, float bv, size_t oidx, float rc) {
+    if (p.out_scale) v = epi_mul(v, sc);
+    if (p.out_mask) v = epi_keep(v, epi_ld4(p.out_mask + oidx));
+    v = epi_add(v, epi_add(nz, bv));
+    if (p.residual) v = epi_add(v, epi_residual(p, oidx, rc));
+    return epi_accumulate(p, epi_gain(p, epi_act_fmax(p, v)), oidx);
 }
 
 template <bool SCALE, bool RELU, int RS>
@@ -342,7 +353,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
     const int oyb = oy0 + 4 * wave, ox = ox0 + 4 * n;
     const bool xok = ox < p.OW;
     float sq = 0.f;
-    const float rc = p.res_sub ? p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) : 0.f;
+    const float rc = p.res_sub ? epi_rc(p) : 0.f;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {                      // accumulator rows (2 h, 2 h + 1) = two channels as one register pair
         const int co0 = m0 + 4 * kq + 2 * h;
@@ -374,64 +385,21 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(const l2i_conv_param
             const int oy = oyb + ry;
             const bool pok = xok && (oy < p.OH);
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
-            float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pok && p.noise) {
-                nz = *reinterpret_cast<const float4*>(p.noise + (size_t)b * plane_o + poff);
-                nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
-            }
+            const float4 nz = epi_noise4(p, pok, (size_t)b * plane_o + poff);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int co = co0 + q;
                 if (!(pok && co < p.Cout)) continue;
                 float4 v = q ? make_float4(y0.y, y1.y, y2.y, y3.y) : make_float4(y0.x, y1.x, y2.x, y3.x);
-                if constexpr (RELU) { v.x *= W4_RELU_UNSCALE; v.y *= W4_RELU_UNSCALE; v.z *= W4_RELU_UNSCALE; v.w *= W4_RELU_UNSCALE; }
+                if constexpr (RELU) v = epi_mul(v, W4_RELU_UNSCALE);
                 const size_t oidx = ((size_t)b * p.Cout + co) * plane_o + poff;
-                if (p.out_scale) { v.x *= scv[q]; v.y *= scv[q]; v.z *= scv[q]; v.w *= scv[q]; }
-                if (p.out_mask) {
-                    const float4 mk = *reinterpret_cast<const float4*>(p.out_mask + oidx);
-                    v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-                }
-                v.x += nz.x + bv[q]; v.y += nz.y + bv[q]; v.z += nz.z + bv[q]; v.w += nz.w + bv[q];
-                if (p.residual) {
-                    float4 rv = *reinterpret_cast<const float4*>(p.residual + oidx);
-                    if (p.res_sub) {                               // residual term = res_coef * (residual - res_sub)
-                        const float4 sb = *reinterpret_cast<const float4*>(p.res_sub + oidx);
-                        rv.x = rc * (rv.x - sb.x); rv.y = rc * (rv.y - sb.y); rv.z = rc * (rv.z - sb.z); rv.w = rc * (rv.w - sb.w);
-                    }
-                    if (p.res_mask) {
-                        const float4 mk = *reinterpret_cast<const float4*>(p.res_mask + oidx);
-                        rv.x = mk.x > 0.f ? rv.x : 0.f; rv.y = mk.y > 0.f ? rv.y : 0.f; rv.z = mk.z > 0.f ? rv.z : 0.f; rv.w = mk.w > 0.f ? rv.w : 0.f;
-                    }
-                    v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-                }
-                if (p.act == L2I_ACT_LRELU) {                      // max(v, slope v) == (v > 0 ? v : slope v) for 0 <= slope <= 1
-                    v.x = __builtin_fmaxf(v.x, v.x * p.act_slope) * p.act_gain; v.y = __builtin_fmaxf(v.y, v.y * p.act_slope) * p.act_gain;
-                    v.z = __builtin_fmaxf(v.z, v.z * p.act_slope) * p.act_gain; v.w = __builtin_fmaxf(v.w, v.w * p.act_slope) * p.act_gain;
-                } else if (p.act == L2I_ACT_RELU) {
-                    v.x = __builtin_fmaxf(v.x, 0.f); v.y = __builtin_fmaxf(v.y, 0.f); v.z = __builtin_fmaxf(v.z, 0.f); v.w = __builtin_fmaxf(v.w, 0.f);
-                }
-                if (p.out_gain != 1.f) { v.x *= p.out_gain; v.y *= p.out_gain; v.z *= p.out_gain; v.w *= p.out_gain; }
-                if (p.accumulate) {
-                    const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
-                    v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                }
+                v = w4_epilogue(p, v, scv[q], nz, bv[q], oidx, rc);
                 *reinterpret_cast<float4*>(p.y + oidx) = v;
-                if (p.sq_ref) {                                    // ContentLoss value of a VGG tap: sum (y - reference)^2 while y is in registers
-                    const float4 rf = *reinterpret_cast<const float4*>(p.sq_ref + oidx);
-                    const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
-                    sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-                }
+                if (p.sq_ref) sq += epi_sq(p, v, oidx);
             }
         }
     }
-    if (p.sq_ref) {                                                // (kernel argument: uniform branch) one atomic per block, 1024 slots
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
-        __syncthreads();                                           // every wave is past its vmcnt(0): no target-less DMA slot can still land in the dump
-        if (lane == 0) dump[wave] = sq;
-        __syncthreads();
-        if (tid == 0) atomicAdd(p.sq_out + (blockIdx.x & (L2I_SQ_SLOTS - 1)), (dump[0] + dump[1]) + (dump[2] + dump[3]));
-    }
+    if (p.sq_ref) epi_sq_commit(p, sq, dump);                    // (every wave is past its vmcnt(0): no target-less DMA slot can still land in the dump)
 }
 
 // ====================================================================================================================================
@@ -825,7 +793,7 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
 
     // ---- epilogue: lane-local inverse transform Y = A^T M A, then 16-byte row stores (lane (g, n): channels m0 + 16 H + 4 g + 0..3, tile (trow, n)) ----
     float sq = 0.f;
-    const float rc = p.res_sub ? p.res_coef * (p.res_coef_dev ? p.res_coef_dev[0] : 1.f) : 0.f;
+    const float rc = p.res_sub ? epi_rc(p) : 0.f;
     // ---- lean classes (EM = the launch's exact operand set): what the set does not hold is compiled out, what it holds is there ----
     constexpr bool LEAN = EM != W4E_GENERIC;
     constexpr bool E_SC = LEAN && (EM & W4E_OUT_SCALE), E_NZ = LEAN && (EM & W4E_NOISE), E_OM = LEAN && (EM & W4E_OUT_MASK);
@@ -895,46 +863,15 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
             const bool pok = xok && (oy < p.OH);
             const size_t poff = (size_t)(oy + p.oy_off) * p.OWf + ox + p.ox_off;
             float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (pok && p.noise) {
-                nz = nz_h[ry];
-                nz.x *= p.noise_w; nz.y *= p.noise_w; nz.z *= p.noise_w; nz.w *= p.noise_w;
-            }
+            if (pok && p.noise) nz = epi_mul(nz_h[ry], p.noise_w);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int co = co0 + q;
                 if (!(pok && co < p.Cout)) { pvalid[q] = false; continue; }
                 float4 v = q ? make_float4(y0.y, y1.y, y2.y, y3.y) : make_float4(y0.x, y1.x, y2.x, y3.x);
-                if constexpr (RELU) { v.x *= W4_RELU_UNSCALE; v.y *= W4_RELU_UNSCALE; v.z *= W4_RELU_UNSCALE; v.w *= W4_RELU_UNSCALE; }
+                if constexpr (RELU) v = epi_mul(v, W4_RELU_UNSCALE);
                 const size_t oidx = ((size_t)b * p.Cout + co) * plane_o + poff;
-                if (p.out_scale) { v.x *= scv[q]; v.y *= scv[q]; v.z *= scv[q]; v.w *= scv[q]; }
-                if (p.out_mask) {
-                    const float4 mk = *reinterpret_cast<const float4*>(p.out_mask + oidx);
-                    v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-                }
-                v.x += nz.x + bv[q]; v.y += nz.y + bv[q]; v.z += nz.z + bv[q]; v.w += nz.w + bv[q];
-                if (p.residual) {
-                    float4 rv = *reinterpret_cast<const float4*>(p.residual + oidx);
-                    if (p.res_sub) {                               // residual term = res_coef * (residual - res_sub)
-                        const float4 sb = *reinterpret_cast<const float4*>(p.res_sub + oidx);
-                        rv.x = rc * (rv.x - sb.x); rv.y = rc * (rv.y - sb.y); rv.z = rc * (rv.z - sb.z); rv.w = rc * (rv.w - sb.w);
-                    }
-                    if (p.res_mask) {
-                        const float4 mk = *reinterpret_cast<const float4*>(p.res_mask + oidx);
-                        rv.x = mk.x > 0.f ? rv.x : 0.f; rv.y = mk.y > 0.f ? rv.y : 0.f; rv.z = mk.z > 0.f ? rv.z : 0.f; rv.w = mk.w > 0.f ? rv.w : 0.f;
-                    }
-                    v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-                }
-                if (p.act == L2I_ACT_LRELU) {                      // max(v, slope v) == (v > 0 ? v : slope v) for 0 <= slope <= 1
-                    v.x = __builtin_fmaxf(v.x, v.x * p.act_slope) * p.act_gain; v.y = __builtin_fmaxf(v.y, v.y * p.act_slope) * p.act_gain;
-                    v.z = __builtin_fmaxf(v.z, v.z * p.act_slope) * p.act_gain; v.w = __builtin_fmaxf(v.w, v.w * p.act_slope) * p.act_gain;
-                } else if (p.act == L2I_ACT_RELU) {
-                    v.x = __builtin_fmaxf(v.x, 0.f); v.y = __builtin_fmaxf(v.y, 0.f); v.z = __builtin_fmaxf(v.z, 0.f); v.w = __builtin_fmaxf(v.w, 0.f);
-                }
-                if (p.out_gain != 1.f) { v.x *= p.out_gain; v.y *= p.out_gain; v.z *= p.out_gain; v.w *= p.out_gain; }
-                if (p.accumulate) {
-                    const float4 o = *reinterpret_cast<const float4*>(p.y + oidx);
-                    v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                }
+                v = w4_epilogue(p, v, scv[q], nz, bv[q], oidx, rc);
                 *reinterpret_cast<float4*>(p.y + oidx) = v;
                 if (p.pool_out) {                                  // [r5] MaxPool2d(2, 2) of y from the tile in registers (l2i.h: pool_out / pool_idx)
                     if ((ry & 1) == 0) { prow[q] = v; pvalid[q] = true; }
@@ -953,11 +890,7 @@ __device__ __forceinline__ void wino4s_body(const l2i_conv_params& p, const Wino
                         *reinterpret_cast<unsigned short*>(p.pool_idx + pidx) = (unsigned short)(i0 | (i1 << 8));
                     }
                 }
-                if (p.sq_ref) {                                    // ContentLoss value of a VGG tap: sum (y - reference)^2 while y is in registers
-                    const float4 rf = *reinterpret_cast<const float4*>(p.sq_ref + oidx);
-                    const float d0 = v.x - rf.x, d1 = v.y - rf.y, d2 = v.z - rf.z, d3 = v.w - rf.w;
-                    sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-                }
+                if (p.sq_ref) sq += epi_sq(p, v, oidx);
             }
         }
         } else {
@@ -1202,9 +1135,7 @@ extern "C" int l2i_conv2d_wino4_f32(const l2i_conv_params* pp, void* stream) {
     if (p.CoutP < p.Cout || (p.CoutP % 32) != 0) return l2i_set_error(L2I_E_ARG, "conv2d_wino4: CoutP must be Cout rounded up to a multiple of 32");
     if (p.oy_off < 0 || p.ox_off < 0 || p.OH + p.oy_off > p.OHf || p.OW + p.ox_off > p.OWf)
         return l2i_set_error(L2I_E_ARG, "conv2d_wino4: output window exceeds the output tensor");
-    auto al16 = [](const void* q) { return (((uintptr_t)q) % 16) == 0; };
-    if ((p.OWf % 4) != 0 || (p.OW % 4) != 0 || (p.ox_off % 4) != 0 || !al16(p.y) || !al16(p.residual) || !al16(p.res_mask) || !al16(p.res_sub) || !al16(p.out_mask) ||
-        !al16(p.noise) || !al16(p.w))
+    if (!l2i_epilogue_vec_ok(p) || (((uintptr_t)p.w) % 16) != 0)       // (dense output was checked above)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino4: output rows must be 16-byte aligned multiples of 4 pixels");
     if ((size_t)p.Cin * p.H * p.W * sizeof(float) >= 0x7FFF0000ull || (size_t)p.Cin * 36 * p.CoutP * sizeof(float) >= 0xFFFFFFF0ull)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wino4: one sample must stay below 2 GiB, the weight pack below 4 GiB (32-bit buffer offsets)");

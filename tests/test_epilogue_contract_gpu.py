@@ -1,5 +1,6 @@
-"""Every copy of the fused conv prologue / epilogue (include/l2i.h: pro / epi / R) against ONE float64 model (tests/epilogue_ref.py), term by
-term: route x case.  A route is one kernel (one copy of the epilogue) reached through the dispatch the product uses; it asserts the entry point
+"""Every kernel's fused conv prologue / epilogue (include/l2i.h: pro / epi / R) against ONE float64 model (tests/epilogue_ref.py), term by
+term: route x case.  A route is one kernel (one kernel's composition of the shared terms of csrc/l2i_epilogue.h, or an epilogue a kernel keeps
+inline) reached through the dispatch the product uses; a new composition is a new route.  A route asserts the entry point
 and kernel family that ran, so a dispatch change cannot empty a row silently.  A case sets one contract field alone, or a combination that exists
 to expose one term-order mistake (tests/test_epilogue_ref_cpu.py proves that it can).  Masks hold exact +-0.0; every output is carved from a larger
 buffer filled with a sentinel and everything outside the launch window must come back bit-identical.  A field a route does not implement must move
