@@ -1,3 +1,3 @@
-"""reference graphs/pggan/transform_base.py — WalkLinearZ_free (:86-102) and the PGGAN TransformGraph (:211-640); walk checkpoints pickle
-this module path (latent2im_amd/pggan.py sets ``WalkLinearZ_free.__module__``)."""
-from latent2im_amd.pggan import PGGAN, ContentLoss, PixelTransform, TransformGraph, WalkLinearZ_free  # noqa: F401
+"""reference graphs/pggan/transform_base.py — WalkLinearZ_free (:86-102), WalkMlpZ3 (:167-188) and the PGGAN TransformGraph (:211-640); walk
+checkpoints pickle this module path (latent2im_amd/pggan.py sets ``__module__`` of both walks)."""
+from latent2im_amd.pggan import PGGAN, ContentLoss, PixelTransform, TransformGraph, WalkLinearZ_free, WalkMlpZ3  # noqa: F401

@@ -544,6 +544,27 @@ int l2i_pixelnorm_act_bwd_h8(void* dx, const void* gy, const void* x, const void
 int l2i_pixelnorm_act_bwd_h8_f16(void* dx, const void* gy, const void* x, const void* addend, int B, int C, int H, int W, float eps, float slope, int pool,
                                  void* stream);
 
+/* ---- [ABI 12, additive] the linear layers of the PGGAN graph's MLP walk (csrc/l2i_walk.hip; WalkMlpZ3, graphs/pggan/transform_base.py:167-188) ------
+ * Skinny products on plain fp32 VALU: B rows (any B >= 1, taken in chunks of at most 16) against W in nn.Linear's own [N = out, K = in] layout.
+ * l2i_linear_rows_f32:      y[B, N] = epi(x[B, K] W^T + bias[N]).  epi = L2I_LINEAR_NONE; L2I_LINEAR_LRELU: v > 0 ? v : v * slope; L2I_LINEAR_WALK: the
+ *   walk's tail y = res[b, n] + a[b] * v (res [B, N] the residual z, a [B] the per-row alpha; both NULL otherwise).
+ * l2i_linear_rows_bwd_f32:  one pass over the layer's [N, K] index space.  g [B, N] = the gradient at the layer's output; g' = g * (y > 0 ? 1 : slope)
+ *   for L2I_LINEAR_LRELU (y [B, N] = the layer's activated output: the mask of an in-place LeakyReLU, y == 0 takes the slope), g' = a[b] * g for
+ *   L2I_LINEAR_WALK (the residual's own gradient is not formed here), g' = g for L2I_LINEAR_NONE.  Writes gw[n, k] = sum_b g'[b, n] x[b, k], gb[n] =
+ *   sum_b g'[b, n] (gb may be NULL) and, when gx is not NULL, gx[b, k] = sum_n g'[b, n] W[n, k] + gx_add[b, k] (gx_add [B, K] may be NULL: the
+ *   residual path of the first layer).  N is cut into `slices` equal slices (N % slices == 0, at most 64 rows each); with slices > 1 the slices'
+ *   shares of gx go to ws (slices * B * K floats) and a second kernel of the same call adds them in slice order.  Without gx, w and ws are not read.
+ * Both: no floating-point atomics — b ascending, n ascending within a slice, slices ascending: equal inputs and equal `slices` give equal bits; no
+ * host synchronisation, nothing allocated.  K % 64 != 0 or N % 64 != 0, a non-positive size, an unknown epi, a missing operand, or x / w / gw / gx /
+ * ws / gx_add off a 16-byte boundary (they are accessed as float4) return L2I_E_ARG before a launch. */
+#define L2I_LINEAR_NONE 0
+#define L2I_LINEAR_LRELU 1
+#define L2I_LINEAR_WALK 2
+int l2i_linear_rows_f32(float* y, const float* x, const float* w, const float* bias, const float* res, const float* a, int B, int K, int N, int epi,
+                        float slope, void* stream);
+int l2i_linear_rows_bwd_f32(float* gw, float* gb, float* gx, float* ws, const float* gx_add, const float* g, const float* y, const float* a,
+                            const float* x, const float* w, int B, int K, int N, int epi, float slope, int slices, void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
  * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins; 12: l2i_sgd_guarded_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('L2I_LIB') or os.path.join(_HERE, 'libl2i_hip.so')      # L2I_LIB: another build of the library (A/B probes)
 
 ACT_NONE, ACT_LRELU, ACT_RELU = 0, 1, 2
+LINEAR_NONE, LINEAR_LRELU, LINEAR_WALK = 0, 1, 2      # L2I_LINEAR_*: the epilogues of l2i_linear_rows_f32 / _bwd_f32
 
 c_f = ctypes.c_float
 c_i = ctypes.c_int32
@@ -124,6 +125,8 @@ _SIGNATURES = {
     'l2i_gram_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_pixelnorm_act_h8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p]),
     'l2i_pixelnorm_act_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p]),
+    'l2i_linear_rows_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    'l2i_linear_rows_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
     'l2i_sizeof_conv_params': (c_i, []),

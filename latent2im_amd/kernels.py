@@ -4,6 +4,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU  # noqa: F401
+from ._lib import LINEAR_LRELU, LINEAR_NONE, LINEAR_WALK  # noqa: F401
 
 SQRT2 = 2 ** 0.5
 
@@ -243,6 +244,52 @@ def segmented_matvec(out, inp, w, segs, block_seg, nblocks, B, in2=None, bias=No
               _lib.fptr(wmod), _lib.fptr(wrgb), _lib.ptr(segs), _lib.ptr(block_seg), int(nblocks), int(B))
     return out
 
+
+
+def linear_rows(x, w, b, epi=LINEAR_NONE, slope=0.2, res=None, a=None, out=None):
+    """l2i_linear_rows_f32: y [B, N] = epi(x [B, K] w^T + b), w [N, K] as nn.Linear holds it.  LINEAR_LRELU: LeakyReLU(slope); LINEAR_WALK: the
+    walk's tail res + a[:, None] * (...) with res [B, N] and a [B]."""
+    B, Kd = x.shape
+    N = w.shape[0]
+    assert tuple(w.shape) == (N, Kd) and b.numel() == N, (x.shape, w.shape, b.shape)
+    if epi == LINEAR_WALK:
+        assert tuple(res.shape) == (B, N) and a.numel() == B, (res.shape, a.shape)
+    y = torch.empty(B, N, device=x.device, dtype=torch.float32) if out is None else out
+    assert tuple(y.shape) == (B, N)
+    _lib.call('l2i_linear_rows_f32', _lib.fptr(y), _lib.fptr(x), _lib.fptr(w), _lib.fptr(b), _lib.fptr(res), _lib.fptr(a), B, Kd, N, int(epi), float(slope))
+    return y
+
+
+def linear_rows_slices(N):
+    """How many row slices l2i_linear_rows_bwd_f32 is launched with: 16 rows a slice (one wave each per 256 columns — 256 waves on a 1024 x 1024
+    layer).  A function of the shape alone: equal inputs give equal bits."""
+    return max(1, N // 16)
+
+
+def linear_rows_bwd(g, x, w, epi=LINEAR_NONE, slope=0.2, y=None, a=None, want_gx=True, gx_add=None, gw=None, gb=None, gx=None, slices=None):
+    """l2i_linear_rows_bwd_f32: one pass over a layer's [N, K] weights.  g [B, N] the gradient at the layer's output, g' = g * (y > 0 ? 1 : slope)
+    (LINEAR_LRELU, y the activated output), a[:, None] * g (LINEAR_WALK) or g.  Returns (gw [N, K], gb [N], gx [B, K] or None); gx_add [B, K] is
+    added to gx (the residual path).  gw / gb / gx: destinations, allocated when absent."""
+    B, N = g.shape
+    Kd = x.shape[1]
+    assert x.shape[0] == B and tuple(w.shape) == (N, Kd), (g.shape, x.shape, w.shape)
+    assert y is None or tuple(y.shape) == (B, N)
+    assert a is None or a.numel() == B
+    slices = linear_rows_slices(N) if slices is None else int(slices)
+    gw = torch.empty(N, Kd, device=g.device, dtype=torch.float32) if gw is None else gw
+    gb = torch.empty(N, device=g.device, dtype=torch.float32) if gb is None else gb
+    ws = None
+    if want_gx:
+        gx = torch.empty(B, Kd, device=g.device, dtype=torch.float32) if gx is None else gx
+        assert gx_add is None or tuple(gx_add.shape) == (B, Kd)
+        ws = torch.empty(slices, B, Kd, device=g.device, dtype=torch.float32) if slices > 1 else None
+    else:
+        assert gx_add is None
+        gx = None
+    assert tuple(gw.shape) == (N, Kd) and gb.numel() == N
+    _lib.call('l2i_linear_rows_bwd_f32', _lib.fptr(gw), _lib.fptr(gb), _lib.fptr(gx), _lib.fptr(ws), _lib.fptr(gx_add), _lib.fptr(g), _lib.fptr(y), _lib.fptr(a),
+              _lib.fptr(x), _lib.fptr(w), B, Kd, N, int(epi), float(slope), slices)
+    return gw, gb, gx
 
 
 def face_resize(x, xbounds, xcoef, ybounds, ycoef):

@@ -4,6 +4,7 @@ kernels.  Same class / method names, argument meaning and error behaviour as the
     graphs/pggan/model_256.py:53-150,188-259     EqualConv2d / PixelNorm / ConvBlock / Generator(code_dim=511, n_label=1)
     graphs/pggan/pggan_256.py:11-51              PGGAN holder (netG / netD)
     graphs/pggan/transform_base.py:86-102        WalkLinearZ_free
+    graphs/pggan/transform_base.py:167-188       WalkMlpZ3 (the default walk: every --walk_type but 'linear')
     graphs/pggan/transform_base.py:211-510       TransformGraph (get_logits with the bilinear halving, get_z_new_tensor, get_reg_preds,
                                                  the clamp pair get_alphas, the [B,1,C] x [B,C] broadcast of get_reg_loss, the `or`
                                                  loss-weight rule of optimizeParametersAll), :596-640 apply_alpha
@@ -177,6 +178,68 @@ class WalkLinearZ_free(nn.Module):
 WalkLinearZ_free.__module__ = 'graphs.pggan.transform_base'            # pickles resolve in the reference's vis_w.py
 
 
+class _WalkMlpFn(torch.autograd.Function):
+    """z + alpha * L3(lrelu(L2(lrelu(L1(z))))) on l2i_linear_rows_f32 / _bwd_f32 (csrc/l2i_walk.hip): three launches forward, one pass per layer
+    backward.  Kept for the backward: z, h1, h2 (and a reference to alpha, an input); nothing when no input requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, keep, z, alpha, w1, b1, w2, b2, w3, b3):
+        zc, a = z.detach().contiguous(), alpha.detach().reshape(-1).contiguous()
+        P = [t.detach().contiguous() for t in (w1, b1, w2, b2, w3, b3)]
+        h1 = K.linear_rows(zc, P[0], P[1], K.LINEAR_LRELU, 0.2)
+        h2 = K.linear_rows(h1, P[2], P[3], K.LINEAR_LRELU, 0.2)
+        z_new = K.linear_rows(h2, P[4], P[5], K.LINEAR_WALK, res=zc, a=a)
+        if keep and any(ctx.needs_input_grad):                  # keep = the caller's grad mode (needs_input_grad is set under no_grad too)
+            ctx.save_for_backward(zc, h1, h2)
+            ctx.alpha, ctx.weights = a, (P[0], P[2], P[4])
+        return z_new
+
+    @staticmethod
+    def backward(ctx, g):
+        z, h1, h2 = ctx.saved_tensors
+        w1, w2, w3 = ctx.weights
+        g = g.contiguous()
+        gw3, gb3, g2 = K.linear_rows_bwd(g, h2, w3, K.LINEAR_WALK, a=ctx.alpha)
+        gw2, gb2, g1 = K.linear_rows_bwd(g2, h1, w2, K.LINEAR_LRELU, 0.2, y=h2)
+        want_z = ctx.needs_input_grad[1]
+        gw1, gb1, gz = K.linear_rows_bwd(g1, z, w1, K.LINEAR_LRELU, 0.2, y=h1, want_gx=want_z, gx_add=g if want_z else None)
+        return None, gz, None, gw1, gb1, gw2, gb2, gw3, gb3
+
+
+class WalkMlpZ3(nn.Module):
+    """The PGGAN graph's MLP walk (transform_base.py:167-188): z + alpha * MLP(z), MLP = dim_z -> 2 dim_z -> 2 dim_z -> dim_z with LeakyReLU(0.2).
+    ``self.linear`` is the reference's nn.Sequential, so default init, parameter order and state_dict keys (linear.0.weight ... linear.4.bias)
+    are the reference's; its modules are never called — forward runs one autograd.Function over the six parameters on the HIP kernels, in fp32
+    on every --precision.  ``alpha`` [B, 1] gets no gradient (it never requires one on this path: the Function returns None for it)."""
+
+    def __init__(self, dim_z, step, Nsliders, attrList):
+        super().__init__()
+        self.dim_z = dim_z
+        self.step = step
+        self.Nsliders = Nsliders
+        self.linear = nn.Sequential(*[nn.Linear(self.dim_z, self.dim_z * 2), nn.LeakyReLU(0.2, True), nn.Linear(self.dim_z * 2, self.dim_z * 2),
+                                      nn.LeakyReLU(0.2, True), nn.Linear(self.dim_z * 2, self.dim_z)])
+
+    def forward(self, input, alpha, layers=None, name=None, index_=None):
+        z = input.unsqueeze(0) if input.dim() == 1 else input              # a 1-D z is one sample: [1, dim_z] comes back, as broadcasting gives
+        dev = self.linear[0].weight.device
+        al = alpha.to(device=dev, dtype=torch.float32)
+        if al.dim() == 1:
+            al = al.unsqueeze(0)
+        if al.dim() != 2 or al.shape[1] != 1 or al.shape[0] not in (1, z.shape[0]):
+            # the reference's `al * out2` broadcasts [B, C] against [B, dim_z] and raises for every C but 1 (and dim_z, which no driver builds:
+            # the kernels take one alpha per row)
+            raise RuntimeError('WalkMlpZ3: alpha of shape %s against the walk direction of shape %s: alpha is one value per row, [B, 1]'
+                               % (tuple(alpha.shape), tuple(z.shape)))
+        if al.shape[0] != z.shape[0]:
+            al = al.expand(z.shape[0], 1)
+        lin = self.linear
+        return _WalkMlpFn.apply(torch.is_grad_enabled(), z.to(torch.float32), al, lin[0].weight, lin[0].bias, lin[2].weight, lin[2].bias, lin[4].weight, lin[4].bias)
+
+
+WalkMlpZ3.__module__ = 'graphs.pggan.transform_base'
+
+
 def load_networks(device, need_vgg=True):
     """Frozen nets of the PGGAN graph.  The reference hard-codes private checkpoint paths (transform_base.py:536-538, 578-582): a configured
     path that does not exist is an error unless synthetic weights were requested explicitly (graph._checkpoint_or_synthetic)."""
@@ -255,8 +318,8 @@ class TransformGraph:
         self.attrIdx = self.get_attr_idx()
         if walk_type == 'linear':
             self.walk = WalkLinearZ_free(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
-        else:
-            raise NotImplementedError('WalkMlpZ3 ("MLP", transform_base.py:279-283) is not on the config-1 path')
+        else:                                                    # "MLP" (transform_base.py:270-275): every other walk type
+            self.walk = WalkMlpZ3(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
         self.loss_scaler = getattr(netG, 'scaler', None)                # fp16 elements: the gradient scales the three networks share (load_networks)
         if self.loss_scaler is not None:
             from . import optim
@@ -394,7 +457,7 @@ class TransformGraph:
 def walk_training_step(graph, zs_batch, alpha_delta, no_content_loss=False, no_gan_loss=True):
     """One z-walk training step in the order of train_multi_attr.py:93-140 on the PGGAN graph's own methods.  (The shipped drivers call
     ``get_w`` / ``get_w_new_tensor``, which only the StyleGAN2 graph has; the PGGAN graph is driven method by method — this is that
-    sequence, used by the tests and by anyone running config 1.)  Returns (loss, x0, x1, alpha_org, alpha_target)."""
+    sequence; trainer.train_step routes a graph without ``get_w`` here.)  Returns (loss, x0, x1, alpha_org, alpha_target)."""
     z = zs_batch if torch.is_tensor(zs_batch) else torch.Tensor(zs_batch).to(graph.device)
     with torch.no_grad():
         out_zs = graph.get_logits({'z': z})

@@ -1,6 +1,7 @@
 """The training drivers' loop (reference train.py:25-134 and train_multi_attr.py:43-231), single process or one
 process per GPU.  Call order per iteration is the reference's: get_w -> get_logits -> get_reg_preds -> get_train_alpha ->
-get_alphas -> get_w_new_tensor -> get_logits -> optimizeParametersAll.  Under data parallelism every rank draws the same
+get_alphas -> get_w_new_tensor -> get_logits -> optimizeParametersAll (a graph without get_w, the PGGAN graph, runs
+pggan.walk_training_step).  Under data parallelism every rank draws the same
 z (seed = epoch) and the same alpha (same numpy seed) and takes every world-th sample of the batch (dist.shard: strided shards keep the discriminator's stddev groups whole)."""
 import logging
 import math
@@ -45,6 +46,17 @@ def make_samples(img_tensor, output_dir, epoch, optim_iter, batch_size, pre_path
 def train_step(graphs, zs_batch, attrList, layers=None, trainEmbed=False, updateGAN=False, opt=None, multi_attr=False):
     """One iteration of the hot loop.  ``zs_batch``: this rank's [B_local, 512] numpy slice.  Returns
     (loss tensor, alpha_for_target, out_zs, transformed_output)."""
+    if not hasattr(graphs, 'get_w'):
+        # the PGGAN graph (config 1) walks in z: no get_w / get_w_new_tensor; its own sequence is pggan.walk_training_step, and the alpha drawn
+        # here is the delta (train_multi_attr.py:113 on transform_base.py:358-364's clamp pair)
+        if opt is not None and getattr(opt, 'hip_graph', False):
+            raise NotImplementedError('--hip_graph records the StyleGAN2 step (capture.CapturedStep); the PGGAN z-walk step has no captured form yet')
+        from . import pggan
+        alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
+        loss, out_zs, transformed_output, _, _ = pggan.walk_training_step(graphs, torch.Tensor(zs_batch).to(graphs.device), alpha_for_graph,
+                                                                          no_content_loss=bool(opt and opt.no_content_loss),
+                                                                          no_gan_loss=bool(opt and opt.no_gan_loss))
+        return loss, alpha_for_target, out_zs, transformed_output
     if opt is not None and getattr(opt, 'hip_graph', False) and not trainEmbed and zs_batch.shape[0] == _captured_batch(graphs, zs_batch):
         # --hip_graph: the same calls, recorded once (capture.CapturedStep) and replayed; alpha is still drawn on the host
         alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)

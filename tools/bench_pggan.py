@@ -8,8 +8,13 @@ calls, median of 20, three alternating runs a side.
 (b) pggan.walk_training_step at 256^2, batch 4 and 8, f32 (the fp32 classes) / f16 / bf16, with and without the content term, synthetic
     weights: ms per step with all runs, the ratio to f32 and whether it lies inside the two sides' spread, the library calls of one step, and the
     three parts a step is made of timed alone (generator forward, regressor forward, one generator forward + backward) to say what holds a leg.
+(c) --walk: pggan.WalkMlpZ3 (dim_z 512) forward + backward at batch 4 and 8 on the l2i_linear_rows kernels against the plain-torch composite on the
+    same device and the same weights (the module's own nn.Sequential on rocBLAS plus autograd), with the library calls / torch ops of each side;
+    then the config-1 step with the default walk ('NNz': WalkMlpZ3) against 'linear', per precision.  A side counts as faster only when the gap
+    exceeds both spreads.
 
     python tools/bench_pggan.py [--out profiles/pggan16_bench.txt] [--skip_step] [--skip_kernels]
+    python tools/bench_pggan.py --walk --skip_step --skip_kernels --out profiles/walk_mlp_bench.txt
 """
 import argparse
 import os
@@ -92,12 +97,12 @@ def kernel_rows(b, ch, hw, prec, lines):
         print(lines[-1], flush=True)
 
 
-def _graph(prec, batch):
+def _graph(prec, batch, walk_type='linear'):
     from latent2im_amd import constants, conv
     from latent2im_amd import pggan as pg
     conv.PRECISION, constants.ALLOW_SYNTHETIC_WEIGHTS, constants.BATCH_SIZE = prec, True, batch
     np.random.seed(0)
-    return pg.faceGraph(lr=1e-3, walk_type='linear', loss='l2', trainEmbed=False, attrList=['Smiling'], attrTable={'Smiling': 31}, layers=None, pgan_opts=None)
+    return pg.faceGraph(lr=1e-3, walk_type=walk_type, loss='l2', trainEmbed=False, attrList=['Smiling'], attrTable={'Smiling': 31}, layers=None, pgan_opts=None)
 
 
 def step_rows(batch, lines):
@@ -153,6 +158,65 @@ def step_rows(batch, lines):
     conv.PRECISION = 'f32'
 
 
+def _verdict(a, b):
+    """'a faster' / 'b faster' only when the two sides' runs do not overlap, else 'inside the spread'."""
+    if max(a) < min(b):
+        return 'first faster (gap exceeds both spreads)'
+    if max(b) < min(a):
+        return 'second faster (gap exceeds both spreads)'
+    return "INSIDE the two sides' spread"
+
+
+def walk_rows(batch, lines):
+    """(c): the walk alone, kernels against the torch composite, then the step per walk type and precision."""
+    from latent2im_amd import conv, synth
+    from latent2im_amd import pggan as pg
+    torch.manual_seed(0)
+    walk = pg.WalkMlpZ3(512, 6, 1, ['Smiling']).cuda()
+    z = torch.Tensor(synth.z_sample(batch, seed=0)).cuda()
+    al = torch.full((batch, 1), 0.3, device='cuda')
+    r = torch.randn(batch, 512, device='cuda')
+
+    def hip():
+        walk.zero_grad(set_to_none=True)
+        (walk(z, al) * r).sum().backward()
+
+    def composite():
+        walk.zero_grad(set_to_none=True)
+        ((z + al * walk.linear(z)) * r).sum().backward()
+    runs = {'hip': [], 'torch': []}
+    for _ in range(3):
+        runs['hip'].append(timed(hip))
+        runs['torch'].append(timed(composite))
+    for name, fn in (('hip', hip), ('torch', composite)):
+        lines.append('walk dim_z 512  batch %d  fwd + bwd  %-28s %8.1f us (runs %s)   %d library calls'
+                     % (batch, 'l2i_linear_rows kernels' if name == 'hip' else 'nn.Sequential + autograd', 1e6 * statistics.median(runs[name]),
+                        ' '.join('%.1f' % (1e6 * v) for v in runs[name]), count_calls(fn)))
+        print(lines[-1], flush=True)
+    lines.append('walk dim_z 512  batch %d  kernels / composite %.3f   %s' % (batch, statistics.median(runs['hip']) / statistics.median(runs['torch']),
+                                                                             _verdict(runs['hip'], runs['torch'])))
+    print(lines[-1], flush=True)
+    ad = torch.full((batch, 1), 0.3, device='cuda')
+    for p in PRECS:
+        graphs = {w: _graph(p, batch, w) for w in ('NNz', 'linear')}
+        step = lambda g: pg.walk_training_step(g, z, ad, no_content_loss=False)
+        sruns = {w: [] for w in graphs}
+        for _ in range(3):
+            for w in graphs:
+                conv.PRECISION = p
+                sruns[w].append(timed(lambda: step(graphs[w])))
+        for w in graphs:
+            lines.append('%-4s step 256^2  batch %d  content on  walk %-6s %8.2f ms (runs %s)   %d library calls'
+                         % (p, batch, w, 1e3 * statistics.median(sruns[w]), ' '.join('%.2f' % (1e3 * v) for v in sruns[w]), count_calls(lambda: step(graphs[w]))))
+            print(lines[-1], flush=True)
+        lines.append('%-4s step 256^2  batch %d  NNz / linear %.3f   %s' % (p, batch, statistics.median(sruns['NNz']) / statistics.median(sruns['linear']),
+                                                                          _verdict(sruns['NNz'], sruns['linear'])))
+        print(lines[-1], flush=True)
+        del graphs
+        torch.cuda.empty_cache()
+    conv.PRECISION = 'f32'
+
+
 def _nograd(fn):
     with torch.no_grad():
         return fn()
@@ -163,6 +227,7 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--skip_step', action='store_true')
     ap.add_argument('--skip_kernels', action='store_true')
+    ap.add_argument('--walk', action='store_true', help='(c): the MLP walk on its kernels against the torch composite, and the step per walk type')
     args = ap.parse_args()
     lines = ['# tools/bench_pggan.py on %s' % torch.cuda.get_device_name(0),
              '# HIP events, 5 warm-up calls, median of 20, three alternating runs a side; kernels: cold inputs (> 512 MiB rotated per operand), GB/s of '
@@ -177,6 +242,10 @@ def main():
             step_rows(batch, lines)
             flush()
             torch.cuda.empty_cache()
+    if args.walk:
+        for batch in (4, 8):
+            walk_rows(batch, lines)
+            flush()
     if not args.skip_kernels:
         for prec in ('f16', 'bf16'):
             for b in (4, 8):
