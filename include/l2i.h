@@ -455,6 +455,21 @@ int l2i_nonfinite_flag_f32(const float* g, int64_t n, int32_t* state, void* stre
 int l2i_adam_guarded_f32(float* p, const float* g, float* m, float* v, float* step, int64_t n, float lr, float beta1, float beta2, float eps,
                          int32_t check_self, int32_t* state, float* scale, float growth, float backoff, int32_t interval, float max_scale,
                          int32_t last, void* stream);
+/* The same pair over a TABLE of tensors, many blocks a launch (the PGGAN graph's MLP walk: 2.1 M parameters in six tensors).  The table is passed
+ * to the kernels by value, so a captured graph bakes it in and no device-side descriptor exists.  Added under ABI 12: nothing existing changed. */
+#define L2I_ADAM_MAX_TENSORS 16
+typedef struct l2i_adam_tensor { float* p; const float* g; float* m; float* v; float* step; int64_t n; } l2i_adam_tensor;
+/* state[L2I_LS_FOUND] = 1 if any g of tensors[0..count) holds an inf / NaN: ONE launch, ceil(n / 4096) blocks a tensor; only g and n are read.
+ * Refused with L2I_E_ARG: a null table or state, count outside 1..L2I_ADAM_MAX_TENSORS, a null g, n <= 0. */
+int l2i_nonfinite_flag_multi_f32(const l2i_adam_tensor* tensors, int32_t count, int32_t* state, void* stream);
+/* The guarded Adam update of tensors[0..count), bit for bit what l2i_adam_guarded_f32(check_self = 0) computes tensor by tensor (same device
+ * function), each tensor with its own step counter: one multi-block update launch that reads state[L2I_LS_FOUND] and the counters and writes
+ * neither, then a one-wave launch that adds 1 to every counter when the flag is clear and, with last != 0, advances the scale state and clears
+ * the flag exactly as above.  16-byte accesses where p, g, m and v of a tensor share their offset to a 16-byte boundary, element by element
+ * otherwise; 4-byte alignment is enough.  Call l2i_nonfinite_flag_multi_f32 on every tensor of the step first.  Refused with L2I_E_ARG: as
+ * above, plus a null p, m, v or step, betas outside [0, 1), eps < 0, a scale with growth < 1 or backoff outside (0, 1]. */
+int l2i_adam_guarded_multi_f32(const l2i_adam_tensor* tensors, int32_t count, float lr, float beta1, float beta2, float eps, int32_t* state,
+                               float* scale, float growth, float backoff, int32_t interval, float max_scale, int32_t last, void* stream);
 /* [ABI 12] The momentum-SGD twin (BP.py:140: torch.optim.SGD(lr, momentum), dampening 0, no Nesterov, no weight decay), same single 1024-thread block.
  * With t = step[0] (a float counter on the device): t == 0: buf = g; otherwise buf = fl(fl(momentum * buf) + g); then p = fl(p - fl(lr * buf)) and
  * step[0] = t + 1 — every product and sum rounded to float32 on its own, no contraction.  "First step" is read from the device, so a captured graph

@@ -58,6 +58,14 @@ class SegmvSeg(ctypes.Structure):
                 ('e_off_c', c_i), ('e_off_b', c_i), ('e_bstride', c_i), ('rgb_off_b', c_i), ('rgb_w_off', c_i), ('part', SegmvPart * 2)]
 
 
+ADAM_MAX_TENSORS = 16     # L2I_ADAM_MAX_TENSORS
+
+
+class AdamTensor(ctypes.Structure):
+    """Mirror of ``struct l2i_adam_tensor`` (include/l2i.h): one row of the table the multi-tensor guarded Adam takes."""
+    _fields_ = [('p', c_p), ('g', c_p), ('m', c_p), ('v', c_p), ('step', c_p), ('n', c_l)]
+
+
 _SIGNATURES = {
     'l2i_conv2d_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_family': (c_i, [ctypes.POINTER(ConvParams)]),
@@ -119,6 +127,8 @@ _SIGNATURES = {
     'l2i_nonfinite_flag_f32': (c_i, [c_p, c_l, c_p, c_p]),
     'l2i_adam_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
     'l2i_sgd_guarded_f32': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_i, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
+    'l2i_nonfinite_flag_multi_f32': (c_i, [ctypes.POINTER(AdamTensor), c_i, c_p, c_p]),
+    'l2i_adam_guarded_multi_f32': (c_i, [ctypes.POINTER(AdamTensor), c_i, c_f, c_f, c_f, c_f, c_p, c_p, c_f, c_f, c_i, c_f, c_i, c_p]),
     'l2i_gram_loss_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_gram_loss_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

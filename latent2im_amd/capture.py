@@ -9,6 +9,8 @@ Python one launch at a time (~300 conv launches + ~500 small kernels per step). 
       -> walk -> synthesis (x1) -> D / VGG / regressor losses on their three streams (forked from and joined to the captured
          stream) -> backward into ``walk.grad``
 
+``CapturedZStep`` is the same for BASELINE config 1, the PGGAN graph's walk in z (pggan.walk_forward_backward): one stream, no noise.
+
 The all-reduce of the walk gradient (RCCL) and the Adam update stay OUTSIDE the graph, in the order optimizeParametersAll runs
 them: a handful of tiny launches, and the captured region holds no collective, so the same graph serves 1 and N ranks.
 Per-layer generator noise (networks.py:281-286) is drawn inside the graph from torch's graph-safe Philox stream (fresh values every
@@ -62,19 +64,40 @@ def forward_backward(g, z, alpha_for_graph, no_content_loss=False, no_gan_loss=F
     return r
 
 
-class CapturedStep:
+class _StagedInputs:
+    """The static device inputs of a captured step — ``z`` [B, dim_z] and ``alpha`` [B, n_attr] — and their refill from the host."""
+
+    def _init_inputs(self, dev, batch, dim_z, n_attr):
+        self.z = torch.zeros(batch, dim_z, device=dev)
+        self.alpha = torch.zeros(batch, n_attr, device=dev)
+        # pinned staging ring: the host runs several replays ahead of the GPU (no per-step sync in bench.py / trainer --no_log_sync), so a
+        # slot is rewritten only after the H2D copies that read it have run (one event per slot)
+        self._ring = [(torch.zeros(batch, dim_z).pin_memory(), torch.zeros(batch, n_attr).pin_memory(), torch.cuda.Event()) for _ in range(4)]
+        self._ring_used = [False] * len(self._ring)
+        self._slot = 0
+
+    def load(self, zs, alpha):
+        """Host -> the graph's static inputs (pinned staging ring, asynchronous on the current stream)."""
+        i = self._slot
+        self._slot = (i + 1) % len(self._ring)
+        stage_z, stage_a, ev = self._ring[i]
+        if self._ring_used[i]:
+            ev.synchronize()                                  # the copies that last read this slot have completed
+        stage_z.copy_(torch.as_tensor(np.asarray(zs), dtype=torch.float32))
+        stage_a.copy_(torch.as_tensor(np.asarray(alpha), dtype=torch.float32))
+        self.z.copy_(stage_z, non_blocking=True)
+        self.alpha.copy_(stage_a, non_blocking=True)
+        ev.record()
+        self._ring_used[i] = True
+
+
+class CapturedStep(_StagedInputs):
     """``step(zs, alpha)`` == selfcheck.run_step(g, zs, alpha, ...) with the forward+backward replayed from one hipGraph."""
 
     def __init__(self, g, batch, n_attr, no_content_loss=False, no_gan_loss=False, clamp=False, layers=None, warmup=2):
         self.g = g
         dev = g.device
-        self.z = torch.zeros(batch, g.dim_z, device=dev)
-        self.alpha = torch.zeros(batch, n_attr, device=dev)
-        # pinned staging ring: the host runs several replays ahead of the GPU (no per-step sync in bench.py / trainer --no_log_sync), so a
-        # slot is rewritten only after the H2D copies that read it have run (one event per slot)
-        self._ring = [(torch.zeros(batch, g.dim_z).pin_memory(), torch.zeros(batch, n_attr).pin_memory(), torch.cuda.Event()) for _ in range(4)]
-        self._ring_used = [False] * len(self._ring)
-        self._slot = 0
+        self._init_inputs(dev, batch, g.dim_z, n_attr)
         kw = dict(no_content_loss=no_content_loss, no_gan_loss=no_gan_loss, clamp=clamp, layers=layers)
         # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights), as stream capture requires
         s = torch.cuda.Stream(device=dev)
@@ -95,20 +118,6 @@ class CapturedStep:
         self._ws_keep = list(conv._WS.values())
         self.launches = None
 
-    def load(self, zs, alpha):
-        """Host -> the graph's static inputs (pinned staging ring, asynchronous on the current stream)."""
-        i = self._slot
-        self._slot = (i + 1) % len(self._ring)
-        stage_z, stage_a, ev = self._ring[i]
-        if self._ring_used[i]:
-            ev.synchronize()                                  # the copies that last read this slot have completed
-        stage_z.copy_(torch.as_tensor(np.asarray(zs), dtype=torch.float32))
-        stage_a.copy_(torch.as_tensor(np.asarray(alpha), dtype=torch.float32))
-        self.z.copy_(stage_z, non_blocking=True)
-        self.alpha.copy_(stage_a, non_blocking=True)
-        ev.record()
-        self._ring_used[i] = True
-
     def __call__(self, zs=None, alpha=None, optimize=True):
         if zs is not None:
             self.load(zs, alpha)
@@ -120,4 +129,57 @@ class CapturedStep:
             self.g.optimizers.step()
         o = dict(self.out)
         o['grad'] = self.grads[0]
+        return o
+
+
+class CapturedZStep(_StagedInputs):
+    """``step(zs, alpha_delta)`` == pggan.walk_training_step(g, zs, alpha_delta, ...) on the PGGAN graph (BASELINE config 1) with
+    pggan.walk_forward_backward replayed from one hipGraph: the no-grad first pass, the clamp pair on the device, the walk in z, the second
+    generator pass, zero_grad, loss and backward, all on one stream (no loss-branch forks: the recorded graph is a chain) and without noise.
+    The all-reduce and the optimiser step (pggan.walk_update: torch's Adam, or GuardedAdam's two library calls on fp16) follow every replay
+    outside the graph, so one graph serves 1 and N ranks.  The warm-up before capture runs loss and backward only, never the update: the walk,
+    the optimiser state and the scaler are what an eager run starts from.  The GAN term cannot be evaluated on this graph (pggan.py) and is off."""
+
+    def __init__(self, g, batch, n_attr, no_content_loss=False, warmup=2):
+        from . import conv
+        self.g = g
+        dev = g.device
+        self.no_content_loss = bool(no_content_loss)
+        self._init_inputs(dev, batch, g.dim_z, n_attr)
+        init_state = getattr(g.optimizer, 'init_state', None)
+        if init_state is not None:
+            init_state()                                                   # GuardedAdam: moments, counters and guard words outside the graph's pool
+        # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights, the attribute-column index), as capture requires
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(max(warmup, 1)):
+                self._forward_backward()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g.optimizer.zero_grad(set_to_none=True)                           # the gradients become static tensors of the graph's pool
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out = self._forward_backward()
+        self.grads = [p.grad for p in g.walk.parameters()]
+        self._ws_keep = list(conv._WS.values())                            # the kernel nodes hold raw pointers into the split-K workspaces
+
+    def _forward_backward(self):
+        """One pggan.walk_forward_backward on the static inputs -> its results, detached: no reference to the autograd graph survives the call.
+        One that did would keep the walk's gradient accumulators on the warm-up's stream, and the capture would fork to that stream."""
+        from . import pggan
+        loss, x0, x1, a0, target = pggan.walk_forward_backward(self.g, self.z, self.alpha, no_content_loss=self.no_content_loss, no_gan_loss=True)
+        return dict(loss=loss.detach(), x0=x0.detach(), x1=x1.detach(), a0=a0.detach(), target=target.detach(), terms=self.g.last_terms)
+
+    def __call__(self, zs=None, alpha_delta=None, optimize=True):
+        from . import pggan
+        if zs is not None:
+            self.load(zs, alpha_delta)
+        self.graph.replay()
+        for p, gr in zip(self.g.walk.parameters(), self.grads):           # the optimiser reads p.grad: the graph's static gradient tensors
+            p.grad = gr
+        if optimize:
+            pggan.walk_update(self.g)
+        o = dict(self.out)
+        o['grads'] = self.grads
         return o

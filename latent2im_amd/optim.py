@@ -11,8 +11,10 @@ the only sync of the reference loop, and the hipGraph replay of config 5 has non
                   dynamic power of two ``scale[0]`` (1.0 at start).  Every branch multiplies the gradient it receives by static * dynamic
                   (a device tensor, so a captured hipGraph sees every update) and the generator's latent gradient by the inverse: walk.grad is the
                   true gradient, or non-finite if anything overflowed on the way.
-``GuardedAdam`` — torch.optim.Adam whose step() is one launch of l2i_adam_guarded_f32 per parameter tensor: finite check, update or skip,
-                  scale-state update.  Same state layout as torch's (exp_avg, exp_avg_sq, step) so state_dict() round-trips.
+``GuardedAdam`` — torch.optim.Adam whose step() is one launch of l2i_adam_guarded_f32 for a single parameter tensor (finite check, update or
+                  skip, scale-state update) and, for several tensors, two library calls per 16 of them: l2i_nonfinite_flag_multi_f32 over every
+                  gradient, then l2i_adam_guarded_multi_f32 (a multi-block update and a one-wave tail).  Same state layout as torch's
+                  (exp_avg, exp_avg_sq, step) so state_dict() round-trips.
 ``GuardedSGD``  — torch.optim.SGD(lr, momentum) the same way on l2i_sgd_guarded_f32 (BP.py:140, the inversion's 'GD'): torch's momentum_buffer plus a
                   device-side ``step`` that tells the kernel whether the buffer is still to be initialised, so a captured graph replays the step.
 """
@@ -89,8 +91,9 @@ def _guarded_step(opt, todo, launch):
 
 
 class GuardedAdam(torch.optim.Adam):
-    """torch.optim.Adam(params, lr, betas) for float32 CUDA parameters with the update on l2i_adam_guarded_f32: skipped as a whole when any gradient
-    of the step is non-finite; ``scaler`` (a LossScaler or None) is advanced by the last launch of the step."""
+    """torch.optim.Adam(params, lr, betas) for float32 CUDA parameters with the update on l2i_adam_guarded_f32 (one tensor) or
+    l2i_adam_guarded_multi_f32 (several): skipped as a whole when any gradient of the step is non-finite; ``scaler`` (a LossScaler or None) is
+    advanced by the last launch of the step."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scaler=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps)
@@ -125,11 +128,40 @@ class GuardedAdam(torch.optim.Adam):
                 _check_param(p, 'GuardedAdam')
                 todo.append((p, group, self._state_of(p)))
 
+        if len(todo) > 1:
+            return self._step_multi(todo)
+
         def launch(p, g, group, st, guard, stream):
             b1, b2 = group['betas']
             _lib.call('l2i_adam_guarded_f32', _lib.fptr(p), _lib.fptr(g), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']),
                       p.numel(), float(group['lr']), float(b1), float(b2), float(group['eps']), *guard, stream=stream)
         return _guarded_step(self, todo, launch)
+
+    def _step_multi(self, todo):
+        """A step over several tensors: chunks of one param group and at most _lib.ADAM_MAX_TENSORS tensors; every chunk's gradients are flagged
+        before the first update, the last update call advances the scale state."""
+        state, scale = self._flags(todo[0][0].device)
+        sc = self.scaler
+        stream = _lib.stream_ptr()
+        chunks, keep = [], []
+        for p, group, st in todo:
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            if not (st['exp_avg'].is_contiguous() and st['exp_avg_sq'].is_contiguous()):
+                raise _lib.L2IError('GuardedAdam updates contiguous moments only')
+            keep.append(g)
+            row = _lib.AdamTensor(_lib.fptr(p), _lib.fptr(g), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']), p.numel())
+            if not chunks or chunks[-1][0] is not group or len(chunks[-1][1]) == _lib.ADAM_MAX_TENSORS:
+                chunks.append((group, []))
+            chunks[-1][1].append(row)
+        tables = [(group, (_lib.AdamTensor * len(rows))(*rows), len(rows)) for group, rows in chunks]
+        for _, table, count in tables:
+            _lib.call('l2i_nonfinite_flag_multi_f32', table, count, _lib.ptr(state), stream=stream)
+        for i, (group, table, count) in enumerate(tables):
+            b1, b2 = group['betas']
+            _lib.call('l2i_adam_guarded_multi_f32', table, count, float(group['lr']), float(b1), float(b2), float(group['eps']), _lib.ptr(state),
+                      _lib.ptr(scale), float(sc.GROWTH if sc else 2.0), float(sc.BACKOFF if sc else 0.5), int(sc.growth_interval if sc else 0),
+                      float(sc.max_scale if sc else 1.0), 1 if i == len(tables) - 1 else 0, stream=stream)
+        return None
 
 
 class GuardedSGD(torch.optim.SGD):

@@ -46,7 +46,8 @@ class TrainOptions:
         p.add_argument('--seed', type=int, default=None, help='seed numpy global RNG (walk init, alpha draws)')
         p.add_argument('--no_log_sync', action='store_true', help='do not read the loss back every step (train.py:110)')
         p.add_argument('--hip_graph', action='store_true',
-                       help='record forward+backward of the step once and replay it from one hipGraph per iteration (static batch size)')
+                       help='record forward+backward of the step once and replay it from one hipGraph per iteration (static batch size; the StyleGAN2 '
+                            'graphs and the PGGAN z-walk)')
         p.add_argument('--precision', type=str, default=None, choices=['f32', 'bf16x3', 'bf16', 'f16'],
                        help='matrix path of the frozen networks: exact fp32 MFMA (default), the 3-term bf16 split on fp32 tensors (fp32 accuracy), '
                             'or the 16-bit path (16-bit feature maps in HBM, one 16-bit MFMA per MAC, fp32 accumulation; BASELINE config 5): '

@@ -402,6 +402,12 @@ class TransformGraph:
 
     optimize_parameters = optimizeParametersAll
 
+    def captured_z_step(self, batch, n_attr, no_content_loss=False):
+        """The step as a hipGraph for ``batch`` samples a replay (capture.CapturedZStep): what trainer.train_step asks a graph without get_w for
+        under --hip_graph."""
+        from . import capture
+        return capture.CapturedZStep(self, batch, n_attr, no_content_loss=no_content_loss)
+
     def save_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
         print('Save W and GAN in %s and %s' % (save_path_w, save_path_gan))
         if updateGAN:
@@ -454,21 +460,39 @@ class TransformGraph:
         raise NotImplementedError('Subclass should implement vis_image_batch')
 
 
-def walk_training_step(graph, zs_batch, alpha_delta, no_content_loss=False, no_gan_loss=True):
-    """One z-walk training step in the order of train_multi_attr.py:93-140 on the PGGAN graph's own methods.  (The shipped drivers call
-    ``get_w`` / ``get_w_new_tensor``, which only the StyleGAN2 graph has; the PGGAN graph is driven method by method — this is that
-    sequence; trainer.train_step routes a graph without ``get_w`` here.)  Returns (loss, x0, x1, alpha_org, alpha_target)."""
-    z = zs_batch if torch.is_tensor(zs_batch) else torch.Tensor(zs_batch).to(graph.device)
+def walk_forward_backward(graph, z, alpha_delta, no_content_loss=False, no_gan_loss=True):
+    """The z-walk step up to the walk gradient, on DEVICE inputs and without a host synchronisation (capture.CapturedZStep records exactly this
+    call): the no-grad first pass, the clamp pair, the walk, the second generator pass, zero_grad, loss and backward.  Leaves d loss / d walk
+    in the walk's ``.grad``.  Returns (loss, x0, x1, alpha_org, alpha_target)."""
     with torch.no_grad():
         out_zs = graph.get_logits({'z': z})
         alpha_org = graph.get_reg_preds(out_zs)
-    ad = alpha_delta if torch.is_tensor(alpha_delta) else torch.tensor(np.asarray(alpha_delta)).float().to(graph.device)
-    alpha_target, alpha_delta_new = graph.get_alphas(alpha_org, ad)
+    alpha_target, alpha_delta_new = graph.get_alphas(alpha_org, alpha_delta)
     z_new = graph.get_z_new_tensor(z, alpha_delta_new)
     transformed_output = graph.get_logits({'z': z_new})
     feed_dict = {'z': z_new, 'org': out_zs, 'logit': transformed_output, 'alpha': alpha_target}
-    loss = graph.optimizeParametersAll(feed_dict, trainEmbed=False, updateGAN=False, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
+    graph.optimizer.zero_grad()
+    loss = graph.get_w_loss(feed_dict, no_content_loss, no_gan_loss)
+    loss.backward()
     return loss, out_zs, transformed_output, alpha_org, alpha_target
+
+
+def walk_update(graph):
+    """The tail of the step (optimizeParametersAll's last two lines): all-reduce of the walk gradient, optimiser step."""
+    dist.average_gradients(graph.walk.parameters())
+    graph.optimizer.step()
+
+
+def walk_training_step(graph, zs_batch, alpha_delta, no_content_loss=False, no_gan_loss=True):
+    """One z-walk training step in the order of train_multi_attr.py:93-140 on the PGGAN graph's own methods.  (The shipped drivers call
+    ``get_w`` / ``get_w_new_tensor``, which only the StyleGAN2 graph has; the PGGAN graph is driven method by method — this is that
+    sequence; trainer.train_step routes a graph without ``get_w`` here.)  walk_forward_backward + walk_update: the two parts the captured step
+    (capture.CapturedZStep) replays and runs.  Returns (loss, x0, x1, alpha_org, alpha_target)."""
+    z = zs_batch if torch.is_tensor(zs_batch) else torch.Tensor(zs_batch).to(graph.device)
+    ad = alpha_delta if torch.is_tensor(alpha_delta) else torch.tensor(np.asarray(alpha_delta)).float().to(graph.device)
+    r = walk_forward_backward(graph, z, ad, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
+    walk_update(graph)
+    return r
 
 
 class _Half(torch.autograd.Function):

@@ -49,10 +49,16 @@ def train_step(graphs, zs_batch, attrList, layers=None, trainEmbed=False, update
     if not hasattr(graphs, 'get_w'):
         # the PGGAN graph (config 1) walks in z: no get_w / get_w_new_tensor; its own sequence is pggan.walk_training_step, and the alpha drawn
         # here is the delta (train_multi_attr.py:113 on transform_base.py:358-364's clamp pair)
-        if opt is not None and getattr(opt, 'hip_graph', False):
-            raise NotImplementedError('--hip_graph records the StyleGAN2 step (capture.CapturedStep); the PGGAN z-walk step has no captured form yet')
+        hip_graph = opt is not None and getattr(opt, 'hip_graph', False)
+        if hip_graph and not hasattr(graphs, 'captured_z_step'):
+            raise NotImplementedError('--hip_graph records the StyleGAN2 step (capture.CapturedStep) or the PGGAN z-walk step (capture.CapturedZStep); '
+                                      'this graph offers neither')
         from . import pggan
         alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
+        # --hip_graph: the same step, recorded once and replayed (a ragged last batch, and the GAN term, which raises, run eagerly)
+        if hip_graph and opt.no_gan_loss and not trainEmbed and zs_batch.shape[0] == _captured_z_batch(graphs, zs_batch, alpha_for_graph, opt):
+            r = graphs._captured_step(zs_batch, alpha_for_graph)
+            return r['loss'], alpha_for_target, r['x0'], r['x1']
         loss, out_zs, transformed_output, _, _ = pggan.walk_training_step(graphs, torch.Tensor(zs_batch).to(graphs.device), alpha_for_graph,
                                                                           no_content_loss=bool(opt and opt.no_content_loss),
                                                                           no_gan_loss=bool(opt and opt.no_gan_loss))
@@ -91,6 +97,14 @@ def _captured_batch(graphs, zs_batch):
         o = graphs._captured_opts
         st = graphs._captured_step = capture.CapturedStep(graphs, zs_batch.shape[0], len(o['attrList']), clamp=o['multi_attr'], layers=o['layers'],
                                                           no_content_loss=o['no_content_loss'], no_gan_loss=o['no_gan_loss'])
+    return st.z.shape[0]
+
+
+def _captured_z_batch(graphs, zs_batch, alpha_for_graph, opt):
+    """The same for a graph that walks in z (the PGGAN graph's captured_z_step)."""
+    st = getattr(graphs, '_captured_step', None)
+    if st is None:
+        st = graphs._captured_step = graphs.captured_z_step(zs_batch.shape[0], np.asarray(alpha_for_graph).shape[1], no_content_loss=bool(opt.no_content_loss))
     return st.z.shape[0]
 
 

@@ -13,8 +13,19 @@ calls, median of 20, three alternating runs a side.
     then the config-1 step with the default walk ('NNz': WalkMlpZ3) against 'linear', per precision.  A side counts as faster only when the gap
     exceeds both spreads.
 
+(d) --hip_graph: the config-1 step launched eagerly (pggan.walk_training_step) against replayed (capture.CapturedZStep, static inputs already on
+    the device, as the eager side's are), MLP and linear walk, f32 / f16 / bf16, batch 4 and 8, the two sides sharing the frozen networks.
+    --parent DIR: a checkout of the parent commit with its own library built; the eager step of parent and branch is then compared on one
+    protocol and one code path: each checkout's own --walk leg in child processes, parent and branch alternating, two children a side (same lease;
+    every child contributes three runs to its side's spread).
+(e) --adam: GuardedAdam's step alone on the MLP walk's six tensors (2.1 M parameters): l2i_nonfinite_flag_multi_f32 + l2i_adam_guarded_multi_f32
+    against the per-tensor path (six l2i_nonfinite_flag_f32 + six l2i_adam_guarded_f32 launches), us and GB/s of the least traffic (the gradient
+    twice, parameter and moments read and written: 32 bytes an element).
+
     python tools/bench_pggan.py [--out profiles/pggan16_bench.txt] [--skip_step] [--skip_kernels]
     python tools/bench_pggan.py --walk --skip_step --skip_kernels --out profiles/walk_mlp_bench.txt
+    python tools/bench_pggan.py --hip_graph --parent ../parent --skip_step --skip_kernels --out profiles/pggan_graph_bench.txt
+    python tools/bench_pggan.py --adam --skip_step --skip_kernels --out profiles/adam_multi_bench.txt
 """
 import argparse
 import os
@@ -217,6 +228,105 @@ def walk_rows(batch, lines):
     conv.PRECISION = 'f32'
 
 
+def graph_rows(batch, lines, results):
+    """(d): eager against replayed, per precision and walk type; ``results[(prec, walk, batch)]`` = the eager runs (for the parent comparison)."""
+    from latent2im_amd import capture, constants, conv, synth
+    from latent2im_amd import pggan as pg
+    zs = synth.z_sample(batch, seed=0)
+    z = torch.Tensor(zs).cuda()
+    ad_np = np.full((batch, 1), 0.3)
+    ad = torch.full((batch, 1), 0.3, device='cuda')
+    for p in PRECS:
+        conv.PRECISION, constants.ALLOW_SYNTHETIC_WEIGHTS, constants.BATCH_SIZE = p, True, batch
+        nets = pg.load_networks(torch.device('cuda', torch.cuda.current_device()))
+        for w in ('NNz', 'linear'):
+            np.random.seed(0)
+            mk = lambda: pg.faceGraph(lr=1e-3, walk_type=w, loss='l2', trainEmbed=False, attrList=['Smiling'], attrTable={'Smiling': 31}, layers=None,
+                                      pgan_opts=None, nets=nets)
+            ge, gc_ = mk(), mk()
+            eager_fn = lambda: pg.walk_training_step(ge, z, ad, no_content_loss=False)
+            alone = timed(eager_fn)                                          # before anything is captured in this process for these networks
+            step = capture.CapturedZStep(gc_, batch, 1)
+            step.load(zs, ad_np)
+            sides = {'eager': eager_fn, 'replayed': lambda: step()}
+            runs = {k: [] for k in sides}
+            for _ in range(3):
+                for k, fn in sides.items():
+                    runs[k].append(timed(fn))
+            results[(p, w, batch)] = runs['eager']
+            for k, fn in sides.items():
+                row = '%-4s step 256^2  batch %d  content on  walk %-6s %-8s %8.2f ms (runs %s)   %d library calls' % (
+                    p, batch, w, k, 1e3 * statistics.median(runs[k]), ' '.join('%.2f' % (1e3 * v) for v in runs[k]), count_calls(fn))
+                sc = ge.loss_scaler
+                if k == 'eager':
+                    row += '   (one run before the capture: %.2f ms)' % (1e3 * alone)
+                lines.append(row + ('' if sc is None else '   scaler %s' % sc.stats()))
+                print(lines[-1], flush=True)
+            lines.append('%-4s step 256^2  batch %d  walk %-6s replayed / eager %.3f   %s' % (
+                p, batch, w, statistics.median(runs['replayed']) / statistics.median(runs['eager']), _verdict(runs['replayed'], runs['eager'])))
+            print(lines[-1], flush=True)
+            del ge, gc_, step, sides, eager_fn
+        del nets
+        torch.cuda.empty_cache()
+    conv.PRECISION = 'f32'
+
+
+def child_walk_rows(tree, tag):
+    """The --walk leg of the checkout at ``tree`` (the parent's, or this one) in a child process of its own -> {(prec, walk, batch): [runs in s]}
+    from its step rows, and the rows themselves."""
+    import re
+    import subprocess
+    import tempfile
+    out = os.path.join(tempfile.mkdtemp(), 'parent_walk.txt')
+    tool = os.path.join(os.path.abspath(tree), 'tools', 'bench_pggan.py')
+    subprocess.run([sys.executable, tool, '--walk', '--skip_step', '--skip_kernels', '--out', out], cwd=os.path.abspath(tree), check=True,
+                   stdout=subprocess.DEVNULL, timeout=600)
+    runs, rows = {}, []
+    for line in open(out):
+        m = re.match(r'(\w+)\s+step 256\^2\s+batch (\d+)\s+content on\s+walk (\w+)\s+[\d.]+ ms \(runs ([\d. ]+)\)', line)
+        if m:
+            runs[(m.group(1), m.group(3), int(m.group(2)))] = [1e-3 * float(v) for v in m.group(4).split()]
+            rows.append('%-16s %s' % (tag, line.rstrip()))
+    return runs, rows
+
+
+def adam_rows(lines):
+    """(e): the guarded update alone on the MLP walk's six tensors."""
+    from latent2im_amd import _lib, optim
+    torch.manual_seed(0)
+    shapes = [(1024, 512), (1024,), (1024, 1024), (1024,), (512, 1024), (512,)]
+    ps = [torch.nn.Parameter(torch.randn(*s, device='cuda') * 0.05) for s in shapes]
+    for q in ps:
+        q.grad = torch.randn_like(q)
+    n = sum(q.numel() for q in ps)
+    sc = optim.LossScaler(dict(R=0, V=0, D=0, G=0), 'cuda')
+    opt = optim.GuardedAdam(ps, lr=1e-3, betas=(0.5, 0.99), scaler=sc)
+    opt.init_state()
+
+    def per_tensor():
+        state, scale = _lib.ptr(sc.state), _lib.ptr(sc.scale)
+        for q in ps:
+            _lib.call('l2i_nonfinite_flag_f32', _lib.fptr(q.grad), q.numel(), state)
+        for i, q in enumerate(ps):
+            st = opt.state[q]
+            _lib.call('l2i_adam_guarded_f32', _lib.fptr(q.data), _lib.fptr(q.grad), _lib.fptr(st['exp_avg']), _lib.fptr(st['exp_avg_sq']), _lib.fptr(st['step']),
+                      q.numel(), 1e-3, 0.5, 0.99, 1e-8, 0, state, scale, 2.0, 0.5, sc.growth_interval, sc.max_scale, 1 if i == len(ps) - 1 else 0)
+    sides = {'multi-tensor (2 calls, 3 kernels)': opt.step, 'per tensor (12 calls, 12 kernels)': per_tensor}
+    runs = {k: [] for k in sides}
+    for _ in range(3):
+        for k, fn in sides.items():
+            runs[k].append(timed(fn))
+    for k, fn in sides.items():
+        m = statistics.median(runs[k])
+        lines.append('guarded Adam, MLP walk (6 tensors, %d parameters)  %-34s %8.1f us (runs %s)  %6.0f GB/s  %d library calls'
+                     % (n, k, 1e6 * m, ' '.join('%.1f' % (1e6 * v) for v in runs[k]), 32.0 * n / m / 1e9, count_calls(fn)))
+        print(lines[-1], flush=True)
+    a, b = list(runs.values())
+    lines.append('guarded Adam  multi-tensor / per tensor %.3f   %s' % (statistics.median(a) / statistics.median(b), _verdict(a, b)))
+    print(lines[-1], flush=True)
+    lines.append('scaler after the timing: %s' % sc.stats())
+
+
 def _nograd(fn):
     with torch.no_grad():
         return fn()
@@ -228,6 +338,9 @@ def main():
     ap.add_argument('--skip_step', action='store_true')
     ap.add_argument('--skip_kernels', action='store_true')
     ap.add_argument('--walk', action='store_true', help='(c): the MLP walk on its kernels against the torch composite, and the step per walk type')
+    ap.add_argument('--hip_graph', action='store_true', help='(d): the config-1 step eager against replayed from the captured graph')
+    ap.add_argument('--parent', default=None, help='(d): a built checkout of the parent commit: its --walk leg and this checkout\'s run alternately in child processes')
+    ap.add_argument('--adam', action='store_true', help="(e): the guarded Adam step alone on the MLP walk's six tensors")
     args = ap.parse_args()
     lines = ['# tools/bench_pggan.py on %s' % torch.cuda.get_device_name(0),
              '# HIP events, 5 warm-up calls, median of 20, three alternating runs a side; kernels: cold inputs (> 512 MiB rotated per operand), GB/s of '
@@ -246,6 +359,32 @@ def main():
         for batch in (4, 8):
             walk_rows(batch, lines)
             flush()
+    if args.hip_graph:
+        results = {}
+        for batch in (4, 8):
+            graph_rows(batch, lines, results)
+            flush()
+        if args.parent:
+            # branch against parent, eager, on the same protocol and code path: each side's own --walk leg in child processes, alternating
+            sides = {'parent': {}, 'branch': {}}
+            for rnd in (1, 2):
+                for name, tree in (('parent', args.parent), ('branch', ROOT)):
+                    runs, rows = child_walk_rows(tree, '%s (child %d)' % (name, rnd))
+                    lines.extend(rows)
+                    for key, v in runs.items():
+                        sides[name].setdefault(key, []).extend(v)
+                    flush()
+            for key in sorted(sides['branch']):
+                if key in sides['parent']:
+                    b, a = sides['branch'][key], sides['parent'][key]
+                    lines.append('%-4s step 256^2  batch %d  walk %-6s eager: branch %.2f ms / parent %.2f ms = %.3f   %s' % (
+                        key[0], key[2], key[1], 1e3 * statistics.median(b), 1e3 * statistics.median(a), statistics.median(b) / statistics.median(a),
+                        _verdict(b, a)))
+                    print(lines[-1], flush=True)
+        flush()
+    if args.adam:
+        adam_rows(lines)
+        flush()
     if not args.skip_kernels:
         for prec in ('f16', 'bf16'):
             for b in (4, 8):
