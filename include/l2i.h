@@ -580,6 +580,27 @@ int l2i_linear_rows_f32(float* y, const float* x, const float* w, const float* b
 int l2i_linear_rows_bwd_f32(float* gw, float* gb, float* gx, float* ws, const float* gx_add, const float* g, const float* y, const float* a,
                             const float* x, const float* w, int B, int K, int N, int epi, float slope, int slices, void* stream);
 
+/* ---- Range histogram of a stored map (csrc/l2i_range.hip): the device-side statistic behind nets16.RangeMonitor --------------------------------------
+ * x = n consecutive elements of `kind` (an h8 map: every stored element, channel padding included — zeros, which move neither the maximum nor
+ * the non-zero statistics).  row = L2I_RANGE_WORDS 64-bit words on the device; the call ADDS to it and never clears it (the host clears it):
+ *   row[0..255]          elements whose value, converted exactly to fp32, has biased exponent field e: field 0 = zeros and fp32 subnormals, field
+ *                        255 = inf / NaN; fp16 subnormals land in fields 103..112, fp16's smallest normal in 113
+ *   row[L2I_RANGE_ZEROS] elements that are exactly +-0 (a subset of field 0)
+ *   row[L2I_RANGE_MAX]   the largest |x| over the FINITE elements as its fp32 bit pattern (an unsigned maximum)
+ *   row[L2I_RANGE_CALLS] calls that added to the row;  row[L2I_RANGE_N]  elements added (n summed)
+ * Integer adds and maxima only: the row is bit-reproducible whatever the order in which blocks, streams or hipGraph replays arrive.  16-byte loads
+ * over the aligned body, single elements in front of and behind it: x needs the alignment of its element type only.  n <= 0, a null pointer, an
+ * unknown kind or a misaligned x / row returns L2I_E_ARG; more than 2^40 elements L2I_E_UNSUPPORTED.  Additive: the ABI version did not move. */
+#define L2I_RANGE_F16 0      /* IEEE fp16 elements (h8 maps of the f16 path) */
+#define L2I_RANGE_BF16 1
+#define L2I_RANGE_F32 2
+#define L2I_RANGE_WORDS 260
+#define L2I_RANGE_ZEROS 256
+#define L2I_RANGE_MAX 257
+#define L2I_RANGE_CALLS 258
+#define L2I_RANGE_N 259
+int l2i_range_stats(uint64_t* row, const void* x, int64_t n, int kind, void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
  * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins; 12: l2i_sgd_guarded_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */

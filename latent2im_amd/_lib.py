@@ -137,6 +137,7 @@ _SIGNATURES = {
     'l2i_pixelnorm_act_bwd_h8': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p]),
     'l2i_linear_rows_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
     'l2i_linear_rows_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'l2i_range_stats': (c_i, [c_p, c_p, c_l, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
     'l2i_sizeof_conv_params': (c_i, []),

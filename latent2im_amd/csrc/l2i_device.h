@@ -131,6 +131,25 @@ __device__ __forceinline__ T block_sum(T v, T* red) {             // fixed order
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
+// wave64 / 256-thread block maximum in every thread, the same way (l2i_range.hip: the largest magnitude of a map, as an unsigned bit pattern)
+template <typename T>
+__device__ __forceinline__ T wave_max_all(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T o = __shfl_xor(v, off);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T block_max(T v, T* red) {
+    v = wave_max_all(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const T a = red[0] > red[1] ? red[0] : red[1], b = red[2] > red[3] ? red[2] : red[3];
+    return a > b ? a : b;
+}
 __device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }   // magic 0 encodes d == 1; else ceil(2^32 / d)
 
 #endif

@@ -442,6 +442,38 @@ class TransformGraph:
 
     optimize_parameters = optimizeParametersAll              # BASELINE.json spelling
 
+    def calibrate_scales(self, n_steps, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False):
+        """--f16_calibrate: measure the fp16 path's static gradient exponents on THIS graph's weights (nets16.calibrate: ``n_steps`` probe steps a
+        round — forward, loss and backward as capture.forward_backward runs them for these loss flags, fresh z and alpha draws, no optimiser step —
+        with a nets16.RangeMonitor behind the probe points).  The chosen exponents land in ``loss_scaler.log2`` and
+        ``weight_sources['loss_scale_log2']``; the walk, its gradients, the optimiser state, the scaler's dynamic factor and counters and the RNG
+        streams are left as they were.  Before the first capture only.  Returns nets16.calibrate's record."""
+        from . import capture, hostutil, nets16
+        if self.loss_scaler is None:
+            raise RuntimeError('calibrate_scales: only the fp16 path (--precision f16) has gradient scales')
+        if getattr(self, '_captured_step', None) is not None:
+            raise RuntimeError('calibrate_scales after the step was captured: the recorded graph has the static scales baked in')
+        params = list(self.walk.parameters())
+        grads = [None if p.grad is None else p.grad.detach().clone() for p in params]
+        terms = self.last_terms
+        sl = dist.shard(self.BATCH_SIZE)
+
+        def probe(k):
+            zs = hostutil.z_sample(self.BATCH_SIZE, seed=nets16.CALIBRATE_SEED + k, dim_z=self.dim_z)[sl]
+            alpha, _, _ = self.get_train_alpha(zs, N_attr=len(self.attrList), trainEmbed=False)
+            capture.forward_backward(self, torch.Tensor(zs).to(self.device), torch.tensor(alpha).float().to(self.device), no_content_loss=no_content_loss,
+                                     no_gan_loss=no_gan_loss, clamp=clamp, layers=layers)
+        try:
+            rec = nets16.calibrate(self.loss_scaler, probe, int(n_steps), self.device)
+        finally:
+            torch.cuda.synchronize()
+            for p, g in zip(params, grads):
+                p.grad = g
+            self.last_terms = terms
+        self.weight_sources['loss_scale_log2'] = dict(self.loss_scaler.log2)
+        self.f16_calibration = rec
+        return rec
+
     # -- checkpoints ---------------------------------------------------------------------------------------------
     def save_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
         print('Save W and GAN in %s and %s' % (save_path_w, save_path_gan))

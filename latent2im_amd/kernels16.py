@@ -210,6 +210,22 @@ def mask_mul(g, ref, pos=1.0, neg=0.0):
     return y
 
 
+RANGE_WORDS, RANGE_ZEROS, RANGE_MAX, RANGE_CALLS, RANGE_N = 260, 256, 257, 258, 259      # L2I_RANGE_* of include/l2i.h
+RANGE_KINDS = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
+
+
+def range_stats(t, row):
+    """l2i_range_stats: ADD the octave histogram, zero count, largest finite magnitude, call and element counts of every stored element of ``t``
+    (contiguous fp16 / bf16 / fp32) to ``row``, RANGE_WORDS contiguous int64 words on the device, on the current stream.  No host read."""
+    kind = RANGE_KINDS.get(t.dtype)
+    if kind is None:
+        raise _lib.L2IError('range_stats reads float16, bfloat16 or float32 tensors, got %s' % t.dtype)
+    if row.dtype != torch.int64 or row.numel() != RANGE_WORDS:
+        raise _lib.L2IError('range_stats adds to %d int64 words, got %s x %d' % (RANGE_WORDS, row.dtype, row.numel()))
+    _lib.call('l2i_range_stats', _lib.ptr(row), _lib.ptr(t), t.numel(), kind)
+    return row
+
+
 def modulate_planes(w32, s, dtype=None):
     """w32: fp32 weights in plane order [Cin/16, KK, 2, CoutP, 8] (conv.pack_weight_h8_f32); s [B, Cin] fp32 -> 16-bit planes [B, Cin/16, KK, 2, CoutP, 8]
     (int16 view) in the element type of the path (or ``dtype``)."""

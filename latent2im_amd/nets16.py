@@ -57,11 +57,252 @@ PAIR = True         # [r6] ResNet-50's trunk: chained 1x1 convs as one launch (c
 PROBE = None            # tools/bf16_study.py --probe: a list that receives (tag, shape, max |g|, median |g| of the non-zero entries) per gradient map
 
 
+# [r7] A RangeMonitor (below) fed from the same points: the device-side, sync-free form of the probe (csrc/l2i_range.hip) — usable inside training and
+# inside a captured graph; --f16_calibrate and --f16_watch of the drivers set it.  Both None: `_probe` does nothing and no call is added to a step.
+MONITOR = None
+F16_SCALES_FLAG = None  # --f16_scales of the drivers: dict of explicit exponents (any subset of R, V, D, G) laid over the table and over L2I_F16_SCALES
+
+
+def _probing():
+    """Is anything listening at the probe points?  (The call sites that build an argument for `_probe` ask first.)"""
+    return PROBE is not None or MONITOR is not None
+
+
 def _probe(tag, t):
     if PROBE is not None:
         a = t.detach().float().abs().reshape(-1)
         nz = a[a > 0]
         PROBE.append((tag, tuple(t.shape), float(a.max()), float(nz.median()) if nz.numel() else 0.0, float((a == 0).float().mean())))
+    if MONITOR is not None:
+        MONITOR.add(tag, t)
+
+
+# ---- the range monitor: one row of l2i_range_stats per probe tag ---------------------------------------------------------------------------------
+F16_MIN_NORMAL_FIELD = 113      # fp32 exponent field of fp16's smallest normal, 2^-14
+WATCH_MIN_MEDIAN_OCTAVE = -14   # --f16_watch warns when a gradient map's median octave is below it: "normal numbers throughout" (F16_SCALE_BASE's note)
+WATCH_MAX_LOG2 = 11             # ... and when a branch's largest stored value reaches 2^11: the low end of the first choice of exponents, which went non-finite
+
+
+def reduce_row(row, kind):
+    """The host-side reductions of one l2i_range_stats row (260 integers; ``kind``: kernels16.RANGE_KINDS value of the element type):
+    n, zeros, nonfinite, calls; max (exact float) and max_log2 (None for a map without a finite non-zero entry); median_octave = the exponent of the
+    bin in which the cumulative count of finite non-zero entries crosses one half (None without any; the lower median of an even count, as
+    torch.median); below_normal = the share of them under the element type's smallest normal (fp16: fields 1..112; bf16 / fp32: field 0 less the zeros)."""
+    r = [int(v) for v in row]
+    zeros, bits = r[K16.RANGE_ZEROS], r[K16.RANGE_MAX]
+    mx = float(np.array([bits], dtype=np.uint32).view(np.float32)[0])
+    cnt = [r[0] - zeros] + r[1:255]                        # finite non-zero entries per exponent field 0 .. 254
+    total = sum(cnt)
+    median = None
+    if total:
+        cum = 0
+        for e, c in enumerate(cnt):
+            cum += c
+            if 2 * cum >= total:
+                median = max(e, 1) - 127                   # (field 0: fp32 subnormals, exponent -126)
+                break
+    below = sum(cnt[:F16_MIN_NORMAL_FIELD]) if kind == K16.RANGE_KINDS[torch.float16] else cnt[0]
+    return dict(n=r[K16.RANGE_N], zeros=zeros, nonfinite=r[255], calls=r[K16.RANGE_CALLS], max=mx, max_log2=math.log2(mx) if mx > 0 else None,
+                median_octave=median, below_normal=below / total if total else 0.0)
+
+
+class RangeMonitor:
+    """One [capacity, 260] int64 table on the device, a row per probe tag (handed out on first sight), filled by kernels16.range_stats on whatever
+    stream the probe point runs on (integer atomics: the loss branches' streams may share the table).  ``read()`` is the only host read.  The table is
+    allocated here, outside any graph's pool, like optim._init_state's optimiser state: a monitor set before a capture is recorded into the
+    hipGraph and every replay keeps adding to it."""
+
+    def __init__(self, device, capacity=128):
+        self.table = torch.zeros(capacity, K16.RANGE_WORDS, dtype=torch.int64, device=device)
+        self.capacity = capacity
+        self.rows = {}                                     # tag -> (row index, element kind)
+
+    def add(self, tag, t):
+        ent = self.rows.get(tag)
+        if ent is None:
+            if len(self.rows) >= self.capacity:
+                raise RuntimeError('RangeMonitor is full: %d tags, no row for %r' % (self.capacity, tag))
+            if t.dtype not in K16.RANGE_KINDS:
+                raise RuntimeError('RangeMonitor reads float16, bfloat16 or float32 maps, %r is %s' % (tag, t.dtype))
+            ent = self.rows[tag] = (len(self.rows), K16.RANGE_KINDS[t.dtype])
+        K16.range_stats(t.detach(), self.table[ent[0]])
+
+    def clear(self):
+        self.table.zero_()
+
+    def read(self):
+        """{tag: reduce_row(...)} — a host read (synchronises)."""
+        host = self.table[:max(len(self.rows), 1)].cpu().numpy()
+        return {tag: reduce_row(host[i], kind) for tag, (i, kind) in self.rows.items()}
+
+
+# ---- calibration of the static exponents ------------------------------------------------------------------------------------------------------------
+CALIBRATE_ROUNDS = 4
+CALIBRATE_STEP = 8              # octaves a saturated (non-finite) or vanished (all-zero) branch moves before it is measured again
+CALIBRATE_SEED = 7700           # z of probe step k: synth-style RandomState(CALIBRATE_SEED + k); alpha: the graph's own get_train_alpha
+
+
+def branch_of(tag):
+    """The loss branch whose exponent a GRADIENT tag speaks for, None for every other tag (forward maps never enter the choice)."""
+    if '.fwd.' in tag:
+        return None
+    if tag.startswith('R.G'):
+        return 'R'
+    if tag == 'V.d4' or tag.startswith('V.g'):
+        return 'V'
+    if tag.startswith('D.g'):
+        return 'D'
+    if tag.startswith('G.dx') or tag.startswith('PG.g_'):
+        return 'G'
+    return None
+
+
+def scale_exponent(true_max):
+    """THE exponent rule the tables were made by: the branch's largest gradient value, as it would be stored under a scale of 1, goes near 2^5."""
+    return 5 - int(round(math.log2(true_max)))
+
+
+def branch_summary(rows, dyn=1.0):
+    """{branch: dict(max = largest stored value over its gradient tags, tag = where, nonfinite = count, dyn = the dynamic factor they were stored under)}
+    from a RangeMonitor.read(); a branch without tags (its loss term is off) is absent."""
+    out = {}
+    for tag, r in rows.items():
+        k = branch_of(tag)
+        if k is None:
+            continue
+        b = out.setdefault(k, dict(max=0.0, tag=None, nonfinite=0, dyn=float(dyn)))
+        b['nonfinite'] += r['nonfinite']
+        if r['max'] > b['max'] or b['tag'] is None:
+            b['max'], b['tag'] = max(r['max'], b['max']), tag
+    return out
+
+
+def calibrate_scales(start, measure, rounds=CALIBRATE_ROUNDS, reduce=None):
+    """The calibration loop as a pure function.  ``start``: {branch: log2}; ``measure(log2)`` runs the probe steps under these exponents and returns a
+    branch_summary; ``reduce`` (optional) makes the ranks agree on it before each decision.  Per branch and round: a non-finite entry -> exponent - 8,
+    every gradient tag all zero -> + 8, otherwise the rule (scale_exponent of stored max / (2^log2 * dyn)); a branch is settled when the rule moves it
+    by at most one octave — a branch is linear in its incoming gradient, so the round after a clean measurement confirms it.  A branch that
+    `measure` does not report (its loss term is off) keeps its start.  Returns (chosen, history = [(log2 of the round, what was seen)]); raises
+    with the history when a branch has not settled after ``rounds`` rounds."""
+    log2 = {k: int(v) for k, v in start.items()}
+    history, open_ = [], set(log2)
+    for _ in range(rounds):
+        seen = measure(dict(log2))
+        if reduce is not None:
+            seen = reduce(seen)
+        history.append((dict(log2), seen))
+        open_ = set()
+        for k in log2:
+            s = seen.get(k)
+            if s is None:
+                continue
+            if s['nonfinite']:
+                log2[k] -= CALIBRATE_STEP
+                open_.add(k)
+            elif not s['max'] > 0:
+                log2[k] += CALIBRATE_STEP
+                open_.add(k)
+            else:
+                new = scale_exponent(s['max'] / (2.0 ** log2[k] * s.get('dyn', 1.0)))
+                if abs(new - log2[k]) > 1:
+                    open_.add(k)
+                log2[k] = new
+        if not open_:
+            return log2, history
+    raise RuntimeError('fp16 scale calibration: branch(es) %s not settled after %d rounds; seen: %s'
+                       % (', '.join(sorted(open_)), rounds, '; '.join('%s -> %s' % (l, {k: (v['max'], v['nonfinite']) for k, v in s.items()}) for l, s in history)))
+
+
+def _reduce_over_ranks(device):
+    from . import dist
+
+    def reduce(seen):
+        if dist.world_size() == 1:
+            return seen
+        out = {}
+        for k in sorted(seen):                             # every rank runs the same loss flags: the same branches, in the same order
+            s = seen[k]
+            out[k] = dict(s, max=float(dist.max_over_ranks(float(s['max']), device)), nonfinite=int(dist.max_over_ranks(float(s['nonfinite']), device)))
+        return out
+    return reduce
+
+
+def calibrate(scaler, probe_step, n_steps, device, rounds=CALIBRATE_ROUNDS):
+    """Calibrate ``scaler.log2`` in place on the fp16 graph itself: rounds of ``n_steps`` calls of ``probe_step(k)`` (forward, loss and backward as
+    training runs them, no optimiser step; k counts up over all rounds) with a RangeMonitor behind the probe points, decided by calibrate_scales.
+    Leaves numpy's global RNG, torch's device RNG and MONITOR as they were (the caller restores what its probe step touches: the walk's .grad).
+    Must run before the first capture: a recorded graph has the static scales baked in.  Under world > 1 every decision is taken on MAX-reduced
+    figures (single-rank is what the tests cover).  Returns dict(start, chosen, rounds, tags = the read() rows of the final round)."""
+    global MONITOR
+    keep, np_state, dev_state = MONITOR, np.random.get_state(), torch.cuda.get_rng_state(device)
+    start, mon, last, k = dict(scaler.log2), RangeMonitor(device), {}, [0]
+
+    def measure(log2):
+        scaler.log2.update(log2)
+        mon.clear()
+        for _ in range(n_steps):
+            probe_step(k[0])
+            k[0] += 1
+        last['rows'] = mon.read()
+        return branch_summary(last['rows'], float(scaler.scale[0]))
+    try:
+        MONITOR = mon
+        chosen, history = calibrate_scales(start, measure, rounds, reduce=_reduce_over_ranks(device))
+    except Exception:
+        scaler.log2.update(start)
+        raise
+    finally:
+        MONITOR = keep
+        np.random.set_state(np_state)
+        torch.cuda.set_rng_state(dev_state, device)
+    scaler.log2.update(chosen)
+    return dict(start=start, chosen=dict(chosen), rounds=len(history), tags=last['rows'])
+
+
+def parse_f16_scales(text, keys='RVDG'):
+    """'R=11,V=22' -> {'R': 11, 'V': 22}: --f16_scales (any subset of ``keys``, integer log2 values); ValueError names what is wrong."""
+    out = {}
+    for item in str(text).split(','):
+        k, sep, v = item.strip().partition('=')
+        if not sep or k not in keys or k in out:
+            raise ValueError('--f16_scales takes KEY=LOG2 pairs with distinct keys out of %s, got %r' % (', '.join(keys), item))
+        try:
+            out[k] = int(v)
+        except ValueError:
+            raise ValueError('--f16_scales: the exponent of %s is an integer power of two, got %r' % (k, v))
+    return out
+
+
+def watch_report(rows):
+    """The lines --f16_watch logs from one RangeMonitor.read(): [(level, text)], one per branch with gradient tags and one for the forward maps.
+    A branch line: largest stored value as 2^x with its tag, lowest median octave with its tag, worst below-normal share with its tag, non-finite
+    count.  'warning' when a non-finite entry was stored, a gradient map's median octave is under WATCH_MIN_MEDIAN_OCTAVE, or the branch's
+    largest stored value reaches 2^WATCH_MAX_LOG2."""
+    groups = {}
+    for tag in sorted(rows):
+        groups.setdefault(branch_of(tag) or ('fwd' if '.fwd.' in tag else tag.split('.')[0]), []).append(tag)
+    lines = []
+    for key in sorted(groups, key=lambda k: (k == 'fwd', k)):
+        tags = groups[key]
+        live = [t for t in tags if rows[t]['max_log2'] is not None]
+        nonfinite = sum(rows[t]['nonfinite'] for t in tags)
+        if not live:
+            lines.append(('warning' if nonfinite else 'info', 'range %s: no finite non-zero entry in %d maps, non-finite %d' % (key, len(tags), nonfinite)))
+            continue
+        top = max(live, key=lambda t: rows[t]['max_log2'])
+        low = min(live, key=lambda t: rows[t]['median_octave'])
+        sub = max(live, key=lambda t: rows[t]['below_normal'])
+        why = []
+        if nonfinite:
+            why.append('non-finite entries stored')
+        if key != 'fwd' and rows[low]['median_octave'] < WATCH_MIN_MEDIAN_OCTAVE:
+            why.append('median of %s under 2^%d: gradients are stored as subnormals or flushed' % (low, WATCH_MIN_MEDIAN_OCTAVE))
+        if key != 'fwd' and rows[top]['max_log2'] >= WATCH_MAX_LOG2:
+            why.append('largest value at 2^%d or above: little headroom under 2^16' % WATCH_MAX_LOG2)
+        text = ('range %s: max 2^%.1f (%s), lowest median octave 2^%d (%s), below-normal share %.3g (%s), non-finite %d'
+                % (key, rows[top]['max_log2'], top, rows[low]['median_octave'], low, rows[sub]['below_normal'], sub, nonfinite))
+        lines.append(('warning', text + ' -- ' + '; '.join(why)) if why else ('info', text))
+    return lines
 
 
 def loss_scale_for(resolution, batch):
@@ -69,15 +310,21 @@ def loss_scale_for(resolution, batch):
     shard, dist.shard: its gradients scale with 1 / B_local, not with the global batch).  The magnitudes follow the loss normalisations: the
     ContentLoss is a mean over B * C * H * W elements (gradient ~ 1 / (B H W)), the regressor's BCE a mean over B * attrs through an average pool
     (1 / B), the discriminator's BCE a mean over B through learned-scale convs, and the generator receives their sum.  An override for experiments
-    and for the overflow-guard tests: L2I_F16_SCALES="R,V,D,G" (log2 values)."""
+    and for the overflow-guard tests: L2I_F16_SCALES="R,V,D,G" (log2 values); the drivers' --f16_scales (F16_SCALES_FLAG) beats both."""
     env = os.environ.get('L2I_F16_SCALES')
     if env:
         r, v, d, g = (int(x) for x in env.split(','))
-        return dict(R=r, V=v, D=d, G=g)
+        return _flagged(dict(R=r, V=v, D=d, G=g))
     lb = int(round(math.log2(max(batch, 1))))
     lr = int(round(math.log2(resolution)))
-    return dict(R=F16_SCALE_BASE['R'] + lb + F16_SCALE_RES['R'] * (lr - 8), V=F16_SCALE_BASE['V'] + lb + F16_SCALE_RES['V'] * (lr - 8),
-                D=F16_SCALE_BASE['D'] + lb + F16_SCALE_RES['D'] * (lr - 8), G=F16_SCALE_BASE['G'] + lb + F16_SCALE_RES['G'] * (lr - 8))
+    return _flagged(dict(R=F16_SCALE_BASE['R'] + lb + F16_SCALE_RES['R'] * (lr - 8), V=F16_SCALE_BASE['V'] + lb + F16_SCALE_RES['V'] * (lr - 8),
+                         D=F16_SCALE_BASE['D'] + lb + F16_SCALE_RES['D'] * (lr - 8), G=F16_SCALE_BASE['G'] + lb + F16_SCALE_RES['G'] * (lr - 8)))
+
+
+def _flagged(log2):
+    if F16_SCALES_FLAG:
+        log2.update({k: int(v) for k, v in F16_SCALES_FLAG.items() if k in log2})
+    return log2
 
 
 # exponents at 256^2, batch 1, and their growth per doubling of the resolution (tools/bf16_study.py --probe, profiles/r05_fp16_gradient_ranges.txt)
@@ -182,7 +429,7 @@ class VGG19Prefix:
         p, idx = K16.maxpool2d_fwd(c2, 2, 2, 0, relu=True)          # relu(maxpool(.)) == maxpool(relu(.)); the stored map is already rectified
         c3 = self.convs[2].forward(p, bias=self.biases[2], sq=sq[2])
         c4 = self.convs[3].forward(c3, relu_in=True, bias=self.biases[3], sq=sq[3])
-        if PROBE is not None:
+        if _probing():
             for tag, t in (('V.fwd.c1', c1), ('V.fwd.c2', c2), ('V.fwd.c3', c3), ('V.fwd.c4', c4)):
                 _probe(tag, t)
         if org is None:
@@ -217,7 +464,7 @@ class _Content16Fn(torch.autograd.Function):
         gl = [gs[k:k + 1].contiguous() for k in range(4)]
         hw = lambda t: (t.shape[2], t.shape[3])
         d4 = K16.sqdiff(o4, c4, coef=2.0 / c4.numel(), coef_dev=gl[3], want_grad=True, want_sum=False)[1]
-        d4_probe = d4 if PROBE is not None else None
+        d4_probe = d4 if _probing() else None
         g3 = net.convs[3].dgrad(d4, hw(c3), out_mask=c3, residual=c3, res_sub=o3, res_coef=2.0 / c3.numel(), res_coef_dev=gl[2])
         del d4
         _probe('V.g3', g3)
@@ -228,7 +475,7 @@ class _Content16Fn(torch.autograd.Function):
         _probe('V.g2', g2)
         g1 = net.convs[1].dgrad(g2, hw(c1), out_mask=c1, residual=c1, res_sub=o1, res_coef=2.0 / c1.numel(), res_coef_dev=gl[0])
         del g2
-        for tag, t in (('V.d4', d4_probe), ('V.g1', g1)) if PROBE is not None else ():
+        for tag, t in (('V.d4', d4_probe), ('V.g1', g1)) if _probing() else ():
             _probe(tag, t)
         g_img = net.convs[0].dgrad(g1, ctx.in_hw, out_f32=True, out_gain=1.0 / S)
         ctx.acts = ctx.org = None
@@ -337,7 +584,7 @@ class _ResNet16Fn(torch.autograd.Function):
             elif keep:
                 saved['blocks'].append((cur, y1, y2, out))
             cur = out
-            if PROBE is not None and blk['down'] is not None:
+            if _probing() and blk['down'] is not None:
                 _probe('R.fwd.out', out)
         b, g8, h, w, _ = cur.shape
         feat = K16.dot_reduce(cur) * (1.0 / (h * w))                                   # adaptive avg-pool (1,1), fp32 sums
@@ -409,7 +656,7 @@ class _ResNet16Fn(torch.autograd.Function):
                 K16.add_zero_insert(Gp, blk['down'].conv.dgrad_compact(G), mask=cur if bi > 0 else None)       # strided 1x1: compact 1x1 conv + zero insertion
             del g_y1
             G = Gp
-            if PROBE is not None and (bi in (0, n - 1) or net.blocks[bi]['down'] is not None):
+            if _probing() and (bi in (0, n - 1) or net.blocks[bi]['down'] is not None):
                 _probe('R.G%d' % bi, G)
         a0 = saved['a0']                                   # [r5] h8 stem map: the 7x7 gradient kernel reads the 16-bit pool gradient and mask
         g_a0 = K16.maxpool2d_bwd(G, saved['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
@@ -604,7 +851,7 @@ class _Synthesis16Fn(torch.autograd.Function):
                 y = L.conv.forward(x, planes=planes, w_bstride=bstride, out_scale=demod, noise=nz, noise_w=L.noise_w, bias=L.bias,
                                    rgb=None if rgb is None else (plan.wmod(w_all, B, li // 2), gen.rgbs[li // 2].bias, rgb), **lr)
             del planes
-            if PROBE is not None and li % 2 == 0:
+            if _probing() and li % 2 == 0:
                 _probe('G.fwd.y%d@%d' % (li, res), y)
             rec = dict(x=x if keep else None, y=y if keep else None, s=s, nz=nz)
             if li == 0 or (li % 2 == 0):
@@ -663,7 +910,7 @@ class _Synthesis16Fn(torch.autograd.Function):
             del planes
             if li == 0:
                 K16.dot_reduce(dxmod, x, out=plan.s(q_all, B, li).view(-1))      # d s via x * s (layers >= 1: inside the next sg2_act_bwd)
-            if PROBE is not None and (li % 2 == 0 or li == len(gen.layers) - 1):
+            if _probing() and (li % 2 == 0 or li == len(gen.layers) - 1):
                 _probe('G.dx%d@%d' % (li, hw[0]), dxmod)
             gin, gin_scale = dxmod, s
             rec['y'] = rec['x'] = None
@@ -692,7 +939,7 @@ def pggan_scale_for(resolution, batch):
     lb = int(round(math.log2(max(batch, 1))))
     lr = int(round(math.log2(resolution)))
     out['G'] = F16_PG_SCALE_BASE + lb + F16_PG_SCALE_RES * (lr - 8)
-    return out
+    return _flagged(out)
 
 
 class _PGConv16:
@@ -779,7 +1026,7 @@ class _PG16Fn(torch.autograd.Function):
             else:
                 out = K16.pixelnorm_act(a2, 0.2, up=2)
             saved.append((a1, a2) if keep else None)
-            if PROBE is not None:
+            if _probing():
                 _probe('PG.fwd.a2@%d' % a2.shape[2], a2)
         rgb = lambda i, t: gen.rgb[i][0].forward(t, bias=gen.rgb[i][1], out_f32=True)
         if not blend:

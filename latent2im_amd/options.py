@@ -56,6 +56,15 @@ class TrainOptions:
         p.add_argument('--synthetic_weights', action='store_true',
                        help='run on seeded random-init G / regressor / VGG when the checkpoint paths of constants.py do not exist '
                             '(default: a missing checkpoint is an error, as in the reference)')
+        p.add_argument('--f16_scales', type=str, default=None,
+                       help='explicit static gradient-scale exponents of the fp16 path, e.g. R=11,V=22,D=16,G=12 (log2; any subset of the keys, the rest '
+                            'from the table of nets16.py; beats the environment variable L2I_F16_SCALES); --precision f16 only')
+        p.add_argument('--f16_calibrate', type=int, default=0,
+                       help='measure those exponents on the loaded weights before training: N probe steps (forward, loss, backward) a round; the result goes to '
+                            'opt.yml (weight_sources.loss_scale_log2) and f16_scales.json; 0 = off; --precision f16 only')
+        p.add_argument('--f16_watch', type=int, default=0,
+                       help='keep the device-side range monitor on while training and log one line per loss branch every N iterations (a host read every N '
+                            'iterations), with a WARNING for non-finite entries, subnormal gradient maps or vanishing headroom; 0 = off; --precision f16 or bf16')
         g = p.add_argument_group('nn', 'parameters used to specify NN walk')
         g.add_argument('--eps', type=float, help='step size of each NN block')
         g.add_argument('--num_steps', type=int, help='number of NN blocks')
@@ -105,6 +114,7 @@ class TrainOptions:
                 args[grp.title] = argparse.Namespace(**d)
         opt = argparse.Namespace(**args)
         delattr(opt, 'config_file')
+        self._check_f16_flags(opt)
         if opt.name:
             output_dir = opt.name
         else:
@@ -125,6 +135,28 @@ class TrainOptions:
             self.print_options(opt)
         self.opt = opt
         return opt
+
+    def _check_f16_flags(self, opt):
+        """The fp16 scale flags against --precision (after the YAML merge): the static exponents exist on the f16 path only; the monitor also reads bf16 maps."""
+        if opt.f16_scales is not None:
+            if opt.precision != 'f16':
+                self.parser.error('--f16_scales sets the static gradient scales of the fp16 path: it needs --precision f16 (got %s)' % (opt.precision or 'f32'))
+            from .nets16 import parse_f16_scales
+            try:
+                opt.f16_scales = parse_f16_scales(opt.f16_scales) if isinstance(opt.f16_scales, str) else {str(k): int(v) for k, v in dict(opt.f16_scales).items()}
+            except ValueError as e:
+                self.parser.error(str(e))
+        if (opt.f16_calibrate or 0) < 0 or (opt.f16_watch or 0) < 0:
+            self.parser.error('--f16_calibrate / --f16_watch take a number of steps >= 0')
+        if opt.f16_calibrate and opt.precision != 'f16':
+            self.parser.error('--f16_calibrate measures the static gradient scales of the fp16 path: it needs --precision f16 (got %s); bf16 and fp32 '
+                              'gradients are not scaled' % (opt.precision or 'f32'))
+        if opt.f16_watch and opt.precision not in ('f16', 'bf16'):
+            self.parser.error('--f16_watch reads the stored 16-bit maps: it needs --precision f16 or bf16 (got %s)' % (opt.precision or 'f32'))
+        # a run without these flags keeps the namespace, opt.txt and opt.yml it had before they existed: an unset one is not carried (readers use getattr)
+        for name in ('f16_scales', 'f16_calibrate', 'f16_watch'):
+            if not getattr(opt, name):
+                delattr(opt, name)
 
     def print_options(self, opt):
         lines, dump, groups = ['----------------- Options ---------------'], OrderedDict(), []

@@ -402,6 +402,35 @@ class TransformGraph:
 
     optimize_parameters = optimizeParametersAll
 
+    def calibrate_scales(self, n_steps, clamp=True, layers=None, no_content_loss=False, no_gan_loss=True):
+        """graph.TransformGraph.calibrate_scales on this graph: the probe step is walk_forward_backward (the GAN term cannot be evaluated here, so
+        the D exponent, which has no tags, keeps its start; ``clamp`` / ``layers`` are the StyleGAN2 graph's and are ignored)."""
+        from . import hostutil, nets16
+        if self.loss_scaler is None:
+            raise RuntimeError('calibrate_scales: only the fp16 path (--precision f16) has gradient scales')
+        if getattr(self, '_captured_step', None) is not None:
+            raise RuntimeError('calibrate_scales after the step was captured: the recorded graph has the static scales baked in')
+        params = list(self.walk.parameters())
+        grads = [None if p.grad is None else p.grad.detach().clone() for p in params]
+        terms = self.last_terms
+        sl = dist.shard(self.BATCH_SIZE)
+
+        def probe(k):
+            zs = hostutil.z_sample(self.BATCH_SIZE, seed=nets16.CALIBRATE_SEED + k, dim_z=self.dim_z)[sl]
+            alpha, _, _ = self.get_train_alpha(zs, N_attr=len(self.attrList), trainEmbed=False)
+            walk_forward_backward(self, torch.Tensor(zs).to(self.device), torch.tensor(np.asarray(alpha)).float().to(self.device),
+                                  no_content_loss=no_content_loss, no_gan_loss=True)
+        try:
+            rec = nets16.calibrate(self.loss_scaler, probe, int(n_steps), self.device)
+        finally:
+            torch.cuda.synchronize()
+            for p, g in zip(params, grads):
+                p.grad = g
+            self.last_terms = terms
+        self.weight_sources['loss_scale_log2'] = dict(self.loss_scaler.log2)
+        self.f16_calibration = rec
+        return rec
+
     def captured_z_step(self, batch, n_attr, no_content_loss=False):
         """The step as a hipGraph for ``batch`` samples a replay (capture.CapturedZStep): what trainer.train_step asks a graph without get_w for
         under --hip_graph."""

@@ -114,11 +114,27 @@ def train(graphs, graph_inputs, output_dir, attrList, layers=None, save_freq=100
     garbage collector's permanent generation (``gc.freeze``: a full collection over the networks' ~270 000 host objects takes 73 ms on the thread
     that launches the step's kernels); ``gc.unfreeze()`` runs in a ``finally`` when training ends, so a caller that drops
     this graph and builds another (notebooks, eval, tests) keeps a working cycle collector.  ``opt.no_gc_freeze`` switches the freeze off."""
+    from . import nets16
+    watch, keep = int(getattr(opt, 'f16_watch', 0) or 0) if opt is not None else 0, nets16.MONITOR
     try:
+        if watch:
+            # --f16_watch: a range monitor behind the probe points of the 16-bit networks for the whole run (set before the step is captured, so
+            # that under --hip_graph its launches are part of the recorded step); read, logged and cleared every `watch` iterations in _train
+            nets16.MONITOR = nets16.RangeMonitor(graphs.device)
         return _train(graphs, graph_inputs, output_dir, attrList, layers, save_freq, trainEmbed, updateGAN, opt, multi_attr)
     finally:
+        nets16.MONITOR = keep
         import gc
         gc.unfreeze()
+
+
+def _log_ranges(monitor, is_main):
+    """One --f16_watch report: read the monitor (the host synchronisation of the flag), log nets16.watch_report's lines, clear it."""
+    from . import nets16
+    if is_main:
+        for level, text in nets16.watch_report(monitor.read()):
+            (logging.warning if level == 'warning' else logging.info)(text)
+    monitor.clear()
 
 
 def _train(graphs, graph_inputs, output_dir, attrList, layers, save_freq, trainEmbed, updateGAN, opt, multi_attr):
@@ -135,6 +151,8 @@ def _train(graphs, graph_inputs, output_dir, attrList, layers, save_freq, trainE
     sl = dist.shard(batch_size)
     sync_log = not (opt is not None and getattr(opt, 'no_log_sync', False))
     loss_values = []
+    from . import nets16
+    watch, done = (int(getattr(opt, 'f16_watch', 0) or 0) if opt is not None and nets16.MONITOR is not None else 0), 0
     for epoch in range(n_epoch):
         if updateGAN:
             raise NotImplementedError('ERROR: jointly training is not implemented yet')      # train.py:40-41
@@ -158,6 +176,9 @@ def _train(graphs, graph_inputs, output_dir, attrList, layers, save_freq, trainE
                 if is_main:
                     logging.info('T, epc, bst, lss, alpha: {}, {}, {}, {}, {}'.format(
                         time.time() - start_time, epoch, batch_start, loss, round(float(at[0]), 2)))
+            done += 1
+            if watch and done % watch == 0:
+                _log_ranges(nets16.MONITOR, is_main)
             if is_main and (i % save_freq == 0):
                 make_samples(out_zs, output_dir, epoch, i * batch_size, batch_size, name='org_%.2f' % (round(float(at[0]), 2)))
                 make_samples(transformed, output_dir, epoch, i * batch_size, batch_size, name='logit_%.2f' % (round(float(at[0]), 2)))
@@ -192,9 +213,23 @@ def main(multi_attr=False, argv=None):
         np.random.seed(1234)                         # identical walk init and alpha stream on every rank
     graph_kwargs = hostutil.set_graph_kwargs(opt)
     model = graph_mod.find_model_using_name(opt.model, opt.transform)
-    g = model(**graph_kwargs)
+    from . import nets16
+    nets16.F16_SCALES_FLAG = getattr(opt, 'f16_scales', None)      # --f16_scales: read where the graph builds its LossScaler (nets16.loss_scale_for)
+    try:
+        g = model(**graph_kwargs)
+    finally:
+        nets16.F16_SCALES_FLAG = None
     if world > 1:                                    # one source of truth for the trainable state
         dist.broadcast_parameters(g.walk.parameters())
+    if getattr(opt, 'f16_calibrate', 0):             # before the first step and the first capture: a recorded graph has the static scales baked in
+        rec = g.calibrate_scales(opt.f16_calibrate, clamp=multi_attr, layers=graph_kwargs['layers'], no_content_loss=bool(opt.no_content_loss),
+                                 no_gan_loss=bool(opt.no_gan_loss))
+        if rk == 0:
+            import json
+            print('fp16 gradient scales: table / flags %s -> calibrated %s (%d rounds of %d probe steps)' % (rec['start'], rec['chosen'], rec['rounds'], opt.f16_calibrate))
+            with open(os.path.join(opt.output_dir, 'f16_scales.json'), 'wt') as f:
+                json.dump(dict(start=rec['start'], chosen=rec['chosen'], rounds=rec['rounds'], probe_steps=opt.f16_calibrate, tags=rec['tags']), f, indent=1, sort_keys=True)
+                f.write('\n')
     if rk == 0:                                      # which frozen weights this run trained against: stdout, opt.yml (and log.txt in train())
         print('weight sources: ', g.weight_sources)
         yml = os.path.join(opt.output_dir, 'opt.yml')
