@@ -10,16 +10,15 @@ Python one launch at a time (~300 conv launches + ~500 small kernels per step). 
          stream) -> backward into ``walk.grad``
 
 ``CapturedZStep`` is the same for BASELINE config 1, the PGGAN graph's walk in z (pggan.walk_forward_backward): one stream, no noise.
+``record`` is the one place that records a step; the inversion's iteration (invert._Replay) goes through it too.
 
-The all-reduce of the walk gradient (RCCL) and the Adam update stay OUTSIDE the graph, in the order optimizeParametersAll runs
-them: a handful of tiny launches, and the captured region holds no collective, so the same graph serves 1 and N ranks.
+The all-reduce of the walk gradient (RCCL) and the Adam update (WalkGraph.walk_update) stay OUTSIDE the graph, in the order optimizeParametersAll
+runs them: a handful of tiny launches, and the captured region holds no collective, so the same graph serves 1 and N ranks.
 Per-layer generator noise (networks.py:281-286) is drawn inside the graph from torch's graph-safe Philox stream (fresh values every
 replay).  Reference: train.py:56-110 is the region; the reference itself is eager PyTorch.
 """
 import numpy as np
 import torch
-
-from . import dist
 
 
 def freeze_host_objects():
@@ -91,95 +90,84 @@ class _StagedInputs:
         self._ring_used[i] = True
 
 
-class CapturedStep(_StagedInputs):
-    """``step(zs, alpha)`` == selfcheck.run_step(g, zs, alpha, ...) with the forward+backward replayed from one hipGraph."""
+def record(device, step, warmup=2, before_capture=None):
+    """Record one call of ``step()`` into a hipGraph (HIP stream capture through ``torch.cuda.graph``).  The protocol, once, for every recorded
+    step of the package: ``max(warmup, 1)`` calls on a side stream (allocator pools, split-K workspaces, lazily packed weights: what capture
+    cannot do), that stream joined both ways and the device synchronised, ``before_capture()`` (the callers' ``zero_grad(set_to_none=True)``:
+    the gradients then become static tensors of the graph's pool), one call inside the capture.  Returns (graph, what the captured call returned,
+    keep-alive list): the graph's kernel nodes hold RAW pointers into the split-K workspaces of conv._WS, allocated during warm-up outside the
+    graph's pool, so the caller keeps that list for as long as the graph, even if a later eager launch replaces a dict entry with a larger one.
 
-    def __init__(self, g, batch, n_attr, no_content_loss=False, no_gan_loss=False, clamp=False, layers=None, warmup=2):
+    Two rules for ``step``.  The warm-up runs loss and backward only, never an update: the walk (or W+), the optimiser state and the fp16 scaler
+    are what an eager run starts from (a step that records its update makes it only under ``torch.cuda.is_current_stream_capturing()``).  And
+    a recording meant to be ONE stream holds nothing attached to the autograd graph across the warm-up, so such a step returns detached tensors:
+    a survivor keeps the leaves' gradient accumulators on the warm-up's stream, and the capture would fork to that stream to run them."""
+    from . import conv
+    s = torch.cuda.Stream(device=device)
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(max(warmup, 1)):
+            step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    if before_capture is not None:
+        before_capture()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = step()
+    return graph, out, list(conv._WS.values())
+
+
+class _CapturedWalkStep(_StagedInputs):
+    """A walk graph's forward + backward (``self._step()``, on the static inputs) recorded once; every call loads the inputs, replays, points the
+    walk's ``.grad`` at the graph's static gradient tensors and runs the graph's ``walk_update`` (all-reduce, optimiser step) outside the graph."""
+
+    def _record(self, g, batch, n_attr, warmup):
         self.g = g
-        dev = g.device
-        self._init_inputs(dev, batch, g.dim_z, n_attr)
-        kw = dict(no_content_loss=no_content_loss, no_gan_loss=no_gan_loss, clamp=clamp, layers=layers)
-        # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights), as stream capture requires
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1)):
-                forward_backward(g, self.z, self.alpha, **kw)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g.optimizers.zero_grad(set_to_none=True)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = forward_backward(g, self.z, self.alpha, **kw)
+        self._init_inputs(g.device, batch, g.dim_z, n_attr)
+        self.graph, self.out, self._ws_keep = record(g.device, self._step, warmup, lambda: g.optimizer.zero_grad(set_to_none=True))
         self.grads = [p.grad for p in g.walk.parameters()]          # static tensors inside the graph's pool, rewritten by every replay
-        # the graph's kernel nodes hold RAW pointers into the split-K workspaces of conv._WS (allocated during warm-up, outside the graph's
-        # pool): keep those tensors alive for as long as the graph, even if a later eager launch replaces the dict entry with a larger one
-        from . import conv
-        self._ws_keep = list(conv._WS.values())
-        self.launches = None
 
     def __call__(self, zs=None, alpha=None, optimize=True):
         if zs is not None:
             self.load(zs, alpha)
         self.graph.replay()
-        for p, gr in zip(self.g.walk.parameters(), self.grads):      # Adam reads p.grad: the graph's static gradient tensors
+        for p, gr in zip(self.g.walk.parameters(), self.grads):      # the optimiser reads p.grad
             p.grad = gr
         if optimize:
-            dist.average_gradients(self.g.walk.parameters())         # one RCCL all-reduce of <= 184 KB, outside the graph
-            self.g.optimizers.step()
+            self.g.walk_update()
         o = dict(self.out)
-        o['grad'] = self.grads[0]
+        o['grad'], o['grads'] = self.grads[0], self.grads
         return o
 
 
-class CapturedZStep(_StagedInputs):
+class CapturedStep(_CapturedWalkStep):
+    """``step(zs, alpha)`` == selfcheck.run_step(g, zs, alpha, ...) with the forward+backward replayed from one hipGraph (the three loss branches
+    fork from and join the captured stream)."""
+
+    def __init__(self, g, batch, n_attr, no_content_loss=False, no_gan_loss=False, clamp=False, layers=None, warmup=2):
+        self._flags = dict(no_content_loss=no_content_loss, no_gan_loss=no_gan_loss, clamp=clamp, layers=layers)
+        self._record(g, batch, n_attr, warmup)
+
+    def _step(self):
+        return forward_backward(self.g, self.z, self.alpha, **self._flags)
+
+
+class CapturedZStep(_CapturedWalkStep):
     """``step(zs, alpha_delta)`` == pggan.walk_training_step(g, zs, alpha_delta, ...) on the PGGAN graph (BASELINE config 1) with
     pggan.walk_forward_backward replayed from one hipGraph: the no-grad first pass, the clamp pair on the device, the walk in z, the second
     generator pass, zero_grad, loss and backward, all on one stream (no loss-branch forks: the recorded graph is a chain) and without noise.
-    The all-reduce and the optimiser step (pggan.walk_update: torch's Adam, or GuardedAdam's two library calls on fp16) follow every replay
-    outside the graph, so one graph serves 1 and N ranks.  The warm-up before capture runs loss and backward only, never the update: the walk,
-    the optimiser state and the scaler are what an eager run starts from.  The GAN term cannot be evaluated on this graph (pggan.py) and is off."""
+    The GAN term cannot be evaluated on this graph (pggan.py) and is off."""
 
     def __init__(self, g, batch, n_attr, no_content_loss=False, warmup=2):
-        from . import conv
-        self.g = g
-        dev = g.device
         self.no_content_loss = bool(no_content_loss)
-        self._init_inputs(dev, batch, g.dim_z, n_attr)
         init_state = getattr(g.optimizer, 'init_state', None)
         if init_state is not None:
             init_state()                                                   # GuardedAdam: moments, counters and guard words outside the graph's pool
-        # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights, the attribute-column index), as capture requires
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1)):
-                self._forward_backward()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g.optimizer.zero_grad(set_to_none=True)                           # the gradients become static tensors of the graph's pool
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.out = self._forward_backward()
-        self.grads = [p.grad for p in g.walk.parameters()]
-        self._ws_keep = list(conv._WS.values())                            # the kernel nodes hold raw pointers into the split-K workspaces
+        self._record(g, batch, n_attr, warmup)
 
-    def _forward_backward(self):
-        """One pggan.walk_forward_backward on the static inputs -> its results, detached: no reference to the autograd graph survives the call.
-        One that did would keep the walk's gradient accumulators on the warm-up's stream, and the capture would fork to that stream."""
+    def _step(self):
+        """One pggan.walk_forward_backward on the static inputs -> its results, detached (``record``'s second rule)."""
         from . import pggan
         loss, x0, x1, a0, target = pggan.walk_forward_backward(self.g, self.z, self.alpha, no_content_loss=self.no_content_loss, no_gan_loss=True)
         return dict(loss=loss.detach(), x0=x0.detach(), x1=x1.detach(), a0=a0.detach(), target=target.detach(), terms=self.g.last_terms)
-
-    def __call__(self, zs=None, alpha_delta=None, optimize=True):
-        from . import pggan
-        if zs is not None:
-            self.load(zs, alpha_delta)
-        self.graph.replay()
-        for p, gr in zip(self.g.walk.parameters(), self.grads):           # the optimiser reads p.grad: the graph's static gradient tensors
-            p.grad = gr
-        if optimize:
-            pggan.walk_update(self.g)
-        o = dict(self.out)
-        o['grads'] = self.grads
-        return o

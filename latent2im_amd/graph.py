@@ -155,6 +155,35 @@ def _checkpoint_or_synthetic(what, path):
                             'L2I_SYNTHETIC_WEIGHTS=1 to run on seeded random-init weights of the same architecture instead' % (what, path))
 
 
+def _regressor_state(src):
+    """The attribute regressor's weights (both graphs' load_networks); the source goes to ``src['R']``."""
+    if _checkpoint_or_synthetic('regressor (reg_path)', constants.reg_path):
+        src['R'] = constants.reg_path
+        return _to_numpy_state(torch.load(constants.reg_path, map_location='cpu')['model'])
+    src['R'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_R
+    return synth.resnet50_state(seed=constants.SYNTH_SEED_R)
+
+
+def _vgg19_state(src):
+    """The VGG-19 prefix's weights, torchvision's ``features.`` prefix stripped; the source goes to ``src['V']``."""
+    if _checkpoint_or_synthetic('VGG-19 (vgg_path; the reference downloads torchvision weights)', constants.vgg_path):
+        src['V'] = constants.vgg_path
+        return {k.replace('features.', ''): v for k, v in _to_numpy_state(torch.load(constants.vgg_path, map_location='cpu')).items()}
+    src['V'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_V
+    return synth.vgg19_prefix_state(seed=constants.SYNTH_SEED_V)
+
+
+def _attach_loss_scaler(nets, scale_for, resolution, device, src):
+    """Gradient scales of the fp16 path: the static exponents ``scale_for(resolution, per-rank batch)`` (nets16.loss_scale_for /
+    pggan_scale_for) — every rank's losses are means over its own shard — times one dynamic factor on the device; one scaler per graph, carried
+    by its networks.  The exponents go to ``src['loss_scale_log2']``."""
+    from . import nets16, optim
+    per_rank = max(constants.BATCH_SIZE // dist.world_size(), 1)
+    scaler = optim.LossScaler(scale_for(resolution, per_rank), device, growth_interval=constants.LOSS_SCALE_GROWTH_INTERVAL)
+    nets16.attach_scaler(nets, scaler)
+    src['loss_scale_log2'] = dict(scaler.log2)
+
+
 def load_networks(resolution, device, need_vgg=True, need_d=True):
     """Frozen nets from the checkpoint paths of ``constants`` (reference transform_base.py:522-549).  Deterministic synthetic
     weights of the same architecture (latent2im_amd.synth) are used only on explicit request (constants.ALLOW_SYNTHETIC_WEIGHTS);
@@ -166,12 +195,7 @@ def load_networks(resolution, device, need_vgg=True, need_d=True):
     else:
         g_state = synth.generator_state(resolution, seed=constants.SYNTH_SEED_G, noise_strength=constants.SYNTH_NOISE_STRENGTH)
         src['G'] = 'synthetic(seed=%d%s)' % (constants.SYNTH_SEED_G, ', noise_strength=%g' % constants.SYNTH_NOISE_STRENGTH if constants.SYNTH_NOISE_STRENGTH else '')
-    if _checkpoint_or_synthetic('regressor (reg_path)', constants.reg_path):
-        r_state = _to_numpy_state(torch.load(constants.reg_path, map_location='cpu')['model'])
-        src['R'] = constants.reg_path
-    else:
-        r_state = synth.resnet50_state(seed=constants.SYNTH_SEED_R)
-        src['R'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_R
+    r_state = _regressor_state(src)
     from . import conv
     if conv.PRECISION in conv.H8_PRECISIONS:                           # the 16-bit path (BASELINE config 5): bf16 h8 feature maps, one bf16 MFMA per MAC (nets16.py)
         from . import nets16
@@ -183,26 +207,13 @@ def load_networks(resolution, device, need_vgg=True, need_d=True):
     reg = RegCls(r_state, device=device)
     vgg = netD = None
     if need_vgg:
-        if _checkpoint_or_synthetic('VGG-19 (vgg_path; the reference downloads torchvision weights)', constants.vgg_path):
-            v_state = _to_numpy_state(torch.load(constants.vgg_path, map_location='cpu'))
-            v_state = {k.replace('features.', ''): v for k, v in v_state.items()}
-            src['V'] = constants.vgg_path
-        else:
-            v_state = synth.vgg19_prefix_state(seed=constants.SYNTH_SEED_V)
-            src['V'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_V
-        vgg = VggCls(v_state, device=device)
+        vgg = VggCls(_vgg19_state(src), device=device)
     if need_d:
         # the reference's netD is ALWAYS freshly initialised (never loaded): seeded here for reproducibility
         netD = DCls(synth.discriminator_state(resolution, seed=constants.SYNTH_SEED_D), resolution, device=device)
         src['D'] = 'random-init(seed=%d)' % constants.SYNTH_SEED_D
     if conv.PRECISION == 'f16':
-        # gradient scales of the fp16 path (nets16.loss_scale_for): static exponents for this resolution and the PER-RANK batch — every rank's losses
-        # are means over its own shard — times one dynamic factor on the device; one scaler per graph, carried by its four networks
-        from . import optim
-        per_rank = max(constants.BATCH_SIZE // dist.world_size(), 1)
-        scaler = optim.LossScaler(nets16.loss_scale_for(resolution, per_rank), device, growth_interval=constants.LOSS_SCALE_GROWTH_INTERVAL)
-        nets16.attach_scaler((netG, netD, reg, vgg), scaler)
-        src['loss_scale_log2'] = dict(scaler.log2)
+        _attach_loss_scaler((netG, netD, reg, vgg), nets16.loss_scale_for, resolution, device, src)
     return netG, netD, reg, vgg, src
 
 
@@ -245,26 +256,20 @@ class _RegBceFn(torch.autograd.Function):
         return torch.mul(g, g_loss), None, None, None, None          # (fp32 tensor x 0-dim float64 tensor -> fp32: one launch)
 
 
-class TransformGraph:
-    def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, stylegan_opts,
-                 nets=None):
+class WalkGraph:
+    """What the StyleGAN2 graph (TransformGraph below) and the PGGAN graph (pggan.TransformGraph) share: bookkeeping, the walk's optimiser, the
+    regressor read-out, the tail of the step, the fp16 calibration and the checkpoints.  A subclass builds its networks and its walk and supplies
+    ``get_logits``, ``get_alphas``, ``get_reg_loss``, ``get_content_loss``, ``get_w_loss``, ``_probe_step``, ``eager_step`` and
+    ``captured_step``: there the reference's two graphs differ."""
+
+    def __init__(self, lr, nsliders, loss_type, trainEmbed):
         assert (loss_type in ['l2', 'lpips']), 'unimplemented loss'
         if not torch.cuda.is_available():
             raise RuntimeError('latent2im_amd runs on an MI355X (ROCm) device only: no GPU is visible and there is no CPU path')
         self.lr = lr
         self.useGPU = constants.useGPU
         self.device = torch.device('cuda', torch.cuda.current_device())
-        self.img_size = constants.resolution
-        if nets is None:
-            nets = load_networks(self.img_size, self.device)
-        netG, netD, self.regressor, self.vgg19, self.weight_sources = nets
-        self.module = StyleGAN(netG, netD)
         self.reg_optmizer = None
-
-        self.attrTable = attrTable
-        self.attrList = attrList
-        self.attrIdx = self.get_attr_idx()
-
         self.dim_z = constants.DIM_Z
         self.Nsliders = nsliders
         self.num_channels = constants.NUM_CHANNELS
@@ -272,6 +277,114 @@ class TransformGraph:
         self.BCE_loss_logits = nn.BCEWithLogitsLoss()
         self.ContentLoss = ContentLoss()
         self.trainEmbed = trainEmbed
+        self.last_terms = None
+
+    def _make_optimizer(self, netG):
+        """fp16 elements (the networks carry a scaler, load_networks): Adam with GradScaler semantics on the device — a step whose gradient holds an
+        inf / NaN is skipped and the dynamic loss scale halves (optim.py); every other precision: torch's own, as in the reference
+        (transform_base.py:329-331)."""
+        self.loss_scaler = getattr(netG, 'scaler', None)
+        if self.loss_scaler is not None:
+            from . import optim
+            self.optimizer = optim.GuardedAdam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99), scaler=self.loss_scaler)
+        else:
+            self.optimizer = torch.optim.Adam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99))
+
+    def get_attr_idx(self):
+        return [self.attrTable[i] for i in self.attrList]
+
+    def _attr_columns(self):
+        """attrIdx as a device index tensor, built once: indexing with the python list would copy it host -> device on every call
+        (a synchronous copy, and not permitted while the step is being captured into a hipGraph)."""
+        t = getattr(self, '_attr_index', None)
+        if t is None or t.numel() != len(self.attrIdx) or t.device != self.device:
+            t = self._attr_index = torch.tensor(list(self.attrIdx), dtype=torch.long, device=self.device)
+        return t
+
+    def get_reg_preds(self, logit):
+        preds = self.regressor(logit).index_select(1, self._attr_columns())        # integer column select: bit-exact
+        if len(preds.size()) == 1:
+            preds = preds.unsqueeze(1)
+        return preds
+
+    def get_bce_loss(self, pred, y, eps=1e-12):
+        return -(y * pred.clamp(min=eps).log() + (1 - y) * (1 - pred).clamp(min=eps).log()).mean()
+
+    def walk_update(self):
+        """The tail of every step, eager or replayed: the data-parallel all-reduce of the walk gradient (one RCCL call of <= 184 KB for the linear
+        W+ walk), then the optimiser step."""
+        dist.average_gradients(self.walk.parameters())
+        self.optimizer.step()
+
+    def optimizeParametersAll(self, feed_dict, trainEmbed, updateGAN, no_content_loss=False, no_gan_loss=False):
+        self.optimizer.zero_grad()
+        loss = self.get_w_loss(feed_dict, no_content_loss, no_gan_loss)
+        loss.backward()
+        self.walk_update()
+        return loss
+
+    optimize_parameters = optimizeParametersAll              # BASELINE.json spelling
+
+    def calibrate_scales(self, n_steps, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False):
+        """--f16_calibrate: measure the fp16 path's static gradient exponents on THIS graph's weights (nets16.calibrate: ``n_steps`` probe steps a
+        round — forward, loss and backward as the graph's ``_probe_step`` runs them for these loss flags, fresh z and alpha draws, no optimiser
+        step — with a nets16.RangeMonitor behind the probe points).  The chosen exponents land in ``loss_scaler.log2`` and
+        ``weight_sources['loss_scale_log2']``; the walk, its gradients, the optimiser state, the scaler's dynamic factor and counters and the RNG
+        streams are left as they were.  Before the first capture only.  Returns nets16.calibrate's record."""
+        from . import hostutil, nets16
+        if self.loss_scaler is None:
+            raise RuntimeError('calibrate_scales: only the fp16 path (--precision f16) has gradient scales')
+        if getattr(self, '_captured_step', None) is not None:
+            raise RuntimeError('calibrate_scales after the step was captured: the recorded graph has the static scales baked in')
+        params = list(self.walk.parameters())
+        grads = [None if p.grad is None else p.grad.detach().clone() for p in params]
+        terms = self.last_terms
+        sl = dist.shard(self.BATCH_SIZE)
+
+        def probe(k):
+            zs = hostutil.z_sample(self.BATCH_SIZE, seed=nets16.CALIBRATE_SEED + k, dim_z=self.dim_z)[sl]
+            alpha, _, _ = self.get_train_alpha(zs, N_attr=len(self.attrList), trainEmbed=False)
+            self._probe_step(torch.Tensor(zs).to(self.device), torch.tensor(np.asarray(alpha)).float().to(self.device), clamp=clamp, layers=layers,
+                             no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
+        try:
+            rec = nets16.calibrate(self.loss_scaler, probe, int(n_steps), self.device)
+        finally:
+            torch.cuda.synchronize()
+            for p, g in zip(params, grads):
+                p.grad = g
+            self.last_terms = terms
+        self.weight_sources['loss_scale_log2'] = dict(self.loss_scaler.log2)
+        self.f16_calibration = rec
+        return rec
+
+    def save_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
+        print('Save W and GAN in %s and %s' % (save_path_w, save_path_gan))
+        if updateGAN:
+            raise NotImplementedError('jointly training the GAN is not implemented in the reference either (train.py:40-41)')
+        if dist.rank() == 0:
+            torch.save(self.walk, save_path_w + '_walk_module.ckpt')
+
+    def load_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
+        print('Load w in %s' % save_path_w)
+        self.walk = torch.load(save_path_w, map_location=self.device, weights_only=False)
+
+    def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7):
+        raise NotImplementedError('Subclass should implement vis_image_batch')
+
+
+class TransformGraph(WalkGraph):
+    def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, stylegan_opts,
+                 nets=None):
+        WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
+        self.img_size = constants.resolution
+        if nets is None:
+            nets = load_networks(self.img_size, self.device)
+        netG, netD, self.regressor, self.vgg19, self.weight_sources = nets
+        self.module = StyleGAN(netG, netD)
+
+        self.attrTable = attrTable
+        self.attrList = attrList
+        self.attrIdx = self.get_attr_idx()
 
         # the reference hard-codes step = 6 (256^2, transform_base.py:285); generalised: n_latent = 2*(step+1)
         self.step = int(math.log2(self.img_size)) - 2
@@ -294,21 +407,13 @@ class TransformGraph:
         else:
             raise NotImplementedError('unknown walk_type %r' % (walk_type,))
 
-        # fp16 elements: the same Adam with GradScaler semantics on the device — a step whose gradient holds an inf / NaN is skipped and the dynamic
-        # loss scale halves (optim.py); every other precision: torch's own, as in the reference (transform_base.py:329-331)
-        self.loss_scaler = getattr(netG, 'scaler', None)
-        if self.loss_scaler is not None:
-            from . import optim
-            self.optimizers = optim.GuardedAdam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99), scaler=self.loss_scaler)
-        else:
-            self.optimizers = torch.optim.Adam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99))
+        self._make_optimizer(netG)
         self.walk_type = walk_type
-        self.last_terms = None
+
+    # the reference's StyleGAN2 graph spells its optimiser ``optimizers`` (transform_base.py:329): the same slot
+    optimizers = property(lambda self: self.optimizer, lambda self, opt: setattr(self, 'optimizer', opt))
 
     # -- reference helpers ---------------------------------------------------------------------------------------
-    def get_attr_idx(self):
-        return [self.attrTable[i] for i in self.attrList]
-
     def get_logits(self, inputs_dict, reshape=True):
         if self.stylegan_opts.latent == 'z':
             raise NameError("latent: the reference's Generator.forward fails for input_is_latent=False (networks.py:471-494)")
@@ -331,20 +436,6 @@ class TransformGraph:
             layers = [int(l) for l in layers]                 # the reference passes strings through
         return self.walk(multi_ws, alpha=alpha, layers=layers)
 
-    def _attr_columns(self):
-        """attrIdx as a device index tensor, built once: indexing with the python list would copy it host -> device on every call
-        (a synchronous copy, and not permitted while the step is being captured into a hipGraph)."""
-        t = getattr(self, '_attr_index', None)
-        if t is None or t.numel() != len(self.attrIdx) or t.device != self.device:
-            t = self._attr_index = torch.tensor(list(self.attrIdx), dtype=torch.long, device=self.device)
-        return t
-
-    def get_reg_preds(self, logit):
-        preds = self.regressor(logit).index_select(1, self._attr_columns())        # integer column select: bit-exact
-        if len(preds.size()) == 1:
-            preds = preds.unsqueeze(1)
-        return preds
-
     def get_alphas(self, alpha_org, alpha_target):
         """train.py flow (transform_base.py:405-408): epsilon = target - org."""
         return alpha_target - alpha_org
@@ -353,9 +444,6 @@ class TransformGraph:
         """train_multi_attr.py:113 flow (graphs/pggan/transform_base.py:358-364): (clamped target, new delta)."""
         alpha_target = torch.clamp(alpha_org + alpha_delta, min=0, max=1)
         return alpha_target, alpha_target - alpha_org
-
-    def get_bce_loss(self, pred, y, eps=1e-12):
-        return -(y * pred.clamp(min=eps).log() + (1 - y) * (1 - pred).clamp(min=eps).log()).mean()
 
     def get_reg_loss(self, feed_dict):
         logit = feed_dict['logit']
@@ -432,60 +520,38 @@ class TransformGraph:
                                gan=None if gan_loss is None else gan_loss.detach())
         return loss
 
-    def optimizeParametersAll(self, feed_dict, trainEmbed, updateGAN, no_content_loss=False, no_gan_loss=False):
-        self.optimizers.zero_grad()
-        loss = self.get_w_loss(feed_dict, no_content_loss, no_gan_loss)
-        loss.backward()
-        dist.average_gradients(self.walk.parameters())        # data parallel: one RCCL all-reduce of <= 184 KB
-        self.optimizers.step()
-        return loss
+    # -- the step as the drivers run it ----------------------------------------------------------------------------
+    def _probe_step(self, z, alpha, **flags):
+        from . import capture
+        capture.forward_backward(self, z, alpha, **flags)
 
-    optimize_parameters = optimizeParametersAll              # BASELINE.json spelling
+    def eager_step(self, zs_batch, alpha_for_graph, *, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False, trainEmbed=False,
+                   updateGAN=False):
+        """One training step launched call by call, in the reference's order (train.py:56-101; ``clamp``: train_multi_attr.py:113,133) ->
+        (loss, original images, edited images)."""
+        z_global = torch.Tensor(zs_batch).to(self.device)                        # train.py:56
+        w_global = self.get_w(z_global)                                          # :62
+        out_zs = self.get_logits({'z': z_global, 'w': w_global})                 # :66
+        if not no_content_loss:
+            self.prefetch_content_taps(out_zs)                                   # the VGG taps of the original start beside the regressor / second generator pass
+        alpha_org = self.get_reg_preds(out_zs)                                   # :69
+        ag = torch.tensor(alpha_for_graph).float().to(self.device)               # :84-85
+        if clamp:
+            alpha_target, epsilon = self.get_alphas_clamped(alpha_org, ag)
+        else:                                                                    # train.py:86
+            alpha_target, epsilon = ag, self.get_alphas(alpha_org, ag)
+        w_new = self.get_w_new_tensor(w_global, epsilon, layers=layers)          # :89
+        transformed_output = self.get_logits({'z': z_global, 'w': w_new})        # :94
+        feed_dict = {'w': w_new, 'org': out_zs, 'logit': transformed_output, 'alpha': alpha_target}
+        loss = self.optimizeParametersAll(feed_dict, trainEmbed=trainEmbed, updateGAN=updateGAN, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
+        return loss, out_zs, transformed_output
 
-    def calibrate_scales(self, n_steps, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False):
-        """--f16_calibrate: measure the fp16 path's static gradient exponents on THIS graph's weights (nets16.calibrate: ``n_steps`` probe steps a
-        round — forward, loss and backward as capture.forward_backward runs them for these loss flags, fresh z and alpha draws, no optimiser step —
-        with a nets16.RangeMonitor behind the probe points).  The chosen exponents land in ``loss_scaler.log2`` and
-        ``weight_sources['loss_scale_log2']``; the walk, its gradients, the optimiser state, the scaler's dynamic factor and counters and the RNG
-        streams are left as they were.  Before the first capture only.  Returns nets16.calibrate's record."""
-        from . import capture, hostutil, nets16
-        if self.loss_scaler is None:
-            raise RuntimeError('calibrate_scales: only the fp16 path (--precision f16) has gradient scales')
-        if getattr(self, '_captured_step', None) is not None:
-            raise RuntimeError('calibrate_scales after the step was captured: the recorded graph has the static scales baked in')
-        params = list(self.walk.parameters())
-        grads = [None if p.grad is None else p.grad.detach().clone() for p in params]
-        terms = self.last_terms
-        sl = dist.shard(self.BATCH_SIZE)
-
-        def probe(k):
-            zs = hostutil.z_sample(self.BATCH_SIZE, seed=nets16.CALIBRATE_SEED + k, dim_z=self.dim_z)[sl]
-            alpha, _, _ = self.get_train_alpha(zs, N_attr=len(self.attrList), trainEmbed=False)
-            capture.forward_backward(self, torch.Tensor(zs).to(self.device), torch.tensor(alpha).float().to(self.device), no_content_loss=no_content_loss,
-                                     no_gan_loss=no_gan_loss, clamp=clamp, layers=layers)
-        try:
-            rec = nets16.calibrate(self.loss_scaler, probe, int(n_steps), self.device)
-        finally:
-            torch.cuda.synchronize()
-            for p, g in zip(params, grads):
-                p.grad = g
-            self.last_terms = terms
-        self.weight_sources['loss_scale_log2'] = dict(self.loss_scaler.log2)
-        self.f16_calibration = rec
-        return rec
+    def captured_step(self, batch, n_attr, *, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False):
+        """The same step as a hipGraph for ``batch`` samples a replay (capture.CapturedStep): what trainer.train_step asks for under --hip_graph."""
+        from . import capture
+        return capture.CapturedStep(self, batch, n_attr, clamp=clamp, layers=layers, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
 
     # -- checkpoints ---------------------------------------------------------------------------------------------
-    def save_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
-        print('Save W and GAN in %s and %s' % (save_path_w, save_path_gan))
-        if updateGAN:
-            raise NotImplementedError('jointly training the GAN is not implemented in the reference either (train.py:40-41)')
-        if dist.rank() == 0:
-            torch.save(self.walk, save_path_w + '_walk_module.ckpt')
-
-    def load_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
-        print('Load w in %s' % save_path_w)
-        self.walk = torch.load(save_path_w, map_location=self.device, weights_only=False)
-
     def load_multi_models_from_single(self, save_path_ws, save_path_gan, trainEmbed=False, updateGAN=False,
                                       single_transform_name=None, index=None):
         for i in range(len(save_path_ws)):
@@ -586,13 +652,9 @@ class TransformGraph:
                             dists[k].append(float(face_d[i]))
         return multi_attr, attri_org, imgs, orgs, dists
 
-    def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7):
-        raise NotImplementedError('Subclass should implement vis_image_batch')
-
 
 class PixelTransform(TransformGraph):
-    def __init__(self, *args, **kwargs):
-        TransformGraph.__init__(self, *args, **kwargs)
+    """transform_base.py:901-903."""
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -657,14 +719,16 @@ class SceneTransform:
 # ----------------------------------------------------------------------------------------------------------------
 # plugin lookup
 # ----------------------------------------------------------------------------------------------------------------
-def _make_graph(name, op_cls):
+def _make_graph(name, op_cls, pixel_cls=PixelTransform, size_constant='resolution'):
+    """transform_graph_scene.py:5-125: ``pixel_cls`` (a graph's PixelTransform) with ``op_cls``'s alpha sampler; the image size is read from
+    ``constants`` when a graph is built."""
     def __init__(self, lr=0.001, walk_type='NNz', loss='l2', eps=1.41, N_f=4, **kwargs):
         nsliders = 1
         self.walk_type = walk_type
         self.num_channels = constants.NUM_CHANNELS
         self.Nsliders = nsliders
-        self.img_size = constants.resolution
-        PixelTransform.__init__(self, lr, walk_type, nsliders, loss, eps, N_f, **kwargs)
+        self.img_size = getattr(constants, size_constant)
+        pixel_cls.__init__(self, lr, walk_type, nsliders, loss, eps, N_f, **kwargs)
         op_cls.__init__(self)
 
     def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7, max_alpha=None,
@@ -676,7 +740,7 @@ def _make_graph(name, op_cls):
             alphas = np.linspace(0, 1, num_panels)
         return [self.scale_test_alpha_for_graph(a, zs_batch) for a in alphas], list(alphas)
 
-    return type(name, (PixelTransform, op_cls), {'__init__': __init__, 'vis_image_batch': vis_image_batch})
+    return type(name, (pixel_cls, op_cls), {'__init__': __init__, 'vis_image_batch': vis_image_batch, '__module__': pixel_cls.__module__})
 
 
 SceneGraph = _make_graph('SceneGraph', SceneTransform)

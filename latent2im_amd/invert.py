@@ -126,13 +126,12 @@ class _Replay:
     guarded optimiser's update, ``curve[idx] = loss`` and ``idx += 1`` on ONE stream.  Static inputs, refilled per image outside the graph: the
     batch, its four target Grams, W+, the optimiser's buffers and step counter, the curve index and (when given) the noise maps; without a noise
     list the maps are drawn inside the graph from torch's graph-safe Philox stream, fresh on every replay.  The fp16 scaler is the Inverter's and
-    carries over from image to image, as on the eager loop.  The warm-up before capture runs the loss and its backward only, never the update:
-    W+, the optimiser state and the scaler are what an eager run starts from."""
+    carries over from image to image, as on the eager loop.  Recorded by capture.record."""
 
     MIN_CAPACITY = 1024
 
     def __init__(self, inv, batch, grams, start, noise, n_loops, warmup=2):
-        from . import conv
+        from .capture import record
         from .optim import GuardedAdam, GuardedSGD
         self.fixed_noise = noise is not None
         self.batch = batch.clone()
@@ -147,31 +146,19 @@ class _Replay:
         self.capacity = max(int(n_loops), self.MIN_CAPACITY)
         self.curve = torch.zeros(self.capacity, dtype=torch.float32, device=batch.device)
         self.idx = torch.zeros(1, dtype=torch.int64, device=batch.device)
-        # warm-up on a side stream (allocator pools, split-K workspaces, lazily packed weights), as stream capture requires
-        s = torch.cuda.Stream(device=batch.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(warmup, 1)):
-                self._forward_backward(inv)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self.opt.zero_grad(set_to_none=True)                                   # w.grad becomes a static tensor of the graph's pool
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            loss, self.out = self._forward_backward(inv)
-            self.opt.step()
-            self.curve.index_copy_(0, self.idx, loss.reshape(1))
-            self.idx += 1
-        # the graph's kernel nodes hold raw pointers into the split-K workspaces of conv._WS: they live as long as the graph
-        self._ws_keep = list(conv._WS.values())
+        self.graph, self.out, self._ws_keep = record(batch.device, lambda: self._step(inv), warmup, lambda: self.opt.zero_grad(set_to_none=True))
 
-    def _forward_backward(self, inv):
-        """Loss and backward of one iteration -> (loss, image), both detached: no reference to the autograd graph survives the call.  One that did
-        would keep W+'s gradient accumulator on the warm-up's stream, and the capture would fork to that stream to run it."""
+    def _step(self, inv):
+        """Loss and backward of one iteration -> the image, detached (capture.record's rules); while recording, also the update, the curve write
+        and the index increment."""
         loss, out = inv.loss(self.w, self.batch, self.grams, self.noise)
         self.w.grad = None
         loss.backward()
-        return loss.detach(), out.detach()
+        if torch.cuda.is_current_stream_capturing():
+            self.opt.step()
+            self.curve.index_copy_(0, self.idx, loss.detach().reshape(1))
+            self.idx += 1
+        return out.detach()
 
     @torch.no_grad()
     def load(self, batch, grams, start, noise):

@@ -29,10 +29,12 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import constants, dist, synth
+from . import constants, synth
 from . import conv as C
 from . import kernels as K
-from .graph import ContentLoss, FaceTransform, SceneTransform, _checkpoint_or_synthetic, _to_numpy_state
+from .graph import ContentLoss  # noqa: F401  (graphs/pggan/transform_base.py re-exports it from here)
+from .graph import (FaceTransform, SceneTransform, WalkGraph, _attach_loss_scaler, _checkpoint_or_synthetic, _make_graph, _regressor_state,
+                    _to_numpy_state, _vgg19_state)
 from .perceptual import VGG19Prefix
 from .regressor import ResNet50
 
@@ -251,62 +253,30 @@ def load_networks(device, need_vgg=True):
     else:
         g_state = synth.pggan_generator_state(seed=constants.SYNTH_SEED_G)
         src['G'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_G
-    if _checkpoint_or_synthetic('regressor (reg_path)', constants.reg_path):
-        r_state = _to_numpy_state(torch.load(constants.reg_path, map_location='cpu')['model'])
-        src['R'] = constants.reg_path
-    else:
-        r_state = synth.resnet50_state(seed=constants.SYNTH_SEED_R)
-        src['R'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_R
-    vgg = None
-    if need_vgg:
-        if _checkpoint_or_synthetic('VGG-19 (vgg_path; the reference downloads torchvision weights)', constants.vgg_path):
-            v_state = {k.replace('features.', ''): v for k, v in _to_numpy_state(torch.load(constants.vgg_path, map_location='cpu')).items()}
-            src['V'] = constants.vgg_path
-        else:
-            v_state = synth.vgg19_prefix_state(seed=constants.SYNTH_SEED_V)
-            src['V'] = 'synthetic(seed=%d)' % constants.SYNTH_SEED_V
+    r_state = _regressor_state(src)
+    v_state = _vgg19_state(src) if need_vgg else None
     if C.PRECISION in C.H8_PRECISIONS:                                  # the 16-bit path: h8 feature maps, 16-bit MFMA with fp32 accumulation (nets16.py)
         from . import nets16
         GenCls, RegCls, VggCls = nets16.PGGenerator, nets16.ResNet50, nets16.VGG19Prefix
     else:
         GenCls, RegCls, VggCls = Generator, ResNet50, VGG19Prefix
     src['precision'] = C.PRECISION
-    if need_vgg:
-        vgg = VggCls(v_state, device=device)
+    vgg = VggCls(v_state, device=device) if need_vgg else None
     nets = GenCls(g_state, device=device), RegCls(r_state, device=device), vgg
     if C.PRECISION == 'f16':
-        # gradient scales of the fp16 path (nets16.pggan_scale_for): static exponents for the PER-RANK batch — every rank's losses are means over
-        # its own shard — times one dynamic factor on the device; one scaler per graph, carried by its three networks (graph.load_networks)
-        from . import optim
-        per_rank = max(constants.BATCH_SIZE // dist.world_size(), 1)
-        scaler = optim.LossScaler(nets16.pggan_scale_for(constants.PG_RESOLUTION, per_rank), device, growth_interval=constants.LOSS_SCALE_GROWTH_INTERVAL)
-        nets16.attach_scaler(nets, scaler)
-        src['loss_scale_log2'] = dict(scaler.log2)
+        _attach_loss_scaler(nets, nets16.pggan_scale_for, constants.PG_RESOLUTION, device, src)
     return nets + (src,)
 
 
-class TransformGraph:
+class TransformGraph(WalkGraph):
     def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, pgan_opts=None, nets=None):
-        assert (loss_type in ['l2', 'lpips']), 'unimplemented loss'
-        if not torch.cuda.is_available():
-            raise RuntimeError('latent2im_amd runs on an MI355X (ROCm) device only: no GPU is visible and there is no CPU path')
-        self.lr = lr
-        self.useGPU = constants.useGPU
-        self.device = torch.device('cuda', torch.cuda.current_device())
+        WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
         if nets is None:
             nets = load_networks(self.device)
         netG, self.regressor, self.vgg19, self.weight_sources = nets
         self.module = PGGAN(netG, None)
-        self.reg_optmizer = None
-        self.dim_z = constants.DIM_Z
-        self.Nsliders = nsliders
         self.img_size = constants.PG_RESOLUTION
-        self.num_channels = constants.NUM_CHANNELS
-        self.BATCH_SIZE = constants.BATCH_SIZE
-        self.BCE_loss_logits = nn.BCEWithLogitsLoss()
-        self.ContentLoss = ContentLoss()
-        self.trainEmbed = trainEmbed
-        self.step = 6                                            # PGAN 256 (transform_base.py:244-246)
+        self.step = 6                                           # PGAN 256 (transform_base.py:244-246)
         self.alpha = 0
         if not attrTable:                                        # transform_base.py:248-256
             from .hostutil import SCENE_DEFAULT_TABLE
@@ -320,26 +290,10 @@ class TransformGraph:
             self.walk = WalkLinearZ_free(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
         else:                                                    # "MLP" (transform_base.py:270-275): every other walk type
             self.walk = WalkMlpZ3(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
-        self.loss_scaler = getattr(netG, 'scaler', None)                # fp16 elements: the gradient scales the three networks share (load_networks)
-        if self.loss_scaler is not None:
-            from . import optim
-            # a non-finite walk gradient skips the update and halves the dynamic scale, on the device (graph.TransformGraph does the same)
-            self.optimizer = optim.GuardedAdam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99), scaler=self.loss_scaler)
-        else:
-            self.optimizer = torch.optim.Adam(self.walk.parameters(), lr=self.lr, betas=(0.5, 0.99))
+        self._make_optimizer(netG)
         self.walk_type = walk_type
         self.N_f = N_f
         self.eps = eps
-        self.last_terms = None
-
-    def get_attr_idx(self):
-        return [self.attrTable[i] for i in self.attrList]
-
-    def _attr_columns(self):
-        t = getattr(self, '_attr_index', None)
-        if t is None or t.numel() != len(self.attrIdx):
-            t = self._attr_index = torch.tensor(list(self.attrIdx), dtype=torch.long, device=self.device)
-        return t
 
     def get_logits(self, inputs_dict, reshape=True):
         """netG(z) then F.upsample(size=half, mode='bilinear') (:308-321) = the mean of every 2x2 window."""
@@ -350,19 +304,10 @@ class TransformGraph:
     def get_z_new_tensor(self, z, alpha, name=None, trainEmbed=False, index_=None, layers=None):
         return self.walk(z.squeeze(), alpha, name=name, index_=index_)
 
-    def get_reg_preds(self, logit):
-        preds = self.regressor(logit).index_select(1, self._attr_columns())
-        if len(preds.size()) == 1:
-            preds = preds.unsqueeze(1)
-        return preds
-
     def get_alphas(self, alpha_org, alpha_delta):
         """(clamped target, new delta) (:358-364) — the pair train_multi_attr.py:113 unpacks."""
         alpha_target = torch.clamp(alpha_org + alpha_delta, min=0, max=1)
         return alpha_target, alpha_target - alpha_org
-
-    def get_bce_loss(self, pred, y, eps=1e-12):
-        return -(y * pred.clamp(min=eps).log() + (1 - y) * (1 - pred).clamp(min=eps).log()).mean()
 
     def get_reg_loss(self, feed_dict):
         """:366-380 — preds[:, attrIdx].unsqueeze(1) is [B,1,C] against alpha [B,C]: the BCE broadcasts to [B,B,C] before the mean (kept)."""
@@ -392,61 +337,22 @@ class TransformGraph:
         self.last_terms = dict(reg=reg_loss.detach(), cont=None if content_losses is None else content_losses.detach(), gan=None)
         return loss
 
-    def optimizeParametersAll(self, feed_dict, trainEmbed, updateGAN, no_content_loss=False, no_gan_loss=False):
-        self.optimizer.zero_grad()
-        loss = self.get_w_loss(feed_dict, no_content_loss, no_gan_loss)
-        loss.backward()
-        dist.average_gradients(self.walk.parameters())
-        self.optimizer.step()
-        return loss
+    def _probe_step(self, z, alpha, no_content_loss=False, **ignored):
+        """calibrate_scales' probe: walk_forward_backward.  The GAN term cannot be evaluated here, so the D exponent, which has no tags, keeps its
+        start; ``clamp`` / ``layers`` are the StyleGAN2 graph's and are ignored."""
+        walk_forward_backward(self, z, alpha, no_content_loss=no_content_loss, no_gan_loss=True)
 
-    optimize_parameters = optimizeParametersAll
+    def eager_step(self, zs_batch, alpha_delta, *, clamp=True, layers=None, no_content_loss=False, no_gan_loss=True, trainEmbed=False, updateGAN=False):
+        """walk_training_step -> (loss, original images, edited images).  The walk in z always clamps and has no ``layers``."""
+        loss, out_zs, transformed_output, _, _ = walk_training_step(self, torch.Tensor(zs_batch).to(self.device), alpha_delta,
+                                                                    no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
+        return loss, out_zs, transformed_output
 
-    def calibrate_scales(self, n_steps, clamp=True, layers=None, no_content_loss=False, no_gan_loss=True):
-        """graph.TransformGraph.calibrate_scales on this graph: the probe step is walk_forward_backward (the GAN term cannot be evaluated here, so
-        the D exponent, which has no tags, keeps its start; ``clamp`` / ``layers`` are the StyleGAN2 graph's and are ignored)."""
-        from . import hostutil, nets16
-        if self.loss_scaler is None:
-            raise RuntimeError('calibrate_scales: only the fp16 path (--precision f16) has gradient scales')
-        if getattr(self, '_captured_step', None) is not None:
-            raise RuntimeError('calibrate_scales after the step was captured: the recorded graph has the static scales baked in')
-        params = list(self.walk.parameters())
-        grads = [None if p.grad is None else p.grad.detach().clone() for p in params]
-        terms = self.last_terms
-        sl = dist.shard(self.BATCH_SIZE)
-
-        def probe(k):
-            zs = hostutil.z_sample(self.BATCH_SIZE, seed=nets16.CALIBRATE_SEED + k, dim_z=self.dim_z)[sl]
-            alpha, _, _ = self.get_train_alpha(zs, N_attr=len(self.attrList), trainEmbed=False)
-            walk_forward_backward(self, torch.Tensor(zs).to(self.device), torch.tensor(np.asarray(alpha)).float().to(self.device),
-                                  no_content_loss=no_content_loss, no_gan_loss=True)
-        try:
-            rec = nets16.calibrate(self.loss_scaler, probe, int(n_steps), self.device)
-        finally:
-            torch.cuda.synchronize()
-            for p, g in zip(params, grads):
-                p.grad = g
-            self.last_terms = terms
-        self.weight_sources['loss_scale_log2'] = dict(self.loss_scaler.log2)
-        self.f16_calibration = rec
-        return rec
-
-    def captured_z_step(self, batch, n_attr, no_content_loss=False):
-        """The step as a hipGraph for ``batch`` samples a replay (capture.CapturedZStep): what trainer.train_step asks a graph without get_w for
-        under --hip_graph."""
+    def captured_step(self, batch, n_attr, *, clamp=True, layers=None, no_content_loss=False, no_gan_loss=True):
+        """The step as a hipGraph for ``batch`` samples a replay (capture.CapturedZStep): what trainer.train_step asks for under --hip_graph.
+        None with the GAN term on: that step raises (get_w_loss), and it does so on the eager route."""
         from . import capture
-        return capture.CapturedZStep(self, batch, n_attr, no_content_loss=no_content_loss)
-
-    def save_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
-        print('Save W and GAN in %s and %s' % (save_path_w, save_path_gan))
-        if updateGAN:
-            raise NotImplementedError('jointly training the GAN is commented out in the reference (transform_base.py:414-468)')
-        if dist.rank() == 0:
-            torch.save(self.walk, save_path_w + '_walk_module.ckpt')
-
-    def load_multi_models(self, save_path_w, save_path_gan, trainEmbed=False, updateGAN=False, single_transform_name=None):
-        print('Load w in %s' % save_path_w)
-        self.walk = torch.load(save_path_w, map_location=self.device, weights_only=False)
+        return capture.CapturedZStep(self, batch, n_attr, no_content_loss=no_content_loss) if no_gan_loss else None
 
     def clip_ims(self, ims):
         return np.uint8(np.clip(((ims + 1) / 2.0) * 256, 0, 255))              # 256, not 255: transform_base.py:595
@@ -485,9 +391,6 @@ class TransformGraph:
             written.append(path)
         return written
 
-    def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7):
-        raise NotImplementedError('Subclass should implement vis_image_batch')
-
 
 def walk_forward_backward(graph, z, alpha_delta, no_content_loss=False, no_gan_loss=True):
     """The z-walk step up to the walk gradient, on DEVICE inputs and without a host synchronisation (capture.CapturedZStep records exactly this
@@ -507,20 +410,19 @@ def walk_forward_backward(graph, z, alpha_delta, no_content_loss=False, no_gan_l
 
 
 def walk_update(graph):
-    """The tail of the step (optimizeParametersAll's last two lines): all-reduce of the walk gradient, optimiser step."""
-    dist.average_gradients(graph.walk.parameters())
-    graph.optimizer.step()
+    """The tail of the step: WalkGraph.walk_update (all-reduce of the walk gradient, optimiser step)."""
+    graph.walk_update()
 
 
 def walk_training_step(graph, zs_batch, alpha_delta, no_content_loss=False, no_gan_loss=True):
     """One z-walk training step in the order of train_multi_attr.py:93-140 on the PGGAN graph's own methods.  (The shipped drivers call
     ``get_w`` / ``get_w_new_tensor``, which only the StyleGAN2 graph has; the PGGAN graph is driven method by method — this is that
-    sequence; trainer.train_step routes a graph without ``get_w`` here.)  walk_forward_backward + walk_update: the two parts the captured step
-    (capture.CapturedZStep) replays and runs.  Returns (loss, x0, x1, alpha_org, alpha_target)."""
+    sequence, the graph's ``eager_step``.)  walk_forward_backward + walk_update: the two parts the captured step (capture.CapturedZStep)
+    replays and runs.  Returns (loss, x0, x1, alpha_org, alpha_target)."""
     z = zs_batch if torch.is_tensor(zs_batch) else torch.Tensor(zs_batch).to(graph.device)
     ad = alpha_delta if torch.is_tensor(alpha_delta) else torch.tensor(np.asarray(alpha_delta)).float().to(graph.device)
     r = walk_forward_backward(graph, z, ad, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
-    walk_update(graph)
+    graph.walk_update()
     return r
 
 
@@ -537,28 +439,8 @@ class _Half(torch.autograd.Function):
 
 
 class PixelTransform(TransformGraph):
-    def __init__(self, *args, **kwargs):
-        TransformGraph.__init__(self, *args, **kwargs)
+    """transform_base.py: the graph the plugin classes are built over."""
 
 
-def _make_graph(name, op_cls):
-    def __init__(self, lr=0.001, walk_type='NNz', loss='l2', eps=1.41, N_f=4, **kwargs):
-        nsliders = 1
-        self.walk_type = walk_type
-        self.num_channels = constants.NUM_CHANNELS
-        self.Nsliders = nsliders
-        self.img_size = constants.PG_RESOLUTION
-        PixelTransform.__init__(self, lr, walk_type, nsliders, loss, eps, N_f, **kwargs)
-        op_cls.__init__(self)
-
-    def vis_image_batch(self, graph_inputs, filename, batch_start, wgt=False, wmask=False, num_panels=7, max_alpha=None, min_alpha=None,
-                        N_attr=40):
-        zs_batch = graph_inputs['z']
-        alphas = np.linspace(min_alpha, max_alpha, num_panels) if (max_alpha is not None and min_alpha is not None) else np.linspace(0, 1, num_panels)
-        return [self.scale_test_alpha_for_graph(a, zs_batch) for a in alphas], list(alphas)
-
-    return type(name, (PixelTransform, op_cls), {'__init__': __init__, 'vis_image_batch': vis_image_batch})
-
-
-SceneGraph = _make_graph('SceneGraph', SceneTransform)
-faceGraph = _make_graph('faceGraph', FaceTransform)
+SceneGraph = _make_graph('SceneGraph', SceneTransform, PixelTransform, 'PG_RESOLUTION')
+faceGraph = _make_graph('faceGraph', FaceTransform, PixelTransform, 'PG_RESOLUTION')

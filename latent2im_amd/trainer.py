@@ -1,6 +1,6 @@
 """The training drivers' loop (reference train.py:25-134 and train_multi_attr.py:43-231), single process or one
 process per GPU.  Call order per iteration is the reference's: get_w -> get_logits -> get_reg_preds -> get_train_alpha ->
-get_alphas -> get_w_new_tensor -> get_logits -> optimizeParametersAll (a graph without get_w, the PGGAN graph, runs
+get_alphas -> get_w_new_tensor -> get_logits -> optimizeParametersAll (graph.TransformGraph.eager_step; the PGGAN graph's is
 pggan.walk_training_step).  Under data parallelism every rank draws the same
 z (seed = epoch) and the same alpha (same numpy seed) and takes every world-th sample of the batch (dist.shard: strided shards keep the discriminator's stddev groups whole)."""
 import logging
@@ -9,7 +9,6 @@ import os
 import time
 
 import numpy as np
-import torch
 
 from . import constants, dist, hostutil
 
@@ -44,68 +43,33 @@ def make_samples(img_tensor, output_dir, epoch, optim_iter, batch_size, pre_path
 
 
 def train_step(graphs, zs_batch, attrList, layers=None, trainEmbed=False, updateGAN=False, opt=None, multi_attr=False):
-    """One iteration of the hot loop.  ``zs_batch``: this rank's [B_local, 512] numpy slice.  Returns
-    (loss tensor, alpha_for_target, out_zs, transformed_output)."""
-    if not hasattr(graphs, 'get_w'):
-        # the PGGAN graph (config 1) walks in z: no get_w / get_w_new_tensor; its own sequence is pggan.walk_training_step, and the alpha drawn
-        # here is the delta (train_multi_attr.py:113 on transform_base.py:358-364's clamp pair)
-        hip_graph = opt is not None and getattr(opt, 'hip_graph', False)
-        if hip_graph and not hasattr(graphs, 'captured_z_step'):
-            raise NotImplementedError('--hip_graph records the StyleGAN2 step (capture.CapturedStep) or the PGGAN z-walk step (capture.CapturedZStep); '
-                                      'this graph offers neither')
-        from . import pggan
-        alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
-        # --hip_graph: the same step, recorded once and replayed (a ragged last batch, and the GAN term, which raises, run eagerly)
-        if hip_graph and opt.no_gan_loss and not trainEmbed and zs_batch.shape[0] == _captured_z_batch(graphs, zs_batch, alpha_for_graph, opt):
-            r = graphs._captured_step(zs_batch, alpha_for_graph)
-            return r['loss'], alpha_for_target, r['x0'], r['x1']
-        loss, out_zs, transformed_output, _, _ = pggan.walk_training_step(graphs, torch.Tensor(zs_batch).to(graphs.device), alpha_for_graph,
-                                                                          no_content_loss=bool(opt and opt.no_content_loss),
-                                                                          no_gan_loss=bool(opt and opt.no_gan_loss))
-        return loss, alpha_for_target, out_zs, transformed_output
-    if opt is not None and getattr(opt, 'hip_graph', False) and not trainEmbed and zs_batch.shape[0] == _captured_batch(graphs, zs_batch):
-        # --hip_graph: the same calls, recorded once (capture.CapturedStep) and replayed; alpha is still drawn on the host
-        alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
+    """One iteration of the hot loop.  ``zs_batch``: this rank's [B_local, 512] numpy slice.  The alpha of the step is drawn here, once, from the
+    global numpy RNG (for the PGGAN graph it is the delta of train_multi_attr.py:113's clamp pair); the graph runs the step, call by call
+    (``eager_step``) or, under --hip_graph, recorded once and replayed (``captured_step``): full batches replay, a ragged last batch, trainEmbed and
+    a step the graph does not record (the PGGAN graph's GAN term, which raises) or recorded with other flags run eagerly.
+    Returns (loss tensor, alpha_for_target, out_zs, transformed_output)."""
+    hip_graph = opt is not None and getattr(opt, 'hip_graph', False)
+    if hip_graph and not hasattr(graphs, 'captured_step'):
+        raise NotImplementedError('--hip_graph records the StyleGAN2 step (capture.CapturedStep) or the PGGAN z-walk step (capture.CapturedZStep); '
+                                  'this graph offers neither')
+    flags = dict(clamp=multi_attr, layers=layers, no_content_loss=bool(opt and opt.no_content_loss), no_gan_loss=bool(opt and opt.no_gan_loss))
+    alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
+    if hip_graph and not trainEmbed and zs_batch.shape[0] == _captured_batch(graphs, zs_batch.shape[0], len(attrList), flags):
         r = graphs._captured_step(zs_batch, alpha_for_graph)
         return r['loss'], alpha_for_target, r['x0'], r['x1']
-    z_global = torch.Tensor(zs_batch).to(graphs.device)                       # train.py:56
-    w_global = graphs.get_w(z_global)                                          # :62
-    out_zs = graphs.get_logits({'z': z_global, 'w': w_global})                 # :66
-    if not (opt and opt.no_content_loss) and hasattr(graphs, 'prefetch_content_taps'):
-        graphs.prefetch_content_taps(out_zs)                                   # the VGG taps of the original start beside the regressor / second generator pass
-    alpha_org = graphs.get_reg_preds(out_zs)                                   # :69
-    alpha_for_graph, alpha_for_target, _ = graphs.get_train_alpha(zs_batch, N_attr=len(attrList), trainEmbed=trainEmbed)
-    ag = torch.tensor(alpha_for_graph).float().to(graphs.device)               # :84-85
-    if multi_attr:                                                             # train_multi_attr.py:113,133
-        alpha_target, epsilon = graphs.get_alphas_clamped(alpha_org, ag)
-    else:                                                                      # train.py:86
-        alpha_target, epsilon = ag, graphs.get_alphas(alpha_org, ag)
-    w_new = graphs.get_w_new_tensor(w_global, epsilon, layers=layers)          # :89
-    transformed_output = graphs.get_logits({'z': z_global, 'w': w_new})        # :94
-    feed_dict = {'w': w_new, 'org': out_zs, 'logit': transformed_output, 'alpha': alpha_target}
-    loss = graphs.optimizeParametersAll(feed_dict, trainEmbed=trainEmbed, updateGAN=updateGAN,
-                                        no_content_loss=bool(opt and opt.no_content_loss),
-                                        no_gan_loss=bool(opt and opt.no_gan_loss))
+    loss, out_zs, transformed_output = graphs.eager_step(zs_batch, alpha_for_graph, trainEmbed=trainEmbed, updateGAN=updateGAN, **flags)
     return loss, alpha_for_target, out_zs, transformed_output
 
 
-def _captured_batch(graphs, zs_batch):
-    """Build the hipGraph of the step on first use (the local batch size is static from then on; a ragged last batch runs eagerly)."""
+def _captured_batch(graphs, batch, n_attr, flags):
+    """The batch size of the graph's recorded step, built on first use (the local batch size and the flags are static from then on); None when the
+    graph does not record a step with these flags, or recorded it with others."""
     st = getattr(graphs, '_captured_step', None)
     if st is None:
-        from . import capture
-        o = graphs._captured_opts
-        st = graphs._captured_step = capture.CapturedStep(graphs, zs_batch.shape[0], len(o['attrList']), clamp=o['multi_attr'], layers=o['layers'],
-                                                          no_content_loss=o['no_content_loss'], no_gan_loss=o['no_gan_loss'])
-    return st.z.shape[0]
-
-
-def _captured_z_batch(graphs, zs_batch, alpha_for_graph, opt):
-    """The same for a graph that walks in z (the PGGAN graph's captured_z_step)."""
-    st = getattr(graphs, '_captured_step', None)
-    if st is None:
-        st = graphs._captured_step = graphs.captured_z_step(zs_batch.shape[0], np.asarray(alpha_for_graph).shape[1], no_content_loss=bool(opt.no_content_loss))
-    return st.z.shape[0]
+        st = graphs._captured_step = graphs.captured_step(batch, n_attr, **flags)
+        if st is not None:
+            st.flags = flags
+    return None if st is None or st.flags != flags else st.z.shape[0]
 
 
 def train(graphs, graph_inputs, output_dir, attrList, layers=None, save_freq=100, trainEmbed=False, updateGAN=False,
@@ -143,8 +107,6 @@ def _train(graphs, graph_inputs, output_dir, attrList, layers, save_freq, trainE
         os.makedirs(os.path.join(output_dir, 'results'), exist_ok=True)
         _configure_logging(os.path.join(output_dir, 'log.txt'), append=False)
         logging.info('weight sources: {}'.format(getattr(graphs, 'weight_sources', None)))
-    graphs._captured_opts = dict(attrList=attrList, multi_attr=multi_attr, layers=None if layers is None else [int(l) for l in layers],
-                                 no_content_loss=bool(opt and opt.no_content_loss), no_gan_loss=bool(opt and opt.no_gan_loss))
     n_epoch = (opt.n_epoch if opt is not None and getattr(opt, 'n_epoch', None) else (3 if multi_attr else 10))
     batch_size = constants.BATCH_SIZE
     num_samples = graph_inputs['z'].shape[0]

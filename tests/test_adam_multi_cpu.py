@@ -113,5 +113,5 @@ def test_train_options_accept_hip_graph_with_the_pggan_model(tmp_path):
                                                       '--models_dir', str(tmp_path), '--attrList', 'Smiling', '--attrPath', './dataset/attributes_celeba.txt'])
     assert opt.hip_graph is True and opt.model == 'pggan' and opt.precision == 'f16'
     from latent2im_amd import capture, pggan, trainer
-    assert hasattr(capture, 'CapturedZStep') and hasattr(pggan.TransformGraph, 'captured_z_step')
-    assert callable(pggan.walk_forward_backward) and callable(pggan.walk_update) and callable(trainer._captured_z_batch)
+    assert hasattr(capture, 'CapturedZStep') and hasattr(pggan.TransformGraph, 'captured_step')
+    assert callable(pggan.walk_forward_backward) and callable(pggan.walk_update) and callable(trainer._captured_batch)
