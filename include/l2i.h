@@ -76,7 +76,8 @@ typedef struct l2i_conv_params {
     int32_t accumulate;
     int32_t tile_hint;      /* 0 = auto, else 1..N selects a tile configuration (tuning / tests) */
     const void* w_hi;       /* l2i_conv2d_bf16x3_f32 only: bf16 planes [Cin/16][KH*KW][CoutP][2][8], hi = bf16(w), */
-    const void* w_lo;       /*                              lo = bf16(w - hi); NULL for the fp32 entry points */
+    const void* w_lo;       /*                              lo = bf16(w - hi); NULL for the fp32 entry points, except l2i_conv_transpose2d_f32 with K = 3: */
+                            /*                              fp32 [Cin][25][CoutP], the 25-plane pack of its 25-product kernel (see there), or NULL      */
     float* ws;              /* l2i_conv2d_f32 split-K workspace: ksplit * B*Cout*OHf*OWf floats, or NULL */
     int32_t ksplit;         /* > 1: the input channels are cut into ksplit ranges computed by separate blocks (raw partial sums in ws),
                                then one reduction pass applies the epilogue: for 4x4..16x16 maps, whose whole K = Cin*KH*KW would
@@ -131,6 +132,40 @@ int l2i_conv2d_family(const l2i_conv_params* p);
  * be unset.  Built for (K,pad) in {(3,0),(3,1),(7,3)}; other shapes return L2I_E_UNSUPPORTED (use the per-parity
  * l2i_conv2d_f32 calls). */
 int l2i_conv_transpose2d_f32(const l2i_conv_params* p, void* stream);
+/* K = 3, pad 0 / 1, fp32 maps at least 32 positions wide, Cin % 4 == 0, no split-K: the entry can run the 25-PRODUCT form instead
+ * (convt_poly_kernel, csrc/l2i_convt_poly.hip).  Per dimension the outputs of one parity are a 2-tap filter of the input, those of the other a 1-tap
+ * filter; two adjacent 2-tap outputs are Winograd F(2,2) (3 products for 4), so a 3x3 raw patch x[2W - 1 + pad + {0,1,2}] of window W gives the
+ * 4x4 output patch 4W .. 4W + 3 from 25 products instead of 36, with coefficients 0 / +-1 only.  It reads `w_lo` = fp32 [Cin][25][CoutP] (latent2im_amd/conv.py:pack_weight_convt_poly), plane
+ * 5 a + b = sum_{ky,kx} g[a][ky] g[b][kx] w[co,ci,ky,kx] with the 1-D planes g = (w2, w0 + w2, w0, w1, w1), float64 sums rounded once; `w` stays
+ * the fused pack.  Same fusions, same output sizes, results within fp32 rounding of the direct kernel (not bit-identical).
+ * tile_hint: 0 = per shape: the new kernel where w_lo is set and the shape is in the launcher's measured table (l2i_convt_poly.hip:
+ *                kPolyRules), else the direct kernel with its automatic tile;
+ *            1 / 2 = the direct kernel's 128- / 256-position tile;   9 = the direct kernel, automatic tile (the A/B comparator; so does every
+ *            other value: callers that walk l2i_conv2d_f32's tile numbers 1 .. 8 over both entries keep what they had);
+ *            10 = the new kernel; L2I_E_UNSUPPORTED where it does not take the struct, L2I_E_ARG without w_lo.
+ * Additive (a struct without w_lo runs as before): the ABI version did not move. */
+#define L2I_CONVT_HINT_DIRECT 9
+#define L2I_CONVT_HINT_POLY 10
+/* Host only, no launch: the kernel family l2i_conv_transpose2d_f32 runs `p` on, ASSUMING the pack in w_lo is supplied (callers build that pack on the
+ * first launch that reports L2I_TFAMILY_POLY); -1 for a null struct. */
+#define L2I_TFAMILY_DIRECT 0        /* convt_mfma_kernel */
+#define L2I_TFAMILY_POLY 1          /* convt_poly_kernel: 25 / 36 of the MFMA work */
+#define L2I_TFAMILY_SMALL 2         /* convt_small_kernel: <= 3 output channels, VALU */
+int l2i_conv_transpose2d_family(const l2i_conv_params* p);
+/* Host only: the launch plan convt_poly_kernel would run `p` with (tests check its tiles, windows, halo and DMA slot ranges without a GPU).
+ * eligible = 0 (and the reason in l2i_last_error) where the kernel does not take the struct; returns L2I_E_ARG for a null argument only.
+ * Block tile = 16 output channels x WTH x WTW windows (<= 64); window (wy, wx) reads the raw rows 2 wy + org .. + 2 (columns alike) and owns the
+ * outputs 4 wy .. 4 wy + 3; the raw tile of a block is IH x IW = (2 WTH + 1) x (2 WTW + 1) values per input channel, staged as nslots DMA slots of
+ * 64 values at an LDS pitch of `plane` floats; CK input channels per stage (CK divides Cin), two stages of stage_floats floats. */
+typedef struct l2i_convt_poly_plan {
+    int32_t eligible, masked;
+    int32_t nwx, nwy;           /* windows across / down the output: ceil(OWf / 4), ceil(OHf / 4) */
+    int32_t WTW, WTH, tiles_x, tiles_y, mblocks;
+    int32_t total, grid;        /* blocks with work = B * tiles_y * tiles_x * mblocks; the launch's grid (rounded up to 8) */
+    int32_t IH, IW, org, nslots, plane, wpitch;
+    int32_t CK, stage_floats, lds_bytes;
+} l2i_convt_poly_plan;
+int l2i_convt_poly_plan_for(const l2i_conv_params* p, l2i_convt_poly_plan* plan);
 
 /* Split-precision variant of l2i_conv2d_f32 (BASELINE config 5's "16-bit MFMA" path; latent2im_amd.conv.PRECISION = 'bf16x3' selects
  * it): operands are split x = bf16(x) + bf16(x - bf16(x)) and a*b is evaluated as ah*bh + ah*bl + al*bh on v_mfma_f32_32x32x16_bf16

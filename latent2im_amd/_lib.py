@@ -58,6 +58,21 @@ class SegmvSeg(ctypes.Structure):
                 ('e_off_c', c_i), ('e_off_b', c_i), ('e_bstride', c_i), ('rgb_off_b', c_i), ('rgb_w_off', c_i), ('part', SegmvPart * 2)]
 
 
+# l2i_conv_transpose2d_f32, K = 3 (include/l2i.h): tile_hint 0 = per shape (the 25-product kernel convt_poly_kernel on the shapes of its measured table
+# where ConvParams.w_lo carries its fp32 pack [Cin][25][CoutP] = conv.pack_weight_convt_poly, else the direct kernel); 1 / 2 = the direct kernel's two
+# tiles; CONVT_HINT_DIRECT = the direct kernel's automatic tile (as every other value); CONVT_HINT_POLY = the new kernel, L2I_E_UNSUPPORTED where it
+# does not take the struct.  l2i_conv_transpose2d_family (host only) says which of TFAMILY_* a struct runs on, assuming the pack is supplied;
+# l2i_convt_poly_plan_for (host only) fills ConvtPolyPlan, the new kernel's launch plan.
+CONVT_HINT_DIRECT, CONVT_HINT_POLY = 9, 10     # L2I_CONVT_HINT_*
+TFAMILY_DIRECT, TFAMILY_POLY, TFAMILY_SMALL = 0, 1, 2      # L2I_TFAMILY_*: l2i_conv_transpose2d_family
+
+
+class ConvtPolyPlan(ctypes.Structure):
+    """Mirror of ``struct l2i_convt_poly_plan`` (include/l2i.h): the launch plan of convt_poly_kernel, a host-side function of the struct."""
+    _fields_ = [(n, c_i) for n in ('eligible', 'masked', 'nwx', 'nwy', 'WTW', 'WTH', 'tiles_x', 'tiles_y', 'mblocks', 'total', 'grid',
+                                   'IH', 'IW', 'org', 'nslots', 'plane', 'wpitch', 'CK', 'stage_floats', 'lds_bytes')]
+
+
 ADAM_MAX_TENSORS = 16     # L2I_ADAM_MAX_TENSORS
 
 
@@ -70,6 +85,8 @@ _SIGNATURES = {
     'l2i_conv2d_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_family': (c_i, [ctypes.POINTER(ConvParams)]),
     'l2i_conv_transpose2d_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
+    'l2i_conv_transpose2d_family': (c_i, [ctypes.POINTER(ConvParams)]),
+    'l2i_convt_poly_plan_for': (c_i, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvtPolyPlan)]),
     'l2i_conv2d_bf16x3_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv_transpose2d_bf16x3_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_wino_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
@@ -149,6 +166,9 @@ for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
     _SIGNATURES[_n + '_f16'] = _SIGNATURES[_n]
 
 ABI_VERSION = 12         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
+# Entry points added without an ABI bump: a library of the same ABI version built before them (L2I_LIB = a parent build, for A/B runs) still loads;
+# has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
+ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for'))
 
 EXPORTS = tuple(_SIGNATURES)
 
@@ -207,6 +227,8 @@ def load():
                            'there is no CPU fallback for the hot path' % LIB_PATH)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGNATURES.items():
+            if name in ADDITIVE and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)           # AttributeError if the export is absent
             fn.restype = res
             fn.argtypes = args
@@ -217,6 +239,11 @@ def load():
                                                                     ctypes.sizeof(ConvParams)))
         _lib = lib
     return _lib
+
+
+def has(name):
+    """Whether the loaded library exports ``name`` (one of ADDITIVE; everything else is always there)."""
+    return hasattr(load(), name)
 
 
 def check(rc, what):

@@ -44,6 +44,7 @@ FAMILY_INFO = {
     'implicit_gemm_f32': ('conv_mfma_kernel / conv3x3s2_dma_kernel', 1.0, 157.3),
     'gemm1x1_f32': ('gemm1x1_kernel', 1.0, 157.3),
     'transposed_f32': ('convt_mfma_kernel', 1.0, 157.3),
+    'transposed_poly_f32': ('convt_poly_kernel', 25.0 / 36.0, 157.3),
     'cin3_f32': ('conv_cin3_kernel', 28.0 / 27.0, 157.3),
     'direct_small_valu': ('conv_direct_small_kernel', 1.0, 157.3),
     'implicit_gemm_bf16x3': ('conv_bf16x3_pipe_kernel', 3.0, 2500.0),
@@ -118,6 +119,25 @@ def pack_weight_wino4(w):
     a = U[..., :4].reshape(cin // 4, coutp // 16, -1)
     b = U[..., 4:].reshape(cin // 4, coutp // 16, -1)
     return torch.cat([a, b], dim=2).float().contiguous()
+
+
+_POLY_G = np.array([[0, 0, 1], [1, 0, 1], [1, 0, 0], [0, 1, 0], [0, 1, 0]], dtype=np.float64)      # 1-D planes (w2, w0 + w2, w0, w1, w1)
+
+
+def pack_weight_convt_poly(w, dtype=torch.float32):
+    """[Cout, Cin, 3, 3] (correlation form of a stride-2 transposed conv, pad 0 or 1) -> the 25 weight planes of csrc/l2i_convt_poly.hip,
+    [Cin, 25, CoutP]: plane 5 a + b = sum_{ky,kx} g[a][ky] g[b][kx] w[ky, kx] with the 1-D planes g = (w2, w0 + w2, w0, w1, w1) — sums of at most
+    four taps, formed in float64 and rounded once to ``dtype``.  (Planes with a == 4 or b == 4 repeat a == 3 / b == 3: the kernel stages the 16
+    distinct ones.)"""
+    w = torch.as_tensor(w, dtype=torch.float64)
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    G = torch.as_tensor(_POLY_G, device=w.device)
+    U = torch.einsum('ik,ockl,jl->ocij', G, w, G)                 # [Cout, Cin, 5, 5]
+    coutp = (cout + 31) // 32 * 32
+    p = torch.zeros(cin, 25, coutp, dtype=dtype, device=w.device)
+    p[:, :, :cout] = U.permute(1, 2, 3, 0).reshape(cin, 25, cout).to(dtype)
+    return p.contiguous()
 
 
 def _bf16x3_planes(self):
@@ -239,8 +259,11 @@ def fused_transposed_taps(K, pad):
 
 class FusedTransposed:
     """One-launch stride-2 transposed conv (l2i_conv_transpose2d_f32): weights packed in the kernel's tap order; for the split-precision
-    path (l2i_conv_transpose2d_bf16x3_f32) the bf16 planes of the plain [Cout, Cin, 3, 3] weight, built on first use."""
-    __slots__ = ('w', 'cin', 'cout', 'k', 'pad', 'w_src', 'w16')
+    path (l2i_conv_transpose2d_bf16x3_f32) the bf16 planes of the plain [Cout, Cin, 3, 3] weight, built on first use; for the 25-product kernel
+    (csrc/l2i_convt_poly.hip) its 25-plane pack, built on the first launch that kernel takes.  That pack is only ever built for a weight handed
+    over on the HOST — a frozen net, packed once.  A net that is being trained hands over a CUDA weight and builds a new FusedTransposed every
+    step (FrozenConv2d): it keeps no ``poly_src`` and stays on the direct kernel instead of repacking 25 planes per step."""
+    __slots__ = ('w', 'cin', 'cout', 'k', 'pad', 'w_src', 'w16', 'poly_src', 'poly')
 
     def __init__(self, w_oihw, pad):
         w = torch.as_tensor(w_oihw, dtype=torch.float32)
@@ -251,11 +274,20 @@ class FusedTransposed:
         self.w = pack_weight(sel.reshape(self.cout, self.cin, self.k * self.k, 1))
         self.w_src = w if (self.k == 3 and pad in (0, 1) and self.cin % 16 == 0) else None
         self.w16 = None
+        self.poly_src = w if (self.k == 3 and pad in (0, 1) and self.cin % 4 == 0 and not w.is_cuda) else None
+        self.poly = None
 
     bf16x3_planes = _bf16x3_planes
 
+    def poly_pack(self):
+        if self.poly is None and self.poly_src is not None:
+            self.poly = pack_weight_convt_poly(self.poly_src).to(self.w.device)
+        return self.poly
+
     def to(self, device):
         self.w = self.w.to(device)
+        if self.poly is not None:
+            self.poly = self.poly.to(device)
         return self
 
 
@@ -421,6 +453,10 @@ def run_fused_transposed(F, x, y, in_scale=None, in_mask=None, mask=(1.0, 0.0), 
         planes = F.bf16x3_planes()
         p.w_hi, p.w_lo = _lib.ptr(planes[0]), _lib.ptr(planes[1])
         name, family = 'l2i_conv_transpose2d_bf16x3_f32', 'transposed_bf16x3'
+    elif (F.poly_src is not None and tile_hint in (0, _lib.CONVT_HINT_POLY) and _lib.has('l2i_conv_transpose2d_family')
+          and _lib.load().l2i_conv_transpose2d_family(p) == _lib.TFAMILY_POLY):
+        p.w_lo = _lib.fptr(F.poly_pack())                   # the 25-product kernel (no split-K): its pack is built on the first such launch
+        family = 'transposed_poly_f32'
     else:
         _split_k(p, B * H * W, cin, y)
     _launch(name, (p,), None, _transposed_meta, p, family)

@@ -575,6 +575,9 @@ extern "C" int l2i_conv_transpose2d_f32(const l2i_conv_params* pp, void* stream)
     if ((((uintptr_t)p.w) % 16) != 0) return l2i_set_error(L2I_E_ARG, "conv_transpose2d: packed weights must be 16-byte aligned");
     if ((size_t)p.Cin * p.KH * p.KW * p.CoutP * sizeof(float) >= 0xFFFFFFF0ull) return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d: weight pack >= 4 GiB");
     hipStream_t st = (hipStream_t)stream;
+    // the 25-product kernel (l2i_convt_poly.hip): forced by its hint, or on the shapes of its measured table where the caller supplied its pack
+    if (p.tile_hint == L2I_CONVT_HINT_POLY) return l2i_launch_convt_poly(p, st);
+    if (p.tile_hint == 0 && p.w_lo && l2i_convt_poly_preferred(p)) return l2i_launch_convt_poly(p, st);
     // 128 positions per block (three blocks per CU) on maps up to 33 positions wide, where 256-position tiles leave a CU with one
     // or two blocks for most of the launch; 256 positions (two per CU, half the weight traffic per MFMA) above.  tile_hint 1 / 2 force.
     const bool narrow = p.tile_hint == 1 || (p.tile_hint != 2 && ((p.OWf + 1) / 2 <= 33 || p.W <= 33));     // (outputs may be up to 8 larger than natural)
@@ -584,3 +587,11 @@ extern "C" int l2i_conv_transpose2d_f32(const l2i_conv_params* pp, void* stream)
     return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d: fused kernel built for (K,pad) in {(3,0),(3,1),(7,3)}");
 }
 
+
+extern "C" int l2i_conv_transpose2d_family(const l2i_conv_params* pp) {
+    if (!pp) return -1;
+    const l2i_conv_params& p = *pp;
+    if (p.CoutP == 4 && p.Cout <= 3) return L2I_TFAMILY_SMALL;
+    if (p.tile_hint == L2I_CONVT_HINT_POLY) return l2i_convt_poly_eligible(p) ? L2I_TFAMILY_POLY : L2I_TFAMILY_DIRECT;
+    return (p.tile_hint == 0 && l2i_convt_poly_preferred(p)) ? L2I_TFAMILY_POLY : L2I_TFAMILY_DIRECT;
+}

@@ -16,6 +16,9 @@ bool l2i_convt_small_eligible(const l2i_conv_params& p);          // l2i_convt_s
 int l2i_launch_convt_small(const l2i_conv_params& p, hipStream_t st);
 bool l2i_conv3x3s2_eligible(const l2i_conv_params& p);            // l2i_conv_s2.hip: unmasked 3x3 stride-2 layers on maps >= 32 wide, both operands by LDS-DMA
 int l2i_launch_conv3x3s2(const l2i_conv_params& p, hipStream_t st);
+bool l2i_convt_poly_eligible(const l2i_conv_params& p);           // l2i_convt_poly.hip: 25-product form of the 3x3 stride-2 transposed conv (reads p.w_lo)
+bool l2i_convt_poly_preferred(const l2i_conv_params& p);          //   eligible and in the measured table of shapes it wins on (tile_hint 0)
+int l2i_launch_convt_poly(const l2i_conv_params& p, hipStream_t st);
 int l2i_launch_splitk_epilogue(const l2i_conv_params& q, hipStream_t st);     // l2i_conv.hip: y = epilogue(sum of q.ksplit partials in q.ws)
 
 // [r5] The ABI-5 fields of l2i_conv_params belong to single entry points (rgb_*: l2i_conv2d_h8; pool_*: l2i_conv2d_wino4_f32; in_h8: the 7x7 kernel inside
