@@ -213,11 +213,30 @@ int l2i_wino4s_epilogue_class(const l2i_conv_params* p);
  *   x, y, residual, res_mask, out_mask, res_sub, sq_ref -> bf16 h8 tensors (fp32 NCHW for y and the epilogue operands when out_f32 = 1);
  *   w_hi -> bf16 weight planes [Cin/16][KH*KW][2][CoutP][8] (latent2im_amd/conv.py:pack_weight_bf16x3, hi plane), per sample when w_bstride != 0;
  *   noise [B,1,OHf,OWf], bias [Cout], out_scale [B,Cout] fp32; `w`, `w_lo` ignored; no prologue fusions (scales live in the weights, masks in
- *   the producing epilogue): in_scale must be NULL, in_mask NULL or == x with mask (1, 0) (ReLU-on-load, 3x3 stride-1 layers); the output
- *   mask is leaky here: * (out_mask > 0 ? mask_pos : mask_neg).  h8 output needs Cout % 8 == 0.
+ *   the producing epilogue): in_scale must be NULL, in_mask NULL or == x with mask (1, 0) (ReLU-on-load, 3x3 stride-1 layers); with the h8
+ *   output the output mask is leaky: * (out_mask > 0 ? mask_pos : mask_neg) (res_mask stays binary).  With out_f32 = 1 the epilogue is the fp32
+ *   kernels' own, whose masks are binary: an out_mask with (mask_pos, mask_neg) != (1, 0) returns L2I_E_UNSUPPORTED.  h8 output needs Cout % 8 == 0.
  * l2i_conv_transpose2d_h8: stride-2 transposed 3x3 conv (pad 0 / 1), all four output parities per launch, h8 in and out. */
 int l2i_conv2d_h8(const l2i_conv_params* p, void* stream);
 int l2i_conv_transpose2d_h8(const l2i_conv_params* p, void* stream);
+/* Host only, no launch: the plan l2i_conv2d_h8 (transposed = 0) / l2i_conv_transpose2d_h8 (transposed != 0) and their _f16 twins run `p` with — the
+ * entry points take it from the same function.  eligible = 0 (every other field 0, the reason in l2i_last_error) where the entry refuses the struct;
+ * returns L2I_E_ARG for a null argument only.  The instantiation of conv_h8_kernel: a block of 32 WM output channels x 4 WN rows x 32 columns (per
+ * input position and four outputs each when TR != 0), K x K taps at stride S, KS 16-channel MFMA steps per chunk, relu_in = ReLU-on-load, out32 =
+ * fp32 NCHW output, extra = the instantiation that carries the lean epilogue's optional outputs (rgb_w, sq_ref).  epilogue: which of the four the
+ * launch takes.  total = B * tiles_y * tiles_x * mblocks blocks with work, grid = total rounded up to 8.  Additive: the ABI version did not move. */
+#define L2I_H8_EPI_LEAN 0           /* h8 output, per-channel vectors and noise only, max(v gpos, v gneg): needs 0 <= gneg <= gpos */
+#define L2I_H8_EPI_GENERAL 1        /* h8 output, every operand (H8Out::finish) */
+#define L2I_H8_EPI_F32_VEC 2        /* fp32 output, the shared fp32 epilogue with 16-byte accesses */
+#define L2I_H8_EPI_F32_SCALAR 3     /* fp32 output, the shared fp32 epilogue element by element */
+typedef struct l2i_conv_h8_plan {
+    int32_t eligible;
+    int32_t WM, WN, KS, K, S, TR;   /* TR: 0 = correlation, 1 / 2 = transposed with pad 0 / 1 */
+    int32_t out32, relu_in, extra, rgb;
+    int32_t epilogue;               /* L2I_H8_EPI_* */
+    int32_t nchunks, tiles_x, tiles_y, mblocks, total, grid, lds_bytes;
+} l2i_conv_h8_plan;
+int l2i_conv_h8_plan_for(const l2i_conv_params* p, int transposed, l2i_conv_h8_plan* plan);
 
 /* [ABI 7] Two chained 1x1 stride-1 convolutions on h8 maps in one launch (csrc/l2i_pair_h8.hip): `first` (Cin1 -> Cout1, with its bias / residual /
  * ReLU / sign-plane masks / sign-plane output, y = the wide map, written) feeds `second` (Cout1 -> Cout2 <= 256, bias / ReLU / sign-plane mask / sign-plane

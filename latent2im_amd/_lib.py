@@ -73,6 +73,23 @@ class ConvtPolyPlan(ctypes.Structure):
                                    'IH', 'IW', 'org', 'nslots', 'plane', 'wpitch', 'CK', 'stage_floats', 'lds_bytes')]
 
 
+H8_EPI_LEAN, H8_EPI_GENERAL, H8_EPI_F32_VEC, H8_EPI_F32_SCALAR = 0, 1, 2, 3      # L2I_H8_EPI_*: l2i_conv_h8_plan.epilogue
+
+
+class ConvH8Plan(ctypes.Structure):
+    """Mirror of ``struct l2i_conv_h8_plan`` (include/l2i.h): the instantiation, epilogue and grid l2i_conv2d_h8 / l2i_conv_transpose2d_h8 run a
+    struct with, a host-side function of the struct (l2i_conv_h8_plan_for)."""
+    _fields_ = [(n, c_i) for n in ('eligible', 'WM', 'WN', 'KS', 'K', 'S', 'TR', 'out32', 'relu_in', 'extra', 'rgb', 'epilogue', 'nchunks', 'tiles_x',
+                                   'tiles_y', 'mblocks', 'total', 'grid', 'lds_bytes')]
+
+
+def conv_h8_plan(p, transposed=False):
+    """The ConvH8Plan of ConvParams ``p`` (no launch, no GPU); plan.eligible == 0 where the entry refuses the struct."""
+    plan = ConvH8Plan()
+    check(load().l2i_conv_h8_plan_for(ctypes.byref(p), int(bool(transposed)), ctypes.byref(plan)), 'l2i_conv_h8_plan_for')
+    return plan
+
+
 ADAM_MAX_TENSORS = 16     # L2I_ADAM_MAX_TENSORS
 
 
@@ -95,6 +112,7 @@ _SIGNATURES = {
     'l2i_conv1x1_pair_f32': (c_i, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_h8': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv_transpose2d_h8': (c_i, [ctypes.POINTER(ConvParams), c_p]),
+    'l2i_conv_h8_plan_for': (c_i, [ctypes.POINTER(ConvParams), c_i, ctypes.POINTER(ConvH8Plan)]),
     'l2i_conv_img_h8': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv1x1_pair_h8': (c_i, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams), c_i, c_p]),
     'l2i_conv_chain3_h8': (c_i, [ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams), ctypes.POINTER(ConvParams), c_i, c_p]),
@@ -168,7 +186,7 @@ for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
 ABI_VERSION = 12         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 # Entry points added without an ABI bump: a library of the same ABI version built before them (L2I_LIB = a parent build, for A/B runs) still loads;
 # has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
-ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for'))
+ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for'))
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -700,11 +700,12 @@ class ImgConvH8:
     def out_hw(self, h, w):
         return (h + 2 * self.padding - self.k) // self.stride + 1, (w + 2 * self.padding - self.k) // self.stride + 1
 
-    def forward(self, x, bias=None, act=ACT_NONE, slope=0.2, gain=1.0, out_gain=1.0, sq=None):
+    def forward(self, x, bias=None, act=ACT_NONE, slope=0.2, gain=1.0, out_gain=1.0, sq=None, out=None):
         B, cin, H, W = x.shape
         assert cin == self.cin and x.dtype == torch.float32
         oh, ow = self.out_hw(H, W)
-        y = torch.empty(B, self.cout // 8, oh, ow, 8, device=x.device, dtype=self.dtype)
+        y = torch.empty(B, self.cout // 8, oh, ow, 8, device=x.device, dtype=self.dtype) if out is None else out
+        assert tuple(y.shape) == (B, self.cout // 8, oh, ow, 8) and y.dtype == self.dtype
         p = _conv_params(x, self.planes, y, B, cin, H, W, self.cout, self.k, self.k, self.stride, self.padding, self.padding, oh, ow, oh, ow, bias=bias,
                          act=act, slope=slope, gain=gain, out_gain=out_gain, sq=sq)
         _launch('l2i_conv_img_h8', (p,), self.dtype, _conv_meta, p, 'conv_h8')

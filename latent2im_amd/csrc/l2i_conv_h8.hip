@@ -536,39 +536,68 @@ __global__ __launch_bounds__(256, ((KS == 1 || K == 1) && TR == 0) ? (EXTRA ? 3 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-template <int WM, int WN, int K, int S, int TR, bool OUT32, bool RELU_IN = false, int KS = 2>
-static int launch_h8(const l2i_conv_params& p, hipStream_t st) {
-    using G = g8::Geo<WN, K, S, TR, KS>;
+// One instantiation of conv_h8_kernel, as a type: h8_select picks it, h8_plan_inst prices it, launch_h8 launches it.
+template <int WM_, int WN_, int K_, int S_, int TR_, bool OUT32_, bool RELU_IN_ = false, int KS_ = 2> struct H8Inst {
+    static constexpr int WM = WM_, WN = WN_, K = K_, S = S_, TR = TR_, KS = KS_;
+    static constexpr bool OUT32 = OUT32_, RELU_IN = RELU_IN_;
+};
+
+// The launch plan of instantiation I for `p` (host only): everything the launcher decides besides the instantiation itself — the grid, the LDS and
+// which epilogue the launch takes.  l2i_conv_h8_plan_for reports it, launch_h8 launches from it: one decision, two users.
+template <class I>
+static int h8_plan_inst(const l2i_conv_params& p, l2i_conv_h8_plan& P) {
+    constexpr int WM = I::WM, K = I::K, S = I::S, TR = I::TR;
+    constexpr bool OUT32 = I::OUT32;
+    using G = g8::Geo<I::WN, K, S, TR, I::KS>;
     constexpr int BM = WM * 32;
     constexpr int WSLOTS = K * G::KS * 2 * BM;
     constexpr bool CAN_EXTRA = (K == 3 && S == 1 && TR == 0 && !OUT32);       // the instantiations that exist with the lean epilogue's optional outputs
-    H8Launch L;
-    L.tiles_x = (p.OW + 31) / 32;
-    L.tiles_y = (p.OH + G::TH - 1) / G::TH;
-    L.mblocks = (p.CoutP + BM - 1) / BM;
-    const long total = (long)p.B * L.tiles_y * L.tiles_x * L.mblocks;
+    P.WM = WM; P.WN = I::WN; P.KS = G::KS; P.K = K; P.S = S; P.TR = TR; P.out32 = OUT32 ? 1 : 0; P.relu_in = I::RELU_IN ? 1 : 0;
+    P.tiles_x = (p.OW + 31) / 32;
+    P.tiles_y = (p.OH + G::TH - 1) / G::TH;
+    P.mblocks = (p.CoutP + BM - 1) / BM;
+    const long total = (long)p.B * P.tiles_y * P.tiles_x * P.mblocks;
     if (total <= 0 || total > 0x7ffffff0L) return l2i_set_error(L2I_E_ARG, "conv2d_h8: grid too large");
-    L.total = (int)total;
-    L.nchunks = p.Cin / G::CK;
-    L.vec_epi = (OUT32 && l2i_epilogue_vec_ok(p)) ? 1 : 0;
+    P.total = (int)total;
+    P.nchunks = p.Cin / G::CK;
+    const bool vec = OUT32 && l2i_epilogue_vec_ok(p);
     // identity / ReLU / leaky ReLU as max(g * gpos, g * gneg) needs 0 <= gneg <= gpos
     const bool gains_ok = p.out_gain > 0.f && (p.act != L2I_ACT_LRELU || (p.act_gain > 0.f && p.act_slope >= 0.f && p.act_slope <= 1.f));
     bool lean = !OUT32 && !p.out_mask && !p.residual && !p.accumulate && gains_ok && (size_t)p.OHf * p.OWf < 0xFFFFFFFFull;
     if (p.sq_ref && !CAN_EXTRA) lean = false;              // the ContentLoss sum rides on the lean epilogue of the EXTRA instantiations only; elsewhere: the general epilogue
-    L.lean_epi = lean ? 1 : 0;
+    P.epilogue = OUT32 ? (vec ? L2I_H8_EPI_F32_VEC : L2I_H8_EPI_F32_SCALAR) : (lean ? L2I_H8_EPI_LEAN : L2I_H8_EPI_GENERAL);
     const bool extra = CAN_EXTRA && lean && (p.rgb_w || p.sq_ref);
-    L.rgb = p.rgb_w ? 1 : 0;
+    P.extra = extra ? 1 : 0;
+    P.rgb = p.rgb_w ? 1 : 0;
     // (Cout % 32: the epilogue fetches the eight rgb_w values of EVERY channel group of the block's 32- / 64-channel tile before it masks the groups
     //  past Cout — with Cout = 40 or 48 those loads would run past the sample's row, and past the buffer for the last sample; the generator's layers
     //  have 32 and 64 channels)
-    if (L.rgb && !(extra && L.mblocks == 1 && p.rgb_bias && p.rgb_out && (p.Cout % 32) == 0 && (((uintptr_t)p.rgb_w) % 16) == 0))
+    if (P.rgb && !(extra && P.mblocks == 1 &&p.rgb_bias && p.rgb_out && (p.Cout % 32) == 0 && (((uintptr_t)p.rgb_w) % 16) == 0))
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: rgb_w needs a 3x3 stride-1 launch on the lean h8 epilogue (no per-pixel operand maps), every output channel in one block (Cout = 32 or 64), rgb_bias / rgb_out, a 16-byte aligned rgb_w");
     size_t lds = (size_t)(2 * G::IN_STAGE + 2 * WSLOTS) * 16;
     if (OUT32 && lds < 4 * 32 * 64 * sizeof(float)) lds = 4 * 32 * 64 * sizeof(float);
     if (lds > 160 * 1024) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: tile does not fit the LDS");
-    const unsigned grid = (unsigned)((total + 7) & ~7L);
+    P.lds_bytes = (int)lds;
+    P.grid = (int)((total + 7) & ~7L);
+    return L2I_OK;
+}
+
+template <class I>
+static int launch_h8(const l2i_conv_params& p, hipStream_t st) {
+    constexpr int WM = I::WM, WN = I::WN, K = I::K, S = I::S, TR = I::TR, KS = I::KS;
+    constexpr bool OUT32 = I::OUT32, RELU_IN = I::RELU_IN;
+    constexpr bool CAN_EXTRA = (K == 3 && S == 1 && TR == 0 && !OUT32);
+    l2i_conv_h8_plan P = {};
+    if (int rc = h8_plan_inst<I>(p, P)) return rc;
+    H8Launch L;
+    L.tiles_x = P.tiles_x; L.tiles_y = P.tiles_y; L.mblocks = P.mblocks; L.total = P.total; L.nchunks = P.nchunks;
+    L.vec_epi = P.epilogue == L2I_H8_EPI_F32_VEC ? 1 : 0;
+    L.lean_epi = P.epilogue == L2I_H8_EPI_LEAN ? 1 : 0;
+    L.rgb = P.rgb;
+    const size_t lds = (size_t)P.lds_bytes;
+    const unsigned grid = (unsigned)P.grid;
     if constexpr (CAN_EXTRA) {
-        if (extra) {
+        if (P.extra) {
             L2I_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_h8_kernel<WM, WN, K, S, TR, OUT32, RELU_IN, KS, true>),
                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             hipLaunchKernelGGL((conv_h8_kernel<WM, WN, K, S, TR, OUT32, RELU_IN, KS, true>), dim3(grid), dim3(256), lds, st, p, L);
@@ -606,16 +635,27 @@ static int h8_common_checks(const l2i_conv_params& p, const char* who) {
     return L2I_OK;
 }
 
-extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
-    if (!pp) return l2i_set_error(L2I_E_ARG, "conv2d_h8: null params");
-    const l2i_conv_params& p = *pp;
+// The struct's checks and the choice of the instantiation, for both entry points (transposed = l2i_conv_transpose2d_h8): `f` is called with the
+// chosen H8Inst and its result returned; a struct the entry does not take returns its error code without calling `f`.
+template <class F>
+static int h8_select(const l2i_conv_params& p, bool transposed, F&& f) {
+    if (transposed) {
+        if (int rc = h8_common_checks(p, "conv_transpose2d_h8")) return rc;
+        const int nat = (p.H - 1) * 2 - 2 * p.pad_y + 3, natw = (p.W - 1) * 2 - 2 * p.pad_x + 3;
+        if ((p.Cin % 32) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d_h8: Cin must be a multiple of 32");
+        if (p.KH != 3 || p.KW != 3 || p.stride != 2 || p.pad_y != p.pad_x || p.pad_x < 0 || p.pad_x > 1 || p.OHf < nat || p.OHf > nat + 8 || p.OWf < natw || p.OWf > natw + 8 ||
+            p.OH != (p.OHf + 1) / 2 || p.OW != (p.OWf + 1) / 2 || p.out_f32 || (p.Cout % 8) != 0 || p.sq_ref || p.in_mask)
+            return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d_h8: 3x3 stride-2 layer (pad 0 or 1), natural output size (or up to 8 larger), h8 output");
+        const bool wide = (p.CoutP % 64) == 0;
+        if (p.pad_x == 0) return wide ? f(H8Inst<2, 1, 3, 1, 1, false>()) : f(H8Inst<1, 2, 3, 1, 1, false>());
+        return wide ? f(H8Inst<2, 1, 3, 1, 2, false>()) : f(H8Inst<1, 2, 3, 1, 2, false>());
+    }
     if (int rc = h8_common_checks(p, "conv2d_h8")) return rc;
     const bool k1 = (p.KH == 1 && p.KW == 1 && p.pad_y == 0 && p.pad_x == 0);
     const bool k3 = (p.KH == 3 && p.KW == 3 && p.pad_y == p.pad_x && p.pad_x >= 0 && p.pad_x <= 1);
     if (!(k1 || k3) || (p.stride != 1 && p.stride != 2) || p.oy_step != 1 || p.ox_step != 1)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: 1x1 (pad 0) or 3x3 (pad 0 / 1) layers, stride 1 or 2, dense output window");
     if (p.oy_off < 0 || p.ox_off < 0 || p.OH + p.oy_off > p.OHf || p.OW + p.ox_off > p.OWf) return l2i_set_error(L2I_E_ARG, "conv2d_h8: output window exceeds the output tensor");
-    hipStream_t st = (hipStream_t)stream;
     bool wide = (p.CoutP % 64) == 0;
     {   // [r5] small maps: with 64-channel blocks a launch of a <= 32^2 map has fewer blocks than the chip has CUs and every block walks its 48 - 96
         // phases alone on its CU (1 wave per SIMD: every barrier and DMA wait exposed); 32-channel blocks double the blocks
@@ -626,9 +666,12 @@ extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
     if (p.out_f32) {                                       // fp32 NCHW output (gradients landing on images, the last layer in front of an fp32 consumer)
         if (p.in_mask) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: ReLU-on-load needs the h8 output");
         if (p.sq_ref) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: sq_ref needs the h8 output");
+        // the fp32 epilogue is the fp32 kernels' own (l2i_epilogue.h), whose masks are binary by its contract: a leaky mask would be ignored there
+        if (p.out_mask && !(p.mask_pos == 1.f && p.mask_neg == 0.f))
+            return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: the fp32 output's out_mask is binary, (mask_pos, mask_neg) = (1, 0); a leaky mask needs the h8 output");
         if ((p.Cin % 32) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: fp32 output needs Cin % 32 == 0");
-        if (p.KH == 3 && p.stride == 1) return wide ? launch_h8<2, 2, 3, 1, 0, true>(p, st) : launch_h8<1, 2, 3, 1, 0, true>(p, st);
-        if (p.KH == 1 && p.stride == 1) return wide ? launch_h8<2, 2, 1, 1, 0, true>(p, st) : launch_h8<1, 2, 1, 1, 0, true>(p, st);
+        if (p.KH == 3 && p.stride == 1) return wide ? f(H8Inst<2, 2, 3, 1, 0, true>()) : f(H8Inst<1, 2, 3, 1, 0, true>());
+        if (p.KH == 1 && p.stride == 1) return wide ? f(H8Inst<2, 2, 1, 1, 0, true>()) : f(H8Inst<1, 2, 1, 1, 0, true>());
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: fp32 output is built for stride-1 layers");
     }
     if ((p.Cout % 8) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: h8 output needs Cout % 8 == 0");
@@ -638,32 +681,40 @@ extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
     const bool ks1 = (p.Cin % 32) != 0 || p.Cin <= 256 || p.OW > 32;    // measured per shape (tools/probes/h8_bench.py): 16 wins everywhere but 512 channels on <= 32^2 maps
     if (p.in_mask) {                                       // ReLU-on-load: the 3x3 stride-1 layers of VGG-19
         if (p.KH == 3 && p.stride == 1) {
-            if (ks1) return wide ? launch_h8<2, 2, 3, 1, 0, false, true, 1>(p, st) : launch_h8<1, 2, 3, 1, 0, false, true, 1>(p, st);
-            return wide ? launch_h8<2, 2, 3, 1, 0, false, true>(p, st) : launch_h8<1, 2, 3, 1, 0, false, true>(p, st);
+            if (ks1) return wide ? f(H8Inst<2, 2, 3, 1, 0, false, true, 1>()) : f(H8Inst<1, 2, 3, 1, 0, false, true, 1>());
+            return wide ? f(H8Inst<2, 2, 3, 1, 0, false, true>()) : f(H8Inst<1, 2, 3, 1, 0, false, true>());
         }
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: ReLU-on-load is built for 3x3 stride-1 layers");
     }
-    if (p.KH == 3 && p.stride == 1 && ks1) return wide ? launch_h8<2, 2, 3, 1, 0, false, false, 1>(p, st) : launch_h8<1, 2, 3, 1, 0, false, false, 1>(p, st);
+    if (p.KH == 3 && p.stride == 1 && ks1) return wide ? f(H8Inst<2, 2, 3, 1, 0, false, false, 1>()) : f(H8Inst<1, 2, 3, 1, 0, false, false, 1>());
     if ((p.Cin % 32) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_h8: Cin % 32 == 0 except for 3x3 stride-1 layers (Cin % 16 == 0)");
-    if (p.KH == 3 && p.stride == 1) return wide ? launch_h8<2, 2, 3, 1, 0, false>(p, st) : launch_h8<1, 2, 3, 1, 0, false>(p, st);
-    if (p.KH == 1 && p.stride == 1) return wide ? launch_h8<2, 2, 1, 1, 0, false>(p, st) : launch_h8<1, 2, 1, 1, 0, false>(p, st);
+    if (p.KH == 3 && p.stride == 1) return wide ? f(H8Inst<2, 2, 3, 1, 0, false>()) : f(H8Inst<1, 2, 3, 1, 0, false>());
+    if (p.KH == 1 && p.stride == 1) return wide ? f(H8Inst<2, 2, 1, 1, 0, false>()) : f(H8Inst<1, 2, 1, 1, 0, false>());
     // 16-channel chunks: the 9 x 65-slot tile of a 32-channel chunk leaves one block per CU
-    if (p.KH == 3 && p.stride == 2) return wide ? launch_h8<2, 1, 3, 2, 0, false, false, 1>(p, st) : launch_h8<1, 1, 3, 2, 0, false, false, 1>(p, st);
-    return wide ? launch_h8<2, 2, 1, 2, 0, false>(p, st) : launch_h8<1, 2, 1, 2, 0, false>(p, st);
+    if (p.KH == 3 && p.stride == 2) return wide ? f(H8Inst<2, 1, 3, 2, 0, false, false, 1>()) : f(H8Inst<1, 1, 3, 2, 0, false, false, 1>());
+    return wide ? f(H8Inst<2, 2, 1, 2, 0, false>()) : f(H8Inst<1, 2, 1, 2, 0, false>());
+}
+
+extern "C" int H8_NAME(l2i_conv2d_h8)(const l2i_conv_params* pp, void* stream) {
+    if (!pp) return l2i_set_error(L2I_E_ARG, "conv2d_h8: null params");
+    return h8_select(*pp, false, [&](auto inst) { return launch_h8<decltype(inst)>(*pp, (hipStream_t)stream); });
 }
 
 extern "C" int H8_NAME(l2i_conv_transpose2d_h8)(const l2i_conv_params* pp, void* stream) {
     if (!pp) return l2i_set_error(L2I_E_ARG, "conv_transpose2d_h8: null params");
-    const l2i_conv_params& p = *pp;
-    if (int rc = h8_common_checks(p, "conv_transpose2d_h8")) return rc;
-    const int nat = (p.H - 1) * 2 - 2 * p.pad_y + 3, natw = (p.W - 1) * 2 - 2 * p.pad_x + 3;
-    if ((p.Cin % 32) != 0) return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d_h8: Cin must be a multiple of 32");
-    if (p.KH != 3 || p.KW != 3 || p.stride != 2 || p.pad_y != p.pad_x || p.pad_x < 0 || p.pad_x > 1 || p.OHf < nat || p.OHf > nat + 8 || p.OWf < natw || p.OWf > natw + 8 ||
-        p.OH != (p.OHf + 1) / 2 || p.OW != (p.OWf + 1) / 2 || p.out_f32 || (p.Cout % 8) != 0 || p.sq_ref || p.in_mask)
-        return l2i_set_error(L2I_E_UNSUPPORTED, "conv_transpose2d_h8: 3x3 stride-2 layer (pad 0 or 1), natural output size (or up to 8 larger), h8 output");
-    hipStream_t st = (hipStream_t)stream;
-    const bool wide = (p.CoutP % 64) == 0;
-    if (p.pad_x == 0) return wide ? launch_h8<2, 1, 3, 1, 1, false>(p, st) : launch_h8<1, 2, 3, 1, 1, false>(p, st);
-    return wide ? launch_h8<2, 1, 3, 1, 2, false>(p, st) : launch_h8<1, 2, 3, 1, 2, false>(p, st);
+    return h8_select(*pp, true, [&](auto inst) { return launch_h8<decltype(inst)>(*pp, (hipStream_t)stream); });
 }
+
+#ifndef L2I_H8_F16
+// Host only, no launch: the plan the entry points of BOTH element types launch `p` with (nothing in the decision depends on the element type).
+extern "C" int l2i_conv_h8_plan_for(const l2i_conv_params* pp, int transposed, l2i_conv_h8_plan* plan) {
+    if (!pp || !plan) return l2i_set_error(L2I_E_ARG, "conv_h8_plan_for: null argument");
+    l2i_conv_h8_plan P = {};
+    const int rc = h8_select(*pp, transposed != 0, [&](auto inst) { return h8_plan_inst<decltype(inst)>(*pp, P); });
+    if (rc != L2I_OK) P = l2i_conv_h8_plan{};              // (the reason is recorded: l2i_last_error)
+    P.eligible = rc == L2I_OK ? 1 : 0;
+    *plan = P;
+    return L2I_OK;
+}
+#endif
 }  // namespace H8_NS

@@ -228,7 +228,8 @@ static int conv_img_h8(const l2i_conv_params* pp, void* stream) {
     if (p.CoutP < p.Cout || (p.CoutP % 32) != 0 || (p.Cout % 8) != 0) return l2i_set_error(L2I_E_ARG, "conv_img_h8: CoutP = Cout rounded up to 32, Cout % 8 == 0");
     if (p.KH != p.KW || p.pad_y != p.pad_x || p.oy_step != 1 || p.ox_step != 1 || p.oy_off < 0 || p.ox_off < 0 || p.OH + p.oy_off > p.OHf || p.OW + p.ox_off > p.OWf)
         return l2i_set_error(L2I_E_ARG, "conv_img_h8: square kernel, symmetric padding, dense output window inside the output tensor");
-    if (p.in_scale || p.in_mask || p.out_scale || p.noise || p.residual || p.res_mask || p.out_mask || p.res_sub || p.accumulate || p.ksplit > 1 || p.out_f32 || p.rgb_w)
+    if (p.in_scale || p.in_mask || p.out_scale || p.noise || p.residual || p.res_mask || p.out_mask || p.res_sub || p.accumulate || p.ksplit > 1 || p.out_f32 || p.rgb_w ||
+        p.w_bstride != 0)                                  // (one plane set for every sample: the kernel stages p.w_hi as is)
         return l2i_set_error(L2I_E_UNSUPPORTED, "conv_img_h8: fused terms are bias, act, out_gain, sq_ref / sq_out");
     if ((p.sq_ref != nullptr) != (p.sq_out != nullptr)) return l2i_set_error(L2I_E_ARG, "conv_img_h8: sq_ref and sq_out go together");
     auto al16 = [](const void* q) { return (((uintptr_t)q) % 16) == 0; };

@@ -9,8 +9,9 @@ the launch to a kernel that does (the recorded family says which) or be refused 
 Bounds are the ones the suite already asserts per family (max|got - ref| / max|ref|): 5e-6 exact-fp32 kernels and the fp32 pair, 3e-5 F(4x4), 2e-5
 bf16x3 (test_bf16x3_split_precision_conv).
 
-Follow-up, not covered here: the 16-bit (h8) epilogues of l2i_conv_h8.hip / l2i_pair_h8.hip have another contract (leaky output mask, sign-plane
-masks); tests/test_h8_gpu.py owns them and a matrix of this kind for them is still to be written."""
+The 16-bit (h8) epilogues of l2i_conv_h8.hip / l2i_img_h8.hip have another contract (leaky output mask, sign-plane masks): their matrix is
+tests/test_epilogue16_contract_gpu.py, against tests/epilogue16_ref.py; the pair / chain3 kernels of l2i_pair_h8.hip are held bit for bit to separate
+l2i_conv2d_h8 launches by tests/test_h8_gpu.py, whose operand sets that matrix contains."""
 from collections import namedtuple
 from contextlib import contextmanager
 
