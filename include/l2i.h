@@ -451,6 +451,54 @@ int l2i_bn_bwd_reduce_f32(double* sum_dy, double* sum_dyxh, const float* gy, con
 int l2i_bn_bwd_apply_f32(float* dx, float* dy_masked, const float* gy, const float* out_mask, const float* x, const float* mean,
                          const float* invstd, const float* gamma, const float* mean_dy, const float* mean_dyxh, int B, int C, int64_t HW,
                          void* stream);
+/* [ABI 12, additive] The [C]-sized algebra between a reduction above and its apply pass, one launch over C each (csrc/l2i_train.hip), so that a
+ * captured graph holds a whole BatchNorm.  n = B * HW of the reduction.  finalize, per channel, float64 until stated otherwise:
+ *   m = sum / n;  var = max(sumsq / n - m * m, 0);  mean = fp32(m);  invstd = fp32(1 / sqrt(var + eps));  then in fp32 scale = weight * invstd,
+ *   shift = bias - mean * scale, running_mean = running_mean * fp32(1 - momentum) + fp32(momentum) * mean, running_var likewise with
+ *   fp32(var * (n / max(n - 1, 1))) (the unbiased variance); num_batches_tracked[0] += 1 (a device int64).  Every product, quotient and sum is
+ *   rounded on its own, no contraction; the float64 square root and quotients are correctly rounded.  running_mean, running_var and
+ *   num_batches_tracked may each be NULL (not updated).
+ * bwd_finalize: d_bias = fp32(sum_dy), d_weight = fp32(sum_dyxh), mean_dy = fp32(sum_dy / n), mean_dyxh = fp32(sum_dyxh / n): exact conversions
+ *   of the float64 sums and quotients.
+ * Refused with L2I_E_ARG before a launch: a null pointer other than the three named, n <= 0, C <= 0, eps < 0, momentum outside [0, 1]. */
+int l2i_bn_finalize_f32(float* mean, float* invstd, float* scale, float* shift, float* running_mean, float* running_var,
+                        int64_t* num_batches_tracked, const double* sum, const double* sumsq, const float* weight, const float* bias, int64_t n, int C,
+                        double eps, double momentum, void* stream);
+int l2i_bn_bwd_finalize_f32(float* d_bias, float* d_weight, float* mean_dy, float* mean_dyxh, const double* sum_dy, const double* sum_dyxh, int64_t n,
+                            int C, void* stream);
+
+/* ---- [ABI 12, additive] Repacking a trained convolution's weight in place, and batches from a device-resident dataset (csrc/l2i_repack.hip) ----------
+ * l2i_repack_taps_f32: w is the weight itself, [Cout][Cin][K][K].  rows = swap ? Cout : Cin, cols = swap ? Cin : Cout.  layout L2I_REPACK_PACKED:
+ *   dst [rows][count][colsP] with dst[r][t][c] = swap ? w[r][c][ky[t]][kx[t]] : w[c][r][ky[t]][kx[t]] for c < cols and 0 for cols <= c < colsP:
+ *   every pack of latent2im_amd/conv.py that is a permutation of the weight (swap = 0 with the K * K taps in row order is pack_weight; swap = 1 with
+ *   the taps reversed is the stride-1 gradient pack; the parity sub-packs, the fused transposed order and the 7x7 stem's [Cin][49][4] are other
+ *   tables).  16-byte stores: colsP % 4 == 0, dst on a 16-byte boundary.  layout L2I_REPACK_OIHW: dst [rows][cols][count], colsP == cols (the plain
+ *   weight a gradient launch keeps).  The table is passed to the kernel by value: a captured graph bakes it in.
+ *   Refused with L2I_E_ARG before a launch: a null pointer, a non-positive size, K > 7, count outside 1..L2I_REPACK_MAX_TAPS, a tap outside the weight,
+ *   colsP < cols, an unknown layout, or what the layout asks of colsP and dst above.
+ * l2i_repack_wino_f32: the Winograd weight transform U = G g G^T of a 3x3 weight w [Cout][Cin][3][3] as seen by a conv of cout' = swap ? Cin : Cout
+ *   output and cin' = swap ? Cout : Cin input channels, g[k][l] = w[..][flip ? 2 - k : k][flip ? 2 - l : l] (swap = flip = 1: the stride-1 gradient).
+ *   kind L2I_REPACK_WINO2: F(2x2,3x3), dst [cin'][4][CoutP][4] (conv.pack_weight_wino); L2I_REPACK_WINO4: F(4x4,3x3), the LDS image order of
+ *   csrc/l2i_wino4.hip (conv.pack_weight_wino4; cin' % 4 == 0); CoutP = cout' rounded up to 32, the padding written as zeros.
+ *   Arithmetic, float64: rows first, T[i][l] = (G[i][0] g[0][l] + G[i][1] g[1][l]) + G[i][2] g[2][l] (k ascending), then columns,
+ *   U[i][j] = (T[i][0] G[j][0] + T[i][1] G[j][1]) + T[i][2] G[j][2] (l ascending); zeros of G are multiplied like any entry, every product and sum
+ *   is rounded on its own with no contraction, and U is rounded once to fp32.  tests/regtrain_ref.py states the same order in numpy.
+ *   Refused with L2I_E_ARG before a launch: a null pointer, a non-positive size, an unknown kind, cin' % 4 != 0 for F(4x4), dst off a 16-byte boundary.
+ * l2i_batch_from_u8_f32: out [B][elems] fp32 = (fp32(src[idx[b]][e]) / 255 - 0.5) * 2 of the uint8 images src [N][elems] (the division correctly
+ *   rounded: CustomDataset's float32 expression bit for bit), idx [B] int64 on the device; label_out [B][L] = labels[idx[b]] when label_out is given.
+ *   An index outside [0, N) writes zeros to both and reads neither.  Refused with L2I_E_ARG: a null out, src or idx, B outside 1..65535, N or elems
+ *   <= 0, label_out without labels or L <= 0. */
+#define L2I_REPACK_MAX_TAPS 49
+#define L2I_REPACK_PACKED 0
+#define L2I_REPACK_OIHW 1
+#define L2I_REPACK_WINO2 2
+#define L2I_REPACK_WINO4 4
+typedef struct l2i_repack_taps { int32_t count; uint8_t ky[L2I_REPACK_MAX_TAPS]; uint8_t kx[L2I_REPACK_MAX_TAPS]; } l2i_repack_taps;
+int l2i_repack_taps_f32(float* dst, const float* w, int Cout, int Cin, int K, const l2i_repack_taps* taps, int swap, int colsP, int layout,
+                        void* stream);
+int l2i_repack_wino_f32(float* dst, const float* w, int Cout, int Cin, int kind, int swap, int flip, void* stream);
+int l2i_batch_from_u8_f32(float* out, float* label_out, const uint8_t* src, const float* labels, const int64_t* idx, int B, int64_t N, int64_t elems,
+                          int L, void* stream);
 
 /* ---- PGGAN-256 generator (BASELINE config 1; reference graphs/pggan/model_256.py) ----
  * PixelNorm fused with the LeakyReLU that follows it (model_256.py:78-84, 128-150) on [B,C,HW] maps:

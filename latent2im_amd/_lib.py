@@ -18,6 +18,7 @@ c_f = ctypes.c_float
 c_i = ctypes.c_int32
 c_p = ctypes.c_void_p
 c_l = ctypes.c_int64
+c_d = ctypes.c_double
 
 
 class ConvParams(ctypes.Structure):
@@ -98,6 +99,25 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [('p', c_p), ('g', c_p), ('m', c_p), ('v', c_p), ('step', c_p), ('n', c_l)]
 
 
+REPACK_MAX_TAPS = 49      # L2I_REPACK_MAX_TAPS
+REPACK_PACKED, REPACK_OIHW = 0, 1      # L2I_REPACK_*: the layouts of l2i_repack_taps_f32
+REPACK_WINO2, REPACK_WINO4 = 2, 4      # the kinds of l2i_repack_wino_f32
+
+
+class RepackTaps(ctypes.Structure):
+    """Mirror of ``struct l2i_repack_taps`` (include/l2i.h): the by-value (ky, kx) table of l2i_repack_taps_f32."""
+    _fields_ = [('count', c_i), ('ky', ctypes.c_uint8 * REPACK_MAX_TAPS), ('kx', ctypes.c_uint8 * REPACK_MAX_TAPS)]
+
+
+def repack_taps(taps):
+    """RepackTaps of [(ky, kx)] (at most REPACK_MAX_TAPS: the entry point refuses more, the mirror has no room for them)."""
+    t = RepackTaps()
+    t.count = len(taps)
+    for i, (ky, kx) in enumerate(taps[:REPACK_MAX_TAPS]):
+        t.ky[i], t.kx[i] = ky, kx
+    return t
+
+
 _SIGNATURES = {
     'l2i_conv2d_f32': (c_i, [ctypes.POINTER(ConvParams), c_p]),
     'l2i_conv2d_family': (c_i, [ctypes.POINTER(ConvParams)]),
@@ -137,6 +157,11 @@ _SIGNATURES = {
     'l2i_bn_apply_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_reduce_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_apply_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
+    'l2i_bn_finalize_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_d, c_d, c_p]),
+    'l2i_bn_bwd_finalize_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_p]),
+    'l2i_repack_taps_f32': (c_i, [c_p, c_p, c_i, c_i, c_i, ctypes.POINTER(RepackTaps), c_i, c_i, c_i, c_p]),
+    'l2i_repack_wino_f32': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'l2i_batch_from_u8_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_p]),
     'l2i_pixelnorm_act_f32': (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_f, c_p]),
     'l2i_pixelnorm_act_bwd_f32': (c_i, [c_p, c_p, c_p, c_i, c_i, c_l, c_f, c_f, c_p]),
     'l2i_upsample2x_nearest_f32': (c_i, [c_p, c_p, c_l, c_i, c_i, c_f, c_p]),
@@ -186,7 +211,8 @@ for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
 ABI_VERSION = 12         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 # Entry points added without an ABI bump: a library of the same ABI version built before them (L2I_LIB = a parent build, for A/B runs) still loads;
 # has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
-ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for'))
+ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for', 'l2i_bn_finalize_f32', 'l2i_bn_bwd_finalize_f32',
+                      'l2i_repack_taps_f32', 'l2i_repack_wino_f32', 'l2i_batch_from_u8_f32'))
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -171,3 +171,49 @@ class CapturedZStep(_CapturedWalkStep):
         from . import pggan
         loss, x0, x1, a0, target = pggan.walk_forward_backward(self.g, self.z, self.alpha, no_content_loss=self.no_content_loss, no_gan_loss=True)
         return dict(loss=loss.detach(), x0=x0.detach(), x1=x1.detach(), a0=a0.detach(), target=target.detach(), terms=self.g.last_terms)
+
+
+class CapturedRegressorStep(_StagedInputs):
+    """One optimiser step of the attribute regressor (regressor_train.train_step_resident on a resident TrainableResNet50) recorded into ONE
+    stream of one hipGraph: (gather,) forward, loss, backward, guarded Adam, in-place repack.  The optimiser is inside the graph because its
+    state is on the device (optim.GuardedAdam: counters included) and its table of pointers never changes (the model's gradient arena);
+    ``record``'s rule holds: the warm-up runs forward, loss and backward only — no update, no repack, and the BatchNorm running statistics
+    and batch counters stay as they are (model.track_stats) — and the update is recorded only while the stream is capturing.
+
+    Inputs: ``dataset`` None — ``step(data, label)`` stages host tensors [B, 3, S, S] / [B, 40] through the pinned ring of ``_StagedInputs``;
+    a regressor_train.DeviceDataset — ``step(idx=...)`` copies B checked int64 indices and the graph's first node gathers the batch
+    (l2i_batch_from_u8_f32).  Returns the loss of the step, a device scalar that the next replay overwrites."""
+
+    def __init__(self, model, optimizer, batch, size, dataset=None, warmup=2):
+        from . import regressor_train as RT
+        if not getattr(model, 'resident', False):
+            raise ValueError('CapturedRegressorStep records a resident model (TrainableResNet50(..., resident=True))')
+        if not hasattr(optimizer, 'init_state'):
+            raise ValueError('CapturedRegressorStep records a device-side optimiser (regressor_train.make_optimizer(model, guarded=True))')
+        optimizer.init_state()                                             # moments, counters and guard words outside the graph's pool
+        self.model, self.optimizer, self.dataset, self.batch = model, optimizer, dataset, batch
+        n_out = model.fc_w.shape[0]
+        self._init_inputs(model.device, batch, 3 * size * size, n_out)
+        self.data, self.label = self.z.view(batch, 3, size, size), self.alpha
+        self.idx = torch.zeros(batch, dtype=torch.long, device=model.device) if dataset is not None else None
+
+        def step():
+            capturing = torch.cuda.is_current_stream_capturing()
+            if dataset is not None:
+                dataset.gather(self.idx, self.data, self.label)
+            model.track_stats = capturing
+            try:
+                return RT.train_step_resident(model, optimizer, self.data, self.label, update=capturing).detach()
+            finally:
+                model.track_stats = True
+        self.graph, self.loss, self._ws_keep = record(model.device, step, warmup)
+
+    def __call__(self, data=None, label=None, idx=None):
+        if self.dataset is not None:
+            idx = torch.as_tensor(idx, dtype=torch.long).reshape(-1)
+            assert idx.numel() == self.batch
+            self.idx.copy_(idx, non_blocking=True)
+        else:
+            self.load(torch.as_tensor(data, dtype=torch.float32).reshape(self.batch, -1).cpu(), torch.as_tensor(label, dtype=torch.float32).cpu())
+        self.graph.replay()
+        return self.loss

@@ -552,6 +552,42 @@ def run_plan(plan, x, y, accumulate=False, **kw):
     return y
 
 
+_TAP_TABLES = {}      # tuple of (ky, kx) -> _lib.RepackTaps (built once: the tables of a net never change)
+
+
+def _repack_taps(dst, weight, taps, swap, layout=_lib.REPACK_PACKED):
+    """dst <- the taps ``taps`` of ``weight`` [Cout, Cin, K, K] (l2i_repack_taps_f32): a [rows][taps][colsP] pack, or the plain
+    [rows][cols][taps] weight for REPACK_OIHW; rows are the input channels, or with ``swap`` the output channels."""
+    cout, cin, k, _ = weight.shape
+    key = tuple(taps)
+    table = _TAP_TABLES.get(key)
+    if table is None:
+        table = _TAP_TABLES[key] = _lib.repack_taps(key)
+    rows, cols = (cout, cin) if swap else (cin, cout)
+    colsp = dst.shape[-1] if layout == _lib.REPACK_PACKED else cols
+    assert dst.numel() == rows * len(key) * colsp and dst.device == weight.device, (tuple(dst.shape), rows, len(key), colsp)
+    _lib.call('l2i_repack_taps_f32', _lib.fptr(dst), _lib.fptr(weight), cout, cin, k, table, int(swap), colsp, layout)
+
+
+def _repack_launch(L, weight, taps, swap, flip=None):
+    """Rewrite in place what Launch ``L`` derived from its weight: ``L`` is the correlation whose weight is w'[co', ci', a] =
+    weight[.., taps[a]] with the roles of the two channel axes swapped when ``swap``.  ``flip`` (3x3 stride-1 launches: whether taps is the
+    reversed order) lets the Winograd packs be rewritten straight from the weight; None: the launch never takes a Winograd kernel."""
+    _repack_taps(L.w, weight, taps, swap)
+    if L.w4 is not None:
+        _repack_taps(L.w4, weight, taps, swap)
+    if L.w_src is not None and L.w_src.data_ptr() != weight.data_ptr():
+        _repack_taps(L.w_src, weight, taps, not swap, _lib.REPACK_OIHW)      # [cout', cin', kh, kw]: its rows are the pack's columns
+    if L.w16 is not None:
+        raise _lib.L2IError('repack_: no kernel rewrites bf16x3 planes (L2I_PRECISION=bf16x3 is for frozen weights)')
+    for pack, kind in ((L.wino, _lib.REPACK_WINO2), (L.wino4, _lib.REPACK_WINO4)):
+        if pack is not None:
+            if flip is None:
+                raise _lib.L2IError('repack_: a Winograd pack on a launch that is not a whole 3x3 weight')
+            cout, cin = weight.shape[:2]
+            _lib.call('l2i_repack_wino_f32', _lib.fptr(pack), _lib.fptr(weight), cout, cin, kind, int(swap), int(flip))
+
+
 def _weight_f32(weight, keep_cuda=False):
     """A conv weight (numpy array or tensor) as an fp32 tensor on the host; ``keep_cuda``: a CUDA weight stays where it lives."""
     w = torch.as_tensor(weight if torch.is_tensor(weight) else np.asarray(weight), dtype=torch.float32)
@@ -622,6 +658,40 @@ class FrozenConv2d:
                 and gy.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and (kw.get('in_mask') is None or kw['in_mask'].data_ptr() % 16 == 0)):
             return run_small_transposed(self.bwd_small, gy, out, **kw)
         return run_plan(self.bwd, gy, out, **kw)
+
+    def repack_(self, weight):
+        """Rewrite, in the memory they already occupy, every tensor this object derived from its weight, from ``weight`` (the same shape, fp32,
+        contiguous, on the device of the packs): the forward pack, the flipped / role-swapped gradient pack or the parity sub-packs of a stride-2
+        gradient, FusedTransposed.w, SmallTransposed.w, w4, the kept plain weights and whatever Winograd pack has been built by now — HIP launches
+        on the current stream only (csrc/l2i_repack.hip), no allocation, no pointer moves: a captured graph replays it.  For a convolution that is
+        being trained, built from a CUDA weight (so without the 25-plane pack, see FusedTransposed); transposed=True is not a layer of such a net."""
+        if self.transposed:
+            raise NotImplementedError('repack_: built for the convolutions of a net that is being trained (no transposed=True layer)')
+        if tuple(weight.shape) != (self.cout, self.cin, self.k, self.k) or weight.dtype != torch.float32 or not weight.is_contiguous():
+            raise _lib.L2IError('repack_ takes a contiguous float32 weight of shape %s' % ((self.cout, self.cin, self.k, self.k),))
+        k = self.k
+        full = [(ky, kx) for ky in range(k) for kx in range(k)]
+        fwd = self.fwd[0]
+        if fwd.w_src is not None and fwd.w_src.data_ptr() != weight.data_ptr():
+            fwd.w_src = weight                                    # the forward launch keeps the weight itself, not a copy
+        _repack_launch(fwd, weight, full, False, flip=False)
+        if self.stride == 1:
+            _repack_launch(self.bwd[0], weight, [(k - 1 - ky, k - 1 - kx) for ky, kx in full], True, flip=True)
+            return self
+        for L, (py, px) in zip(self.bwd, ((0, 0), (0, 1), (1, 0), (1, 1))):
+            if L is not None:
+                ty, tx = _phase_axis(k, self.padding, py)[0], _phase_axis(k, self.padding, px)[0]
+                _repack_launch(L, weight, [(a, b) for a in ty for b in tx], True)
+        F = self.bwd_fused
+        if F is not None:
+            if F.poly is not None or F.poly_src is not None or F.w16 is not None:
+                raise _lib.L2IError('repack_: this convolution was packed from a host weight (25-plane or bf16x3 planes); build it from a CUDA weight')
+            _repack_taps(F.w, weight, fused_transposed_taps(k, self.padding), True)
+            if F.w_src is not None:
+                _repack_taps(F.w_src, weight, full, False, _lib.REPACK_OIHW)
+        if self.bwd_small is not None:
+            _repack_taps(self.bwd_small.w, weight, full, True)
+        return self
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------

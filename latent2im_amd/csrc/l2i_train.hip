@@ -13,6 +13,8 @@
 //   l2i_bn_bwd_reduce_f32  sum_dy[c], sum_dy_xhat[c] with dy = gy * (out > 0 ?), xhat = (x - mean[c]) * invstd[c]      (float64 sums)
 //   l2i_bn_bwd_apply_f32   dx = gamma*invstd * (dy - sum_dy/N - xhat * sum_dy_xhat/N); optionally also writes the masked dy (the gradient
 //                          of a residual branch)
+//   l2i_bn_finalize_f32    sums -> mean, invstd, scale, shift, running statistics and the batch counter: one launch over C
+//   l2i_bn_bwd_finalize_f32  sums -> d bias, d weight and the two means l2i_bn_bwd_apply_f32 takes
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "l2i.h"
@@ -210,6 +212,74 @@ extern "C" int l2i_bn_bwd_apply_f32(float* dx, float* dy_masked, const float* gy
     const long long n = (long long)B * C * HW;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(l2i_grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, dx, dy_masked, gy, out_mask, x, mean, invstd, gamma,
                        mean_dy, mean_dyxh, C, (long long)HW, n);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The [C]-sized algebra between the reduction and the apply pass of each direction: one launch over C instead of a dozen torch ops, so that
+// a captured graph holds the whole BatchNorm.  Every float64 and float32 operation below is rounded on its own (no contraction).
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bn_finalize_kernel(float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale,
+                                                          float* __restrict__ shift, float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                          long long* __restrict__ num_batches_tracked, const double* __restrict__ sum,
+                                                          const double* __restrict__ sumsq, const float* __restrict__ weight,
+                                                          const float* __restrict__ bias, double n, double unbias, double eps, float keep, float mom, int C) {
+#pragma clang fp contract(off)                                                  // every product and sum below is an instruction of its own
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c == 0 && num_batches_tracked) num_batches_tracked[0] += 1;
+    if (c >= C) return;
+    const double m64 = sum[c] / n;
+    const double ex2 = sumsq[c] / n, mm = m64 * m64;
+    double var = ex2 - mm;                                                      // biased variance normalises
+    if (!(var > 0.0)) var = 0.0;
+    const float m = (float)m64;
+    const double ve = var + eps;
+    const float is = (float)(1.0 / __builtin_sqrt(ve));
+    mean[c] = m; invstd[c] = is;
+    const float sc = weight[c] * is;
+    const float msc = m * sc;
+    scale[c] = sc;
+    shift[c] = bias[c] - msc;
+    if (running_mean) {
+        const float a = running_mean[c] * keep, b = mom * m;
+        running_mean[c] = a + b;
+    }
+    if (running_var) {
+        const double vu = var * unbias;
+        const float a = running_var[c] * keep, b = mom * (float)vu;
+        running_var[c] = a + b;
+    }
+}
+
+extern "C" int l2i_bn_finalize_f32(float* mean, float* invstd, float* scale, float* shift, float* running_mean, float* running_var,
+                                   int64_t* num_batches_tracked, const double* sum, const double* sumsq, const float* weight, const float* bias,
+                                   int64_t n, int C, double eps, double momentum, void* stream) {
+    if (!mean || !invstd || !scale || !shift || !sum || !sumsq || !weight || !bias) return l2i_set_error(L2I_E_ARG, "bn_finalize: null pointer");
+    if (n <= 0 || C <= 0 || !(eps >= 0.0) || !(momentum >= 0.0 && momentum <= 1.0)) return l2i_set_error(L2I_E_ARG, "bn_finalize: n, C >= 1, eps >= 0, momentum in [0, 1]");
+    const double unbias = (double)n / (double)(n > 1 ? n - 1 : 1);              // the unbiased variance feeds the running statistic
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, invstd, scale, shift, running_mean, running_var,
+                       (long long*)num_batches_tracked, sum, sumsq, weight, bias, (double)n, unbias, eps, (float)(1.0 - momentum), (float)momentum, C);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(float* __restrict__ d_bias, float* __restrict__ d_weight, float* __restrict__ m_dy,
+                                                              float* __restrict__ m_dyxh, const double* __restrict__ sum_dy,
+                                                              const double* __restrict__ sum_dyxh, double n, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const double s = sum_dy[c], q = sum_dyxh[c];
+    d_bias[c] = (float)s; d_weight[c] = (float)q;
+    m_dy[c] = (float)(s / n); m_dyxh[c] = (float)(q / n);
+}
+
+extern "C" int l2i_bn_bwd_finalize_f32(float* d_bias, float* d_weight, float* mean_dy, float* mean_dyxh, const double* sum_dy, const double* sum_dyxh,
+                                       int64_t n, int C, void* stream) {
+    if (!d_bias || !d_weight || !mean_dy || !mean_dyxh || !sum_dy || !sum_dyxh) return l2i_set_error(L2I_E_ARG, "bn_bwd_finalize: null pointer");
+    if (n <= 0 || C <= 0) return l2i_set_error(L2I_E_ARG, "bn_bwd_finalize: n, C >= 1");
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_bias, d_weight, mean_dy, mean_dyxh, sum_dy,
+                       sum_dyxh, (double)n, C);
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }

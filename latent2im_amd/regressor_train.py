@@ -7,6 +7,11 @@ Everything heavy runs on libl2i_hip.so: the forward / input-gradient convolution
 GPU after every optimiser step), the weight gradients ``l2i_conv2d_wgrad_f32`` and the training-mode BatchNorm passes ``l2i_bn_*``
 (csrc/l2i_train.hip).  torch supplies tensors, the [C]-sized statistics algebra, the 2048x40 fc GEMMs and ``torch.optim.Adam`` (the
 reference uses it too).  No autograd graph is built: the backward is scheduled by hand like the frozen networks' input-gradients.
+
+Opt-in (``TrainableResNet50(resident=True)``, ``make_optimizer(guarded=True)``, ``DeviceDataset``, ``main(resident / hip_graph / device_data)``):
+the same step with nothing packed, allocated or counted on the host between two batches — packs rewritten in place (csrc/l2i_repack.hip), the
+[C]-sized algebra as kernels, one gradient arena, optim.GuardedAdam, batches gathered from uint8 crops on the device — which
+capture.CapturedRegressorStep records into one hipGraph.
 """
 import csv
 import os
@@ -102,30 +107,126 @@ class _Conv:
         return conv_wgrad(x, gy, self.k, self.stride, self.padding)
 
 
+class _ResidentBN(_BN):
+    """_BN of a resident model: the sums of both passes are slices of the model's two float64 arenas (zeroed by one memset per pass), the
+    [C]-sized algebra is l2i_bn_finalize_f32 / l2i_bn_bwd_finalize_f32 into buffers that live as long as the model, and the parameter gradients
+    land in the model's gradient arena.  ``owner.track_stats`` False (the warm-up of a recording): the running statistics and the batch
+    counter stay as they are."""
+
+    def attach(self, owner, fwd_sums, bwd_sums, small, g_weight, g_bias):
+        self.owner, self.fs, self.bs = owner, fwd_sums, bwd_sums
+        self.mean, self.invstd, self.scale, self.shift, self.m_dy, self.m_dyxh = small
+        self.g_weight, self.g_bias = g_weight, g_bias
+
+    def forward(self, x, residual=None, relu=True):
+        b, c, h, w = x.shape
+        track = self.owner.track_stats
+        _lib.call('l2i_bn_stats_f32', _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(x), b, c, h * w)
+        _lib.call('l2i_bn_finalize_f32', _lib.fptr(self.mean), _lib.fptr(self.invstd), _lib.fptr(self.scale), _lib.fptr(self.shift),
+                  _lib.fptr(self.running_mean) if track else None, _lib.fptr(self.running_var) if track else None,
+                  _lib.ptr(self.num_batches_tracked) if track else None, _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(self.weight),
+                  _lib.fptr(self.bias), b * h * w, c, BN_EPS, BN_MOMENTUM)
+        y = torch.empty_like(x)
+        _lib.call('l2i_bn_apply_f32', _lib.fptr(y), _lib.fptr(x), _lib.fptr(self.scale), _lib.fptr(self.shift), _lib.fptr(residual), int(relu), b, c, h * w)
+        return y, (x, self.mean, self.invstd)
+
+    def backward(self, gy, saved, out_mask=None, want_masked=False):
+        x, mean, invstd = saved
+        b, c, h, w = x.shape
+        _lib.call('l2i_bn_bwd_reduce_f32', _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
+                  _lib.fptr(invstd), b, c, h * w)
+        _lib.call('l2i_bn_bwd_finalize_f32', _lib.fptr(self.g_bias), _lib.fptr(self.g_weight), _lib.fptr(self.m_dy), _lib.fptr(self.m_dyxh),
+                  _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), b * h * w, c)
+        dx = torch.empty_like(x)
+        gm = torch.empty_like(x) if want_masked else None
+        _lib.call('l2i_bn_bwd_apply_f32', _lib.fptr(dx), _lib.fptr(gm), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
+                  _lib.fptr(invstd), _lib.fptr(self.weight), _lib.fptr(self.m_dy), _lib.fptr(self.m_dyxh), b, c, h * w)
+        return dx, self.g_weight, self.g_bias, gm
+
+
+class _ResidentConv(_Conv):
+    """_Conv of a resident model: packed once, then rewritten in place from the weight (FrozenConv2d.repack_); the weight gradient accumulates
+    straight into its view of the model's gradient arena (zeroed once per step)."""
+
+    def plan(self):
+        if self.fc is None:
+            super().plan()
+        else:
+            self.fc.repack_(self.weight)
+
+    def wgrad(self, x, gy):
+        b, cin, h, w = x.shape
+        _, cout, oh, ow = gy.shape
+        _lib.call('l2i_conv2d_wgrad_f32', _lib.fptr(self.g_weight), _lib.fptr(x), _lib.fptr(gy), b, cin, h, w, cout, oh, ow, self.k, self.k, self.stride,
+                  self.padding, self.padding)
+        return self.g_weight
+
+
 class TrainableResNet50:
     """torchvision ResNet-50 v1.5 (stride on the 3x3, downsample on the first block of a layer, adaptive average pool), every parameter
     trainable, BatchNorm in training mode.  ``state_dict()`` / ``load_state_dict()`` use torchvision's key names, so the checkpoints are
-    the ones ``graph.load_networks`` (and the reference) read."""
+    the ones ``graph.load_networks`` (and the reference) read.
 
-    def __init__(self, state, device='cuda', num_classes=40):
+    ``resident=True``: nothing the step touches between two batches is allocated or packed by the host — every parameter gradient is a view
+    of ONE flat buffer (``grad_arena``, zeroed once per step; ``p.grad`` points into it for good, so an optimiser's table of pointers never
+    changes), the BatchNorm sums of a pass are one float64 arena zeroed by one memset, ``replan()`` is 53 ``FrozenConv2d.repack_`` calls.
+    The step is then ``train_step_resident``; it can be recorded into a hipGraph (capture.CapturedRegressorStep)."""
+
+    def __init__(self, state, device='cuda', num_classes=40, resident=False):
         P = state
         self.device = device
-        self.stem, self.stem_bn = _Conv(P, 'conv1', 2, 3, device), _BN(P, 'bn1', device)
+        self.resident, self.track_stats = bool(resident), True
+        Conv, BN = (_ResidentConv, _ResidentBN) if resident else (_Conv, _BN)
+        self.stem, self.stem_bn = Conv(P, 'conv1', 2, 3, device), BN(P, 'bn1', device)
         self.blocks = []
         for li, (planes, blocks, stride) in enumerate(RESNET50_LAYERS):
             for b in range(blocks):
                 p = 'layer%d.%d' % (li + 1, b)
                 s = stride if b == 0 else 1
                 self.blocks.append(dict(
-                    c1=_Conv(P, p + '.conv1', 1, 0, device), b1=_BN(P, p + '.bn1', device),
-                    c2=_Conv(P, p + '.conv2', s, 1, device), b2=_BN(P, p + '.bn2', device),
-                    c3=_Conv(P, p + '.conv3', 1, 0, device), b3=_BN(P, p + '.bn3', device),
-                    cd=_Conv(P, p + '.downsample.0', s, 0, device) if b == 0 else None,
-                    bd=_BN(P, p + '.downsample.1', device) if b == 0 else None))
+                    c1=Conv(P, p + '.conv1', 1, 0, device), b1=BN(P, p + '.bn1', device),
+                    c2=Conv(P, p + '.conv2', s, 1, device), b2=BN(P, p + '.bn2', device),
+                    c3=Conv(P, p + '.conv3', 1, 0, device), b3=BN(P, p + '.bn3', device),
+                    cd=Conv(P, p + '.downsample.0', s, 0, device) if b == 0 else None,
+                    bd=BN(P, p + '.downsample.1', device) if b == 0 else None))
         self.fc_w = torch.as_tensor(np.asarray(P['fc.weight']), dtype=torch.float32).clone().to(device)
         self.fc_b = torch.as_tensor(np.asarray(P['fc.bias']), dtype=torch.float32).clone().to(device)
         assert self.fc_w.shape[0] == num_classes
+        if resident:
+            self._make_resident()
         self.replan()
+
+    def _convs(self):
+        return [self.stem] + [blk[c] for blk in self.blocks for c in ('c1', 'c2', 'c3', 'cd') if blk[c] is not None]
+
+    def _make_resident(self):
+        """The arenas of a resident model, and every object's views into them."""
+        named = self.named_parameters()
+        offs, total = {}, 0
+        for k, t in named:
+            offs[k] = total
+            total += (t.numel() + 3) // 4 * 4                       # every view on a 16-byte boundary (the optimiser's 16-byte accesses)
+        self.grad_arena = torch.zeros(total, device=self.device, dtype=torch.float32)
+        self.grads = {k: self.grad_arena[offs[k]:offs[k] + t.numel()].view(t.shape) for k, t in named}
+        for k, t in named:
+            t.grad = self.grads[k]
+        bns = self._bns()
+        csum = sum(bn.weight.numel() for bn in bns)
+        self.fwd_sums = torch.zeros(2 * csum, device=self.device, dtype=torch.float64)
+        self.bwd_sums = torch.zeros(2 * csum, device=self.device, dtype=torch.float64)
+        small = torch.zeros(6 * csum, device=self.device, dtype=torch.float32)
+        o = 0
+        for bn in bns:
+            c = bn.weight.numel()
+            bn.attach(self, self.fwd_sums[2 * o:2 * (o + c)].view(2, c), self.bwd_sums[2 * o:2 * (o + c)].view(2, c),
+                      [small[6 * o + i * c:6 * o + (i + 1) * c] for i in range(6)], self.grads[bn.name + '.weight'], self.grads[bn.name + '.bias'])
+            o += c
+        for cv in self._convs():
+            cv.g_weight = self.grads[cv.name + '.weight']
+
+    def zero_grad(self):
+        """Resident: one memset over every parameter gradient."""
+        self.grad_arena.zero_()
 
     # -- parameters (torchvision order: conv1, bn1, layer*.*, fc) ------------------------------------------------------------
     def named_parameters(self):
@@ -173,6 +274,8 @@ class TrainableResNet50:
     def forward(self, img, keep=True):
         """[B,3,H,W] -> [B,40] in training mode; ``keep``: save what ``backward`` needs."""
         x = img.detach().contiguous()
+        if self.resident:
+            self.fwd_sums.zero_()                                   # every BatchNorm's sums of this pass: one memset
         z0 = self.stem.forward(x)
         a0, s0 = self.stem_bn.forward(z0)
         p0, idx0 = K.maxpool2d_fwd(a0, 3, 2, 1)
@@ -202,7 +305,12 @@ class TrainableResNet50:
     def backward(self, g_preds):
         """dL/d preds [B,40] -> {parameter name: gradient} (and nothing else: the image gets no gradient here)."""
         sv = self._saved
-        grads = {'fc.weight': torch.mm(g_preds.t(), sv['feat']), 'fc.bias': g_preds.sum(0)}
+        if self.resident:                                          # into the gradient arena (zeroed by the caller: the weight gradients accumulate)
+            self.bwd_sums.zero_()
+            grads = {'fc.weight': torch.mm(g_preds.t(), sv['feat'], out=self.grads['fc.weight']),
+                     'fc.bias': torch.sum(g_preds, 0, out=self.grads['fc.bias'])}
+        else:
+            grads = {'fc.weight': torch.mm(g_preds.t(), sv['feat']), 'fc.bias': g_preds.sum(0)}
         b, c, h, w = sv['last']
         g = (torch.mm(g_preds, self.fc_w) * (1.0 / (h * w))).reshape(b, c, 1, 1).expand(b, c, h, w).contiguous()
         for blk, saved in zip(reversed(self.blocks), reversed(sv['blocks'])):
@@ -264,7 +372,29 @@ def train_step(model, optimizer, data, label):
     return loss
 
 
-def make_optimizer(model, lr=1e-4):
+def train_step_resident(model, optimizer, data, label, update=True):
+    """``train_step`` on a resident model: the gradients land in the model's arena (``p.grad`` already points there), the packs are rewritten
+    in place.  Nothing here reads the device or depends on the step count, so a stream capture records it as it stands (``update`` False: the
+    warm-up of a recording stops before the optimiser)."""
+    assert model.resident
+    preds = model(data)
+    model.zero_grad()
+    loss, g = mse_loss_and_grad(preds, label.to(preds.device).float())
+    model.backward(g)
+    if update:
+        optimizer.step()
+        model.replan()
+    return loss
+
+
+def make_optimizer(model, lr=1e-4, guarded=False):
+    """scene_regressor_256.py:116: Adam(lr=1e-4), default betas.  ``guarded``: optim.GuardedAdam — the same arithmetic on the device (step
+    counters included, so a hipGraph replays it; a step with a non-finite gradient is skipped as a whole), state allocated here and now."""
+    if guarded:
+        from . import optim
+        opt = optim.GuardedAdam(model.parameters(), lr=lr)
+        opt.init_state()
+        return opt
     return torch.optim.Adam(model.parameters(), lr=lr)                          # scene_regressor_256.py:116
 
 
@@ -304,6 +434,13 @@ class CustomDataset:
         return len(self.image_list)
 
     def __getitem__(self, index):
+        crop, label = self.crop_u8(index)
+        a = np.asarray(crop, dtype=np.float32) / 255.0
+        x = torch.from_numpy((a.transpose(2, 0, 1) - 0.5) / 0.5)
+        return x, torch.Tensor(label)
+
+    def crop_u8(self, index):
+        """(the resized, centre-cropped image as uint8 [S, S, 3], its label row): everything of ``__getitem__`` before ToTensor."""
         from PIL import Image
         path = self.image_list[index]
         im = Image.open(path).convert('RGB')
@@ -314,30 +451,85 @@ class CustomDataset:
         im = im.resize(new, Image.BILINEAR)
         w, h = im.size
         l, t = (w - self.image_size) // 2, (h - self.image_size) // 2
-        a = np.asarray(im.crop((l, t, l + self.image_size, t + self.image_size)), dtype=np.float32) / 255.0
-        x = torch.from_numpy((a.transpose(2, 0, 1) - 0.5) / 0.5)
-        return x, torch.Tensor(self.label_dict['/'.join(path.split('/')[-2:])])
+        return np.asarray(im.crop((l, t, l + self.image_size, t + self.image_size)), dtype=np.uint8), self.label_dict['/'.join(path.split('/')[-2:])]
+
+
+class DeviceDataset:
+    """A split kept on the GPU: ``dataset`` (a CustomDataset: deterministic Resize + CenterCrop, no augmentation) is decoded ONCE; the uint8
+    crops [N, 3, S, S] and the labels [N, 40] stay on the device (the whole training split is under 2 GB) and a batch is one launch of
+    l2i_batch_from_u8_f32 by an int64 index tensor — bit for bit what ``dataset[j]`` gives."""
+
+    def __init__(self, dataset, device='cuda'):
+        n, s = len(dataset), dataset.image_size
+        crops, labels = np.empty((n, 3, s, s), dtype=np.uint8), None
+        for j in range(n):
+            crop, label = dataset.crop_u8(j)
+            crops[j] = crop.transpose(2, 0, 1)
+            if labels is None:
+                labels = np.empty((n, len(label)), dtype=np.float32)
+            labels[j] = np.asarray(label, dtype=np.float32)              # (what torch.Tensor(label) rounds to)
+        self.n, self.size, self.device = n, s, device
+        self.crops, self.labels = torch.from_numpy(crops).to(device), torch.from_numpy(labels).to(device)
+
+    def __len__(self):
+        return self.n
+
+    def indices(self, sel):
+        """A host selection -> int64 indices, checked here (on the device an index outside [0, N) gives a zero image, not an error)."""
+        sel = np.asarray(sel, dtype=np.int64).reshape(-1)
+        if sel.size == 0 or sel.min() < 0 or sel.max() >= self.n:
+            raise IndexError('DeviceDataset: indices outside [0, %d)' % self.n)
+        return torch.from_numpy(sel)
+
+    def gather(self, idx, data=None, label=None):
+        """data [B, 3, S, S], label [B, 40] <- the images / labels at the device indices ``idx`` (on the current stream)."""
+        b = idx.numel()
+        data = torch.empty(b, 3, self.size, self.size, device=self.device) if data is None else data
+        label = torch.empty(b, self.labels.shape[1], device=self.device) if label is None else label
+        assert idx.dtype == torch.long and data.shape[0] == b and label.shape == (b, self.labels.shape[1])
+        _lib.call('l2i_batch_from_u8_f32', _lib.fptr(data), _lib.fptr(label), _lib.ptr(self.crops), _lib.fptr(self.labels), _lib.ptr(idx), b, self.n,
+                  3 * self.size * self.size, self.labels.shape[1])
+        return data, label
+
+    def batch(self, sel):
+        return self.gather(self.indices(sel).to(self.device))
 
 
 def main(data_path='/transient_scene/imageAlignedLD/', label_path='/transient_scene/annotations/annotations.tsv',
-         split_path='/transient_scene/training_test_splits/random_split/', n_epoch=500, batch_size=32, out_dir='./checkpoint_256', state=None):
+         split_path='/transient_scene/training_test_splits/random_split/', n_epoch=500, batch_size=32, out_dir='./checkpoint_256', state=None,
+         image_size=256, resident=False, hip_graph=False, device_data=False):
     """The reference script's __main__ (scene_regressor_256.py:86-171) without tensorboard / tqdm: train, evaluate (in training mode, like the
-    reference), save a checkpoint per epoch."""
+    reference), save a checkpoint per epoch.  Opt-in: ``resident`` — the resident model and the guarded Adam (train_step_resident);
+    ``hip_graph`` (implies resident) — full batches replay capture.CapturedRegressorStep, the ragged last batch and the test loop run the same
+    model and optimiser eagerly; ``device_data`` — the training split lives on the GPU (DeviceDataset)."""
     from . import synth
     os.makedirs(out_dir, exist_ok=True)
     labels = load_labelfile(label_path)
-    train = CustomDataset(data_path, labels, split_path + 'training.txt')
-    test = CustomDataset(data_path, labels, split_path + 'test.txt')
+    train = CustomDataset(data_path, labels, split_path + 'training.txt', image_size=image_size)
+    test = CustomDataset(data_path, labels, split_path + 'test.txt', image_size=image_size)
+    resident = resident or hip_graph
     # the reference starts from torchvision's ImageNet weights (a download); offline the caller passes a state dict, or seeded random init
-    model = TrainableResNet50(state if state is not None else synth.resnet50_state(seed=300), device='cuda')
-    optimizer = make_optimizer(model)
+    model = TrainableResNet50(state if state is not None else synth.resnet50_state(seed=300), device='cuda', resident=resident)
+    optimizer = make_optimizer(model, guarded=resident)
+    step = train_step_resident if resident else train_step
+    on_device = DeviceDataset(train) if device_data else None
+    captured = None
     for epoch in range(n_epoch):
         order = np.random.permutation(len(train))
         for i in range(0, len(order), batch_size):
-            batch = [train[j] for j in order[i:i + batch_size]]
-            data = torch.stack([b[0] for b in batch]).cuda()
-            label = torch.stack([b[1] for b in batch]).cuda()
-            loss = train_step(model, optimizer, data, label)
+            sel = order[i:i + batch_size]
+            if on_device is None:
+                batch = [train[j] for j in sel]
+                data, label = torch.stack([b[0] for b in batch]), torch.stack([b[1] for b in batch])
+            if hip_graph and len(sel) == batch_size:
+                if captured is None:
+                    from . import capture
+                    captured = capture.CapturedRegressorStep(model, optimizer, batch_size, image_size, dataset=on_device)
+                loss = captured(idx=on_device.indices(sel)) if on_device is not None else captured(data, label)
+                continue
+            if on_device is not None:
+                data, label = on_device.batch(sel)
+            loss = step(model, optimizer, data.cuda(), label.cuda())
         if epoch != 0:
             tl = []
             for i in range(0, len(test), batch_size):
