@@ -661,6 +661,45 @@ int l2i_pixelnorm_act_bwd_h8(void* dx, const void* gy, const void* x, const void
 int l2i_pixelnorm_act_bwd_h8_f16(void* dx, const void* gy, const void* x, const void* addend, int B, int C, int H, int W, float eps, float slope, int pool,
                                  void* stream);
 
+/* ---- [ABI 12, additive] Training on 16-bit h8 maps: the weight gradient of a convolution and training-mode BatchNorm (csrc/l2i_train_h8.hip; bf16
+ * elements, and IEEE fp16 with the suffix _f16).  Maps are h8 [B][C/8][H][W][8] on 16-byte boundaries.  No floating-point atomics: every sum has
+ * a fixed order, so two calls on the same inputs give the same bits.  Nothing is allocated: the caller passes the workspaces.
+ * l2i_conv2d_wgrad_h8: dw[co,ci,ky,kx] = out_scale * sum_{b,oy,ox} gy[b,co,oy,ox] * x[b,ci,oy*stride+ky-pad,ox*stride+kx-pad], products on
+ *   v_mfma_f32_32x32x16 (exact in fp32), fp32 accumulation: per 64-pixel wave strip, the four waves of a block, then the pixel slices in slice order.
+ *   dw fp32 [Cout][Cin][K][K] is OVERWRITTEN (no zeroed buffer needed).  out_scale = the host float, times *out_scale_dev when that pointer is not
+ *   NULL (read on the device at run time: the inverse of a dynamic loss scale).  ws: ws_bytes >= what l2i_conv2d_wgrad_ws_h8 returns for the shape.
+ *   Built for K in {1, 3}, stride in {1, 2}, pad in {0, 1}, Cin % 32 == 0, Cout % 32 == 0, OH / OW the conv's output size, x and gy below 4 GiB
+ *   each: everything else, a NULL ws and a ws too small return L2I_E_UNSUPPORTED with a message and launch nothing.
+ * l2i_conv2d_wgrad_ws_h8 (host only): *bytes = the workspace of that shape (0 and L2I_E_UNSUPPORTED for a refused shape).
+ * l2i_bn_stats_h8: sum[c], sumsq[c] (float64, OVERWRITTEN) of the stored elements of x over (b, pixel): what l2i_bn_finalize_f32 reads.
+ * l2i_bn_apply_h8: y = relu?(x * scale[c] + shift[c] (+ residual)), fp32 arithmetic, one rounding at the store; residual (h8) may be NULL.
+ * l2i_bn_bwd_reduce_h8: sum_dy[c] = sum dy, sum_dyxh[c] = sum dy * xhat (float64, OVERWRITTEN) with dy = gy * (out_mask > 0) when out_mask (h8, may be
+ *   NULL) is given, xhat = (x - mean[c]) * invstd[c] in fp32: what l2i_bn_bwd_finalize_f32 reads.
+ * l2i_bn_bwd_apply_h8: dx = gamma[c] * invstd[c] * (dy - mean_dy[c] - xhat * mean_dyxh[c]) stored h8; dy_masked (h8, may be NULL) receives dy.
+ * l2i_bn_ws_h8 (host only): *bytes = the float64 workspace of the two reductions (one row of 16 sums per block, added in block order).
+ * All BatchNorm entries: C % 8 == 0, B <= 65535, any HW >= 1; other shapes return L2I_E_UNSUPPORTED, a NULL or misaligned pointer or a workspace
+ * too small L2I_E_ARG; nothing is launched then. */
+int l2i_conv2d_wgrad_h8(float* dw, const void* x, const void* gy, float* ws, int64_t ws_bytes, float out_scale, const float* out_scale_dev, int B, int Cin,
+                        int H, int W, int Cout, int OH, int OW, int K, int stride, int pad, void* stream);
+int l2i_conv2d_wgrad_h8_f16(float* dw, const void* x, const void* gy, float* ws, int64_t ws_bytes, float out_scale, const float* out_scale_dev, int B, int Cin,
+                            int H, int W, int Cout, int OH, int OW, int K, int stride, int pad, void* stream);
+int l2i_conv2d_wgrad_ws_h8(int64_t* bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad);
+int l2i_conv2d_wgrad_ws_h8_f16(int64_t* bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad);
+int l2i_bn_ws_h8(int64_t* bytes, int B, int C, int64_t HW);
+int l2i_bn_ws_h8_f16(int64_t* bytes, int B, int C, int64_t HW);
+int l2i_bn_stats_h8(double* sum, double* sumsq, const void* x, double* ws, int64_t ws_bytes, int B, int C, int64_t HW, void* stream);
+int l2i_bn_stats_h8_f16(double* sum, double* sumsq, const void* x, double* ws, int64_t ws_bytes, int B, int C, int64_t HW, void* stream);
+int l2i_bn_apply_h8(void* y, const void* x, const float* scale, const float* shift, const void* residual, int relu, int B, int C, int64_t HW, void* stream);
+int l2i_bn_apply_h8_f16(void* y, const void* x, const float* scale, const float* shift, const void* residual, int relu, int B, int C, int64_t HW, void* stream);
+int l2i_bn_bwd_reduce_h8(double* sum_dy, double* sum_dyxh, const void* gy, const void* out_mask, const void* x, const float* mean, const float* invstd,
+                         double* ws, int64_t ws_bytes, int B, int C, int64_t HW, void* stream);
+int l2i_bn_bwd_reduce_h8_f16(double* sum_dy, double* sum_dyxh, const void* gy, const void* out_mask, const void* x, const float* mean, const float* invstd,
+                             double* ws, int64_t ws_bytes, int B, int C, int64_t HW, void* stream);
+int l2i_bn_bwd_apply_h8(void* dx, void* dy_masked, const void* gy, const void* out_mask, const void* x, const float* mean, const float* invstd,
+                        const float* gamma, const float* mean_dy, const float* mean_dyxh, int B, int C, int64_t HW, void* stream);
+int l2i_bn_bwd_apply_h8_f16(void* dx, void* dy_masked, const void* gy, const void* out_mask, const void* x, const float* mean, const float* invstd,
+                            const float* gamma, const float* mean_dy, const float* mean_dyxh, int B, int C, int64_t HW, void* stream);
+
 /* ---- [ABI 12, additive] the linear layers of the PGGAN graph's MLP walk (csrc/l2i_walk.hip; WalkMlpZ3, graphs/pggan/transform_base.py:167-188) ------
  * Skinny products on plain fp32 VALU: B rows (any B >= 1, taken in chunks of at most 16) against W in nn.Linear's own [N = out, K = in] layout.
  * l2i_linear_rows_f32:      y[B, N] = epi(x[B, K] W^T + bias[N]).  epi = L2I_LINEAR_NONE; L2I_LINEAR_LRELU: v > 0 ? v : v * slope; L2I_LINEAR_WALK: the

@@ -1,4 +1,4 @@
-"""Python call wrappers for the streaming kernels of the 16-bit path (csrc/l2i_stream_h8.hip, l2i_gram_h8.hip, l2i_pggan_h8.hip; include/l2i.h): bf16 tensors in the
+"""Python call wrappers for the streaming kernels of the 16-bit path (csrc/l2i_stream_h8.hip, l2i_gram_h8.hip, l2i_pggan_h8.hip, l2i_train_h8.hip; include/l2i.h): bf16 tensors in the
 channel-blocked h8 layout [B, C/8, H, W, 8] in, out; fp32 for images, noise, bias, per-sample vectors and reductions.  No autograd here."""
 import ctypes
 
@@ -279,3 +279,87 @@ class ModulatePlan:
             views.append(planes[off * 8:(off + sps * B) * 8].view((B,) + shp))
             off += sps * B
         return views
+
+
+# ---- training on h8 maps (csrc/l2i_train_h8.hip): the weight gradient and training-mode BatchNorm ---------------------------------------------------
+def _twin(name, dtype):
+    return getattr(_lib.load(), name + ('_f16' if dtype is torch.float16 else ''))
+
+
+def wgrad_ws_bytes(b, cin, h, w, cout, oh, ow, k, stride, pad, dtype=None):
+    """l2i_conv2d_wgrad_ws_h8: bytes of workspace l2i_conv2d_wgrad_h8 needs for the shape (host only); raises for a shape it refuses."""
+    n = ctypes.c_int64(0)
+    _lib.check(_twin('l2i_conv2d_wgrad_ws_h8', dtype)(ctypes.byref(n), b, cin, h, w, cout, oh, ow, k, stride, pad), 'l2i_conv2d_wgrad_ws_h8')
+    return n.value
+
+
+def bn_ws_bytes(b, c, hw, dtype=None):
+    """l2i_bn_ws_h8: bytes of the float64 workspace of bn_stats / bn_bwd_reduce for the shape (host only)."""
+    n = ctypes.c_int64(0)
+    _lib.check(_twin('l2i_bn_ws_h8', dtype)(ctypes.byref(n), b, c, hw), 'l2i_bn_ws_h8')
+    return n.value
+
+
+def conv_wgrad(x, gy, k, stride, pad, out=None, ws=None, out_scale=1.0, out_scale_dev=None):
+    """l2i_conv2d_wgrad_h8: dw [Cout, Cin, k, k] fp32 = out_scale * out_scale_dev[0] * sum gy * x over (b, pixel) of h8 maps x, gy; ``out`` is
+    OVERWRITTEN; ``ws`` a float32 workspace of at least wgrad_ws_bytes (allocated when absent)."""
+    b, gi, h, w, _ = x.shape
+    _, go, oh, ow, _ = gy.shape
+    cin, cout = gi * 8, go * 8
+    assert gy.dtype == x.dtype and gy.shape[0] == b
+    if ws is None:
+        ws = torch.empty(wgrad_ws_bytes(b, cin, h, w, cout, oh, ow, k, stride, pad, x.dtype) // 4, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(cout, cin, k, k, device=x.device, dtype=torch.float32)
+    assert out.numel() == cout * cin * k * k
+    _lib.call('l2i_conv2d_wgrad_h8', _lib.fptr(out), _h8(x), _h8(gy), _lib.fptr(ws), ws.numel() * 4, float(out_scale), _lib.fptr(out_scale_dev), b, cin, h, w,
+              cout, oh, ow, k, stride, pad, dtype=x.dtype)
+    return out
+
+
+def _bn_ws(x, ws):
+    b, g8, h, w, _ = x.shape
+    if ws is None:
+        ws = torch.empty(bn_ws_bytes(b, g8 * 8, h * w, x.dtype) // 8, device=x.device, dtype=torch.float64)
+    assert ws.dtype == torch.float64
+    return ws
+
+
+def bn_stats(x, sums, ws=None):
+    """l2i_bn_stats_h8: sums [2, C] float64 (OVERWRITTEN) <- per-channel sum and sum of squares of the stored h8 map x."""
+    b, g8, h, w, _ = x.shape
+    ws = _bn_ws(x, ws)
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (2, g8 * 8)
+    _lib.call('l2i_bn_stats_h8', _lib.ptr(sums[0]), _lib.ptr(sums[1]), _h8(x), _lib.ptr(ws), ws.numel() * 8, b, g8 * 8, h * w, dtype=x.dtype)
+    return sums
+
+
+def bn_apply(x, scale, shift, residual=None, relu=True, out=None):
+    """l2i_bn_apply_h8: relu?(x * scale[c] + shift[c] (+ residual)) on h8 maps."""
+    b, g8, h, w, _ = x.shape
+    out = torch.empty_like(x) if out is None else out
+    assert residual is None or (residual.shape == x.shape and residual.dtype == x.dtype)
+    _lib.call('l2i_bn_apply_h8', _h8(out), _h8(x), _lib.fptr(scale), _lib.fptr(shift), None if residual is None else _h8(residual), int(bool(relu)), b, g8 * 8,
+              h * w, dtype=x.dtype)
+    return out
+
+
+def bn_bwd_reduce(gy, out_mask, x, mean, invstd, sums, ws=None):
+    """l2i_bn_bwd_reduce_h8: sums [2, C] float64 (OVERWRITTEN) <- sum dy, sum dy * xhat with dy = gy * (out_mask > 0) when a mask map is given."""
+    b, g8, h, w, _ = x.shape
+    ws = _bn_ws(x, ws)
+    assert sums.dtype == torch.float64 and tuple(sums.shape) == (2, g8 * 8) and gy.shape == x.shape and gy.dtype == x.dtype
+    _lib.call('l2i_bn_bwd_reduce_h8', _lib.ptr(sums[0]), _lib.ptr(sums[1]), _h8(gy), None if out_mask is None else _h8(out_mask), _h8(x), _lib.fptr(mean),
+              _lib.fptr(invstd), _lib.ptr(ws), ws.numel() * 8, b, g8 * 8, h * w, dtype=x.dtype)
+    return sums
+
+
+def bn_bwd_apply(gy, out_mask, x, mean, invstd, gamma, m_dy, m_dyxh, want_masked=False, out=None, masked=None):
+    """l2i_bn_bwd_apply_h8: (dx, masked dy or None) on h8 maps."""
+    b, g8, h, w, _ = x.shape
+    out = torch.empty_like(x) if out is None else out
+    if want_masked and masked is None:
+        masked = torch.empty_like(x)
+    _lib.call('l2i_bn_bwd_apply_h8', _h8(out), None if masked is None else _h8(masked), _h8(gy), None if out_mask is None else _h8(out_mask), _h8(x),
+              _lib.fptr(mean), _lib.fptr(invstd), _lib.fptr(gamma), _lib.fptr(m_dy), _lib.fptr(m_dyxh), b, g8 * 8, h * w, dtype=x.dtype)
+    return out, masked

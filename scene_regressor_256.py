@@ -14,7 +14,10 @@ def parse_args(argv=None):
     ap.add_argument('--resident', action='store_true', help='resident model: gradient arena, in-place weight repack, BatchNorm algebra and Adam on the device')
     ap.add_argument('--hip_graph', action='store_true', help='replay every full batch from one hipGraph (implies --resident)')
     ap.add_argument('--device_data', action='store_true', help='decode the training split once and keep it on the GPU as uint8')
-    return {k: v for k, v in vars(ap.parse_args(argv)).items() if v not in (None, False)}
+    ap.add_argument('--precision', choices=('f32', 'f16', 'bf16'), help='f16 / bf16: h8 maps and the 16-bit MFMA (fp32 master weights, implies --resident); '
+                                                                        'f16 is the recommended 16-bit type')
+    ap.add_argument('--loss_scale_log2', type=int, help='static loss-scale exponent of the 16-bit path (default: regtrain_scale_for for f16, 0 for bf16)')
+    return {k: v for k, v in vars(ap.parse_args(argv)).items() if v is not None and v is not False}
 
 
 if __name__ == '__main__':

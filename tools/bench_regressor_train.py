@@ -12,6 +12,13 @@ pack — against 6.3 TB/s, with the time per launch.
 
     python tools/bench_regressor_train.py [--out profiles/regressor_train_graph_bench.txt] [--batch 32] [--size 256]
     python tools/bench_regressor_train.py --only resident --steps 3      # one side, a few steps: the run to put under a kernel trace
+
+--precision f32,f16,bf16 (profiles/regressor_train16_bench.txt): the resident fp32 step beside the 16-bit trainer
+(regressor_train.TrainableResNet50H8) of each listed element type, same method; the first three losses of each side; the host's share of a step
+(the time Python and the torch packing ops take to ISSUE it, against the time the GPU takes to run it).  --wgrad_table: every distinct weight-
+gradient shape of ResNet-50 at that batch and size, l2i_conv2d_wgrad_h8 (fp16) against l2i_conv2d_wgrad_f32 on the same maps cast to fp32.
+L2I_LIB=<another build> --precision f32 times the fp32 side on that build (the parent's, for the comparison of the same session).
+--only f16 / bf16 runs a few steps of the 16-bit trainer alone (the run to put under a kernel trace).
 """
 import argparse
 import os
@@ -57,12 +64,126 @@ def png_set(root, n, size):
         f.write('\n'.join(names) + '\n')
 
 
+def wgrad_shapes(size):
+    """Every distinct (k, stride, pad, cin, cout, input side) the h8 weight-gradient kernel runs in one step of ResNet-50 on ``size``^2 images."""
+    from latent2im_amd.specs import RESNET50_LAYERS
+    out, inpl, hw = [], 64, size // 4
+    for planes, blocks, stride in RESNET50_LAYERS:
+        for b in range(blocks):
+            s = stride if b == 0 else 1
+            rows = [(1, 1, 0, inpl, planes, hw), (3, s, 1, planes, planes, hw), (1, 1, 0, planes, 4 * planes, hw // s)]
+            if b == 0:
+                rows.append((1, s, 0, inpl, 4 * planes, hw))
+            for r in rows:
+                if r not in out:
+                    out.append(r)
+            inpl, hw = 4 * planes, hw // s
+    return out
+
+
+def wgrad_table(B, S, say):
+    from latent2im_amd import _lib
+    from latent2im_amd import kernels16 as K16
+    say('weight gradient per shape, batch %d at %d^2: l2i_conv2d_wgrad_h8 (fp16 maps) against l2i_conv2d_wgrad_f32 (the same maps cast to fp32); %s' % (B, S, torch.cuda.get_device_name(0)))
+    say('  %-34s %10s %9s %10s %9s %7s  %s' % ('k s  cin -> cout, map', 'h8 ms', 'TFLOP/s', 'f32 ms', 'TFLOP/s', 'f32/h8', 'slices x tiles x taps'))
+    g = torch.Generator(device='cuda').manual_seed(1)
+    slower = []
+    for k, s, pad, cin, cout, h in wgrad_shapes(S):
+        oh = (h + 2 * pad - k) // s + 1
+        x = torch.randn(B, cin // 8, h, h, 8, device='cuda', generator=g).to(torch.float16)
+        gy = (torch.randn(B, cout // 8, oh, oh, 8, device='cuda', generator=g) * 0.1).to(torch.float16)
+        x32, gy32 = K16.cast_from_h8(x), K16.cast_from_h8(gy)
+        ws = torch.empty(K16.wgrad_ws_bytes(B, cin, h, h, cout, oh, oh, k, s, pad, x.dtype) // 4, device='cuda')
+        dw, dw32 = torch.empty(cout, cin, k, k, device='cuda'), torch.zeros(cout, cin, k, k, device='cuda')
+        t16 = timed(lambda: K16.conv_wgrad(x, gy, k, s, pad, out=dw, ws=ws))
+        t32 = timed(lambda: _lib.call('l2i_conv2d_wgrad_f32', _lib.fptr(dw32), _lib.fptr(x32), _lib.fptr(gy32), B, cin, h, h, cout, oh, oh, k, k, s, pad, pad))
+        flop = 2.0 * B * oh * oh * cin * cout * k * k
+        tiles = ((cin + 63) // 64) * ((cout + 63) // 64)
+        say('  %dx%d s%d %4d -> %4d, %3d^2 -> %3d^2 %10.3f %9.1f %10.3f %9.1f %7.1f  %d x %d x %d'
+            % (k, k, s, cin, cout, h, oh, t16 * 1e3, flop / t16 / 1e12, t32 * 1e3, flop / t32 / 1e12, t32 / t16, ws.numel() // (4096 * tiles * k * k), tiles, k * k))
+        if t16 > t32:
+            slower.append((k, s, cin, cout, h))
+    say('  rows on which the new kernel is slower: %s' % (slower or 'none'))
+
+
+def precision_bench(precisions, B, S, st, data, label, say):
+    """The resident fp32 step and the 16-bit trainer of each listed element type: losses, step times, the host's share."""
+    import time
+    from latent2im_amd import _lib
+    from latent2im_amd import regressor_train as RT
+    say('regressor training step, batch %d at %d^2, sides %s; %s; library %s' % (B, S, ', '.join(precisions), torch.cuda.get_device_name(0), os.path.basename(os.path.dirname(_lib.LIB_PATH)) or '.'))
+    sides = {}
+    for p in precisions:
+        m = RT.make_model(st, precision=p, resident=True, **({} if p == 'f32' else dict(image_size=S, batch=B)))
+        o = RT.make_optimizer(m, guarded=True)
+        sides[p] = (m, o, (lambda m=m, o=o: RT.train_step_resident(m, o, data, label)))
+    for p, (m, o, fn) in sides.items():
+        say('  first three losses, %-5s %s%s' % (p, ' '.join('%.6f' % float(fn()) for _ in range(3)), '' if p == 'f32' else '   (static scale 2^%d)' % m.loss_scale_log2))
+    runs = {p: [] for p in sides}
+    for _ in range(3):
+        for p in sides:
+            runs[p].append(timed(sides[p][2]))
+    say('  step time, median of 20 after 5 warm-up calls, three alternating runs (ms):')
+    for p, v in runs.items():
+        say('    %-5s %s   median %.1f ms  = %.1f images/s' % (p, ' '.join('%7.1f' % (t * 1e3) for t in v), statistics.median(v) * 1e3, B / statistics.median(v)))
+    med = {p: statistics.median(v) for p, v in runs.items()}
+    say('  largest run-to-run spread of a side: %.1f %%' % (100 * max((max(v) - min(v)) / statistics.median(v) for v in runs.values())))
+    for p in sides:
+        if p != 'f32' and 'f32' in med:
+            say('  f32 resident / %-5s %.2fx' % (p, med['f32'] / med[p]))
+    say('  host share: time to ISSUE one step from Python (no synchronisation inside; median of 10) against the GPU time above')
+    for p, (m, o, fn) in sides.items():
+        hs, rp = [], []
+        for _ in range(10):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            hs.append(time.perf_counter() - t0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.replan()
+            rp.append(time.perf_counter() - t0)
+        say('    %-5s issue %.1f ms of which replan() %.1f ms; GPU %.1f ms: %s' % (p, statistics.median(hs) * 1e3, statistics.median(rp) * 1e3, med[p] * 1e3,
+                                                                                    'HOST-BOUND' if statistics.median(hs) > 0.9 * med[p] else 'GPU-bound'))
+        if p != 'f32':
+            say('    %-5s scaler %s' % (p, o.scaler.stats()))
+
+
+def ranges(say):
+    """The largest stored map per stage of one fp16 step (nets16.RangeMonitor / l2i_range_stats on the h8 maps themselves) at the two shapes the
+    static exponent was chosen on: what regtrain_scale_for puts near 2^5."""
+    from latent2im_amd import nets16, synth
+    from latent2im_amd import regressor_train as RT
+    st = synth.resnet50_state(seed=300)
+    say('stored ranges of one fp16 regressor step (synthetic weights, seed 300; data randn * 0.5, RandomState(5)); gradient maps are stored x 2^e')
+    for B, S in ((8, 128), (32, 256)):
+        rs = np.random.RandomState(5)
+        data, label = torch.from_numpy(rs.randn(B, 3, S, S).astype(np.float32) * 0.5).cuda(), torch.from_numpy(rs.rand(B, 40).astype(np.float32)).cuda()
+        m = RT.TrainableResNet50H8(st, device='cuda', precision='f16', image_size=S, batch=B)
+        o = RT.make_optimizer(m, guarded=True)
+        m.monitor = nets16.RangeMonitor('cuda')
+        RT.train_step_resident(m, o, data, label)
+        rows = m.monitor.read()
+        e = m.loss_scale_log2
+        say('  batch %d at %d^2, e = %d (regtrain_scale_for):' % (B, S, e))
+        for tag in sorted(rows):
+            r = rows[tag]
+            say('    %-12s max 2^%6.2f  median octave 2^%d  below-normal share %.3g  non-finite %d' % (tag, r['max_log2'], r['median_octave'], r['below_normal'], r['nonfinite']))
+        gmax = max(r['max_log2'] for t, r in rows.items() if t.startswith('T.g.'))
+        amax = max(r['max_log2'] for t, r in rows.items() if t.startswith('T.fwd.'))
+        say('    largest stored gradient 2^%.2f = true 2^%.2f -> the rule 5 - round(log2 true max) gives e = %d; largest stored activation %.1f'
+            % (gmax, gmax - e, 5 - int(round(gmax - e)), 2.0 ** amax))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--ranges', action='store_true', help='stored ranges of one fp16 step at 8 x 128^2 and 32 x 256^2 (the static exponent rule)')
+    ap.add_argument('--precision', help='comma list of f32, f16, bf16: the 16-bit comparison instead of the fp32 sides')
+    ap.add_argument('--wgrad_table', action='store_true', help='the per-shape weight-gradient table')
     ap.add_argument('--out')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--size', type=int, default=256)
-    ap.add_argument('--only', choices=('eager', 'resident', 'replayed'))
+    ap.add_argument('--only', choices=('eager', 'resident', 'replayed', 'f16', 'bf16'))
     ap.add_argument('--steps', type=int, default=3)
     a = ap.parse_args()
     from latent2im_amd import capture, synth
@@ -79,7 +200,25 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
+    def finish():
+        if a.out:
+            with open(a.out, 'a' if (a.precision or a.wgrad_table or a.ranges) else 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+
+    if a.precision or a.wgrad_table or a.ranges:
+        if a.ranges:
+            ranges(say)
+        if a.precision:
+            precision_bench(a.precision.split(','), B, S, st, data, label, say)
+        if a.wgrad_table:
+            wgrad_table(B, S, say)
+        return finish()
+
     def make(side):
+        if side in ('f16', 'bf16'):
+            m = RT.TrainableResNet50H8(st, device='cuda', precision=side, image_size=S, batch=B)
+            o = RT.make_optimizer(m, guarded=True)
+            return m, (lambda: RT.train_step_resident(m, o, data, label))
         if side == 'eager':
             m = RT.TrainableResNet50(st, device='cuda')
             o = RT.make_optimizer(m)
@@ -153,9 +292,7 @@ def main():
         model.replan()
     t = timed(g.replay)
     say('  the same replayed from a graph: %.3f ms = %.0f GB/s (%.1f %% of 6.3 TB/s)' % (t * 1e3, byt / t / 1e9, 100 * byt / t / HBM))
-    if a.out:
-        with open(a.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    finish()
 
 
 if __name__ == '__main__':
