@@ -759,13 +759,20 @@ class ImgConvH8:
     """[r5] An image-side convolution of the 16-bit path (csrc/l2i_img_h8.hip): fp32 NCHW image in, h8 map out; forward only (the input gradients
     land on the fp32 image through the generic kernels: H8Conv.dgrad(out_f32=True), FrozenConv2d.dgrad_h8in)."""
 
-    def __init__(self, weight, stride=1, padding=0, device='cuda'):
+    def __init__(self, weight, stride=1, padding=0, device='cuda', dtype=None):
         w = _weight_f32(weight)
         self.cout, self.cin, self.k, _ = w.shape
         assert (self.k, stride) in ((1, 1), (3, 1), (7, 2)) and self.cout % 8 == 0, (self.k, stride, self.cout)
-        self.stride, self.padding = stride, padding
-        self.dtype = h8_dtype()
-        self.planes = pack_weight_img_h8(w).to(device)
+        self.stride, self.padding, self.device = stride, padding, device
+        self.dtype = dtype or h8_dtype()
+        self.repack(w)
+
+    def repack(self, weight):
+        """Rebuild ``planes`` from a weight of the same shape, as ``__init__`` does: packed on the host (9408 weights for the 7x7 stem) and moved.
+        Torch ops that allocate: not in place, not capture-safe."""
+        w = _weight_f32(weight)
+        assert tuple(w.shape) == (self.cout, self.cin, self.k, self.k), tuple(w.shape)
+        self.planes = pack_weight_img_h8(w, dtype=self.dtype).to(self.device)
 
     def out_hw(self, h, w):
         return (h + 2 * self.padding - self.k) // self.stride + 1, (w + 2 * self.padding - self.k) // self.stride + 1
@@ -787,19 +794,24 @@ class H8Conv:
     TRANSPOSED conv (``transposed=True``: y[co, 2i+k-pad] += x[ci, i] w[co, ci, k], as FrozenConv2d).  Forward and input-gradient both run on
     l2i_conv2d_h8 / l2i_conv_transpose2d_h8; no weight gradients (the walk is the only trainable tensor)."""
 
-    def __init__(self, weight, stride=1, padding=0, transposed=False, device='cuda', cin_pad=32):
+    def __init__(self, weight, stride=1, padding=0, transposed=False, device='cuda', cin_pad=32, dtype=None):
         w = _weight_f32(weight)
         self.cout, self.cin, self.k, _ = w.shape
-        self.stride, self.padding, self.transposed, self.device = stride, padding, transposed, device
+        self.stride, self.padding, self.transposed, self.device, self.cin_pad = stride, padding, transposed, device, cin_pad
         assert cin_pad == 32 or (cin_pad == 16 and self.k == 3 and stride == 1 and not transposed), 'a 16-channel chunk exists for 3x3 stride-1 layers only'
         self.cinp, self.coutp_in = (self.cin + cin_pad - 1) // cin_pad * cin_pad, (self.cout + 31) // 32 * 32
-        self.dtype = h8_dtype()                                       # element type of the weight planes: the maps it is called with must have it
-        wt = w.transpose(0, 1).contiguous()
-        self.fwd_planes = pack_weight_h8(w, cin_pad).to(device)
-        if transposed or stride == 2:
-            self.bwd_planes = pack_weight_h8(wt).to(device)          # transposed fwd: dx = corr_s2(gy, wt); stride-2 fwd: dx = transposed(gy, wt)
-        else:
-            self.bwd_planes = pack_weight_h8(torch.flip(wt, [2, 3])).to(device)
+        self.dtype = dtype or h8_dtype()                              # element type of the weight planes: the maps it is called with must have it
+        self.repack(w)                                                # (packed on the host)
+        self.fwd_planes, self.bwd_planes = self.fwd_planes.to(device), self.bwd_planes.to(device)
+
+    def repack(self, weight):
+        """Rebuild ``fwd_planes`` and ``bwd_planes`` from a weight of the same shape with the packing of ``__init__``, on the device the weight
+        lives on (a trainer's master weight after an optimiser step).  Torch ops that allocate: not in place, not capture-safe."""
+        assert tuple(weight.shape) == (self.cout, self.cin, self.k, self.k), tuple(weight.shape)
+        wt = weight.transpose(0, 1).contiguous()
+        self.fwd_planes = pack_weight_h8(weight, self.cin_pad, dtype=self.dtype)
+        # transposed fwd: dx = corr_s2(gy, wt); stride-2 fwd: dx = transposed(gy, wt); stride 1: the correlation with the flipped taps
+        self.bwd_planes = pack_weight_h8(wt if self.transposed or self.stride == 2 else torch.flip(wt, [2, 3]), dtype=self.dtype)
 
     def out_hw(self, h, w):
         if self.transposed:

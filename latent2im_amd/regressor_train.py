@@ -8,14 +8,19 @@ GPU after every optimiser step), the weight gradients ``l2i_conv2d_wgrad_f32`` a
 (csrc/l2i_train.hip).  torch supplies tensors, the [C]-sized statistics algebra, the 2048x40 fc GEMMs and ``torch.optim.Adam`` (the
 reference uses it too).  No autograd graph is built: the backward is scheduled by hand like the frozen networks' input-gradients.
 
-Opt-in (``TrainableResNet50(resident=True)``, ``make_optimizer(guarded=True)``, ``DeviceDataset``, ``main(resident / hip_graph / device_data)``):
-the same step with nothing packed, allocated or counted on the host between two batches — packs rewritten in place (csrc/l2i_repack.hip), the
-[C]-sized algebra as kernels, one gradient arena, optim.GuardedAdam, batches gathered from uint8 crops on the device — which
-capture.CapturedRegressorStep records into one hipGraph.
-
-``TrainableResNet50H8`` (``main(precision='f16' / 'bf16')``): the resident step on 16-bit h8 maps — conv.H8Conv / ImgConvH8 forward
-and input gradients, ``l2i_conv2d_wgrad_h8`` and the h8 BatchNorm kernels of csrc/l2i_train_h8.hip, fp32 master weights, a static x dynamic loss scale
-(optim.LossScaler) — with the fp32 model's interface and checkpoints.
+ONE schedule, three layer families.  ``TrainableResNet50.forward`` / ``backward`` / ``block_backward`` / ``stem_backward`` are the only walk over
+the network; what a step launches is decided by the layer objects ``_layer_types()`` selects — all with one interface (conv: ``plan``, ``forward``,
+``dgrad(gy, in_hw, residual=None)``, ``wgrad(x, gy)``; BatchNorm: ``forward``, ``backward``) — by the module the pool and the average come from
+(``maps``: kernels or kernels16) and by four small hooks (``_input``, ``_head_grad``, ``_end_backward``, ``_probe``):
+  _Conv / _BN                   the default eager fp32 step (``train_step``): 53 FrozenConv2d rebuilt per step, the [C]-sized algebra in torch;
+  _ResidentConv / _ResidentBN   opt-in (``TrainableResNet50(resident=True)``, ``make_optimizer(guarded=True)``, ``DeviceDataset``, ``main(resident /
+                                hip_graph / device_data)``): nothing packed, allocated or counted on the host between two batches — packs rewritten in
+                                place (csrc/l2i_repack.hip), the [C]-sized algebra as kernels, one gradient arena, optim.GuardedAdam, batches gathered
+                                from uint8 crops on the device — which capture.CapturedRegressorStep records into one hipGraph (DESIGN.md section 5.2);
+  _H8StemConv / _H8Conv / _H8BN ``TrainableResNet50H8`` (``main(precision='f16' / 'bf16')``): the resident step on 16-bit h8
+                                maps — conv.ImgConvH8 / H8Conv forward and input gradients (planes rebuilt by their ``repack``), ``l2i_conv2d_wgrad_h8``
+                                and the h8 BatchNorm kernels of csrc/l2i_train_h8.hip, fp32 master weights, a static x dynamic loss scale
+                                (optim.LossScaler) — with the fp32 model's interface and checkpoints.
 """
 import csv
 import os
@@ -26,6 +31,7 @@ import torch
 from . import _lib
 from . import conv as C
 from . import kernels as K
+from . import kernels16 as K16
 from .specs import RESNET50_LAYERS
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -104,8 +110,11 @@ class _Conv:
     def forward(self, x):
         return self.fc.forward(x)
 
-    def dgrad(self, gy, in_hw):
-        return self.fc.dgrad(gy, in_hw)
+    def dgrad(self, gy, in_hw, residual=None):
+        """dL/dx (+ ``residual``).  The sum is one axpby with alpha = beta = 1: a + b and b + a are the same bits, so the operand order is not
+        special-cased (a downsample block hands conv1's gradient in as the residual of the downsample conv's)."""
+        g = self.fc.dgrad(gy, in_hw)
+        return g if residual is None else K.axpby(g, residual)
 
     def wgrad(self, x, gy):
         return conv_wgrad(x, gy, self.k, self.stride, self.padding)
@@ -122,14 +131,23 @@ class _ResidentBN(_BN):
         self.mean, self.invstd, self.scale, self.shift, self.m_dy, self.m_dyxh = small
         self.g_weight, self.g_bias = g_weight, g_bias
 
-    def forward(self, x, residual=None, relu=True):
-        b, c, h, w = x.shape
+    def _finalize(self, n, c):
+        """The forward sums of ``n`` values per channel -> mean, invstd, scale, shift (and the running statistics)."""
         track = self.owner.track_stats
-        _lib.call('l2i_bn_stats_f32', _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(x), b, c, h * w)
         _lib.call('l2i_bn_finalize_f32', _lib.fptr(self.mean), _lib.fptr(self.invstd), _lib.fptr(self.scale), _lib.fptr(self.shift),
                   _lib.fptr(self.running_mean) if track else None, _lib.fptr(self.running_var) if track else None,
                   _lib.ptr(self.num_batches_tracked) if track else None, _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(self.weight),
-                  _lib.fptr(self.bias), b * h * w, c, BN_EPS, BN_MOMENTUM)
+                  _lib.fptr(self.bias), n, c, BN_EPS, BN_MOMENTUM)
+
+    def _bwd_finalize(self, n, c):
+        """The backward sums -> the parameter gradients (in the arena) and the two means the apply pass subtracts."""
+        _lib.call('l2i_bn_bwd_finalize_f32', _lib.fptr(self.g_bias), _lib.fptr(self.g_weight), _lib.fptr(self.m_dy), _lib.fptr(self.m_dyxh),
+                  _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), n, c)
+
+    def forward(self, x, residual=None, relu=True):
+        b, c, h, w = x.shape
+        _lib.call('l2i_bn_stats_f32', _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(x), b, c, h * w)
+        self._finalize(b * h * w, c)
         y = torch.empty_like(x)
         _lib.call('l2i_bn_apply_f32', _lib.fptr(y), _lib.fptr(x), _lib.fptr(self.scale), _lib.fptr(self.shift), _lib.fptr(residual), int(relu), b, c, h * w)
         return y, (x, self.mean, self.invstd)
@@ -139,8 +157,7 @@ class _ResidentBN(_BN):
         b, c, h, w = x.shape
         _lib.call('l2i_bn_bwd_reduce_f32', _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
                   _lib.fptr(invstd), b, c, h * w)
-        _lib.call('l2i_bn_bwd_finalize_f32', _lib.fptr(self.g_bias), _lib.fptr(self.g_weight), _lib.fptr(self.m_dy), _lib.fptr(self.m_dyxh),
-                  _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), b * h * w, c)
+        self._bwd_finalize(b * h * w, c)
         dx = torch.empty_like(x)
         gm = torch.empty_like(x) if want_masked else None
         _lib.call('l2i_bn_bwd_apply_f32', _lib.fptr(dx), _lib.fptr(gm), _lib.fptr(gy), _lib.fptr(out_mask), _lib.fptr(x), _lib.fptr(mean),
@@ -151,6 +168,9 @@ class _ResidentBN(_BN):
 class _ResidentConv(_Conv):
     """_Conv of a resident model: packed once, then rewritten in place from the weight (FrozenConv2d.repack_); the weight gradient accumulates
     straight into its view of the model's gradient arena (zeroed once per step)."""
+
+    def attach(self, owner, g_weight):
+        self.owner, self.g_weight = owner, g_weight
 
     def plan(self):
         if self.fc is None:
@@ -235,7 +255,7 @@ class TrainableResNet50:
                       [small[6 * o + i * c:6 * o + (i + 1) * c] for i in range(6)], self.grads[bn.name + '.weight'], self.grads[bn.name + '.bias'])
             o += c
         for cv in self._convs():
-            cv.g_weight = self.grads[cv.name + '.weight']
+            cv.attach(self, self.grads[cv.name + '.weight'])
 
     def zero_grad(self):
         """Resident: one memset over every parameter gradient."""
@@ -283,85 +303,102 @@ class TrainableResNet50:
                 if blk[c] is not None:
                     blk[c].plan()
 
-    # -- forward / backward ----------------------------------------------------------------------------------------------------
+    # -- forward / backward: the one schedule of every flavour ------------------------------------------------------------------
+    maps = K                 # the module of the pool and the average: the maps are fp32 NCHW here
+    monitor = None           # (TrainableResNet50H8 can hold a range monitor; nothing listens here)
+
+    def _input(self, img):
+        return img.detach().contiguous()
+
+    def _head_grad(self, g_preds, last):
+        """dL/d preds [B,40] -> dL/d(last block's output) through the fc and the average pool."""
+        b, c, h, w = last
+        return (torch.mm(g_preds, self.fc_w) * (1.0 / (h * w))).reshape(b, c, 1, 1).expand(b, c, h, w).contiguous()
+
+    def _end_backward(self):
+        pass
+
+    def _probe(self, tag, *maps):
+        pass
+
     def forward(self, img, keep=True):
         """[B,3,H,W] -> [B,40] in training mode; ``keep``: save what ``backward`` needs."""
-        x = img.detach().contiguous()
+        x = self._input(img)
         if self.resident:
             self.fwd_sums.zero_()                                   # every BatchNorm's sums of this pass: one memset
         z0 = self.stem.forward(x)
         a0, s0 = self.stem_bn.forward(z0)
-        p0, idx0 = K.maxpool2d_fwd(a0, 3, 2, 1)
+        p0, idx0 = self.maps.maxpool2d_fwd(a0, 3, 2, 1)
+        self._probe('T.fwd.stem', z0, a0)
         saved = dict(img=x, s0=s0, a0=a0, idx0=idx0, blocks=[])
         cur = p0
         for blk in self.blocks:
-            z1 = blk['c1'].forward(cur)
-            y1, s1 = blk['b1'].forward(z1)
-            z2 = blk['c2'].forward(y1)
-            y2, s2 = blk['b2'].forward(z2)
+            y1, s1 = blk['b1'].forward(blk['c1'].forward(cur))
+            y2, s2 = blk['b2'].forward(blk['c2'].forward(y1))
             z3 = blk['c3'].forward(y2)
             if blk['cd'] is not None:
-                zd = blk['cd'].forward(cur)
-                idt, sd = blk['bd'].forward(zd, relu=False)
+                idt, sd = blk['bd'].forward(blk['cd'].forward(cur), relu=False)
             else:
                 idt, sd = cur, None
             out, s3 = blk['b3'].forward(z3, residual=idt, relu=True)
-            saved['blocks'].append((cur, y1, s1, y2, s2, s3, sd, out))
+            self._probe('T.fwd.' + blk['c1'].name.split('.')[0], s1[0], y1, s2[0], y2, z3, out)
+            if keep:
+                saved['blocks'].append((cur, y1, s1, y2, s2, s3, sd, out))
             cur = out
-        b, c, h, w = cur.shape
-        feat = K.dot_reduce(cur) * (1.0 / (h * w))
-        self._saved = dict(saved, feat=feat, last=(b, c, h, w)) if keep else None
+        feat = self.maps.dot_reduce(cur) * (1.0 / (cur.shape[2] * cur.shape[3]))
+        self._saved = dict(saved, feat=feat, last=tuple(cur.shape[:4])) if keep else None
         return torch.addmm(self.fc_b, feat, self.fc_w.t())
 
     __call__ = forward
 
     def backward(self, g_preds):
-        """dL/d preds [B,40] -> {parameter name: gradient} (and nothing else: the image gets no gradient here)."""
+        """dL/d preds [B,40] -> {parameter name: gradient} (resident: the views of the arena, which the caller zeroed — the fp32 weight
+        gradients accumulate) and nothing else: the image gets no gradient here."""
         sv = self._saved
-        if self.resident:                                          # into the gradient arena (zeroed by the caller: the weight gradients accumulate)
+        if self.resident:
             self.bwd_sums.zero_()
-            grads = {'fc.weight': torch.mm(g_preds.t(), sv['feat'], out=self.grads['fc.weight']),
-                     'fc.bias': torch.sum(g_preds, 0, out=self.grads['fc.bias'])}
+            grads = self.grads
+            torch.mm(g_preds.t(), sv['feat'], out=grads['fc.weight'])
+            torch.sum(g_preds, 0, out=grads['fc.bias'])
         else:
             grads = {'fc.weight': torch.mm(g_preds.t(), sv['feat']), 'fc.bias': g_preds.sum(0)}
-        b, c, h, w = sv['last']
-        g = (torch.mm(g_preds, self.fc_w) * (1.0 / (h * w))).reshape(b, c, 1, 1).expand(b, c, h, w).contiguous()
+        g = self._head_grad(g_preds, sv['last'])
+        self._probe('T.g.head', g)
         for blk, saved in zip(reversed(self.blocks), reversed(sv['blocks'])):
             g = self.block_backward(blk, saved, g, grads)
         self.stem_backward(sv, g, grads)
+        self._end_backward()
         self._saved = None
         return grads
 
-    @staticmethod
-    def block_backward(blk, saved, g, grads):
+    def block_backward(self, blk, saved, g, grads):
         """One bottleneck block: g = dL/d(block output) -> dL/d(block input); parameter gradients are added to ``grads`` by name."""
         cur, y1, s1, y2, s2, s3, sd, out = saved
-        in_hw = (cur.shape[2], cur.shape[3])
-        # out = relu(bn3(z3) + idt): the masked gradient feeds bn3 and the identity branch
+        hw = lambda t: (t.shape[2], t.shape[3])
+        # out = relu(bn3(z3) + idt): the masked gradient gm feeds bn3 and the identity branch
         g_z3, dw, db, gm = blk['b3'].backward(g, s3, out_mask=out, want_masked=True)
         grads[blk['b3'].name + '.weight'], grads[blk['b3'].name + '.bias'] = dw, db
         grads[blk['c3'].name + '.weight'] = blk['c3'].wgrad(y2, g_z3)
-        g_y2 = blk['c3'].dgrad(g_z3, (y2.shape[2], y2.shape[3]))
-        g_z2, dw, db, _ = blk['b2'].backward(g_y2, s2, out_mask=y2)
+        g_z2, dw, db, _ = blk['b2'].backward(blk['c3'].dgrad(g_z3, hw(y2)), s2, out_mask=y2)
         grads[blk['b2'].name + '.weight'], grads[blk['b2'].name + '.bias'] = dw, db
         grads[blk['c2'].name + '.weight'] = blk['c2'].wgrad(y1, g_z2)
-        g_y1 = blk['c2'].dgrad(g_z2, (y1.shape[2], y1.shape[3]))
-        g_z1, dw, db, _ = blk['b1'].backward(g_y1, s1, out_mask=y1)
+        g_z1, dw, db, _ = blk['b1'].backward(blk['c2'].dgrad(g_z2, hw(y1)), s1, out_mask=y1)
         grads[blk['b1'].name + '.weight'], grads[blk['b1'].name + '.bias'] = dw, db
         grads[blk['c1'].name + '.weight'] = blk['c1'].wgrad(cur, g_z1)
-        g_in = blk['c1'].dgrad(g_z1, in_hw)
-        if blk['cd'] is not None:
-            g_zd, dw, db, _ = blk['bd'].backward(gm, sd)
-            grads[blk['bd'].name + '.weight'], grads[blk['bd'].name + '.bias'] = dw, db
-            grads[blk['cd'].name + '.weight'] = blk['cd'].wgrad(cur, g_zd)
-            return K.axpby(g_in, blk['cd'].dgrad(g_zd, in_hw))
-        return K.axpby(g_in, gm)
+        self._probe('T.g.' + blk['c1'].name.split('.')[0], g_z3, g_z2, g_z1)
+        if blk['cd'] is None:
+            return blk['c1'].dgrad(g_z1, hw(cur), residual=gm)      # the identity gradient rides on the conv's residual operand
+        g_zd, dw, db, _ = blk['bd'].backward(gm, sd)
+        grads[blk['bd'].name + '.weight'], grads[blk['bd'].name + '.bias'] = dw, db
+        grads[blk['cd'].name + '.weight'] = blk['cd'].wgrad(cur, g_zd)
+        return blk['cd'].dgrad(g_zd, hw(cur), residual=blk['c1'].dgrad(g_z1, hw(cur)))
 
     def stem_backward(self, sv, g, grads):
         """maxpool <- relu <- bn1 <- conv1: g = dL/d(pooled map); the image itself gets no gradient."""
         a0 = sv['a0']
-        g_a0 = K.maxpool2d_bwd(g, sv['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
+        g_a0 = self.maps.maxpool2d_bwd(g, sv['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
         g_z0, dw, db, _ = self.stem_bn.backward(g_a0, sv['s0'], out_mask=a0)
+        self._probe('T.g.stem', g_a0, g_z0)
         grads['bn1.weight'], grads['bn1.bias'] = dw, db
         grads['conv1.weight'] = self.stem.wgrad(sv['img'], g_z0)
 
@@ -382,95 +419,81 @@ def regtrain_scale_for(image_size, batch):
     return 15 + (int(round(math.log2(max(batch, 1)))) - 3) + 2 * (int(round(math.log2(image_size))) - 7)
 
 
-class _precision:
-    """conv.PRECISION = ``elem`` while a 16-bit conv object is built (it reads its element type there once and keeps it)."""
-
-    def __init__(self, elem):
-        self.elem = elem
-
-    def __enter__(self):
-        self.old, C.PRECISION = C.PRECISION, self.elem
-
-    def __exit__(self, *exc):
-        C.PRECISION = self.old
+def _in_scaled_tail(name, t):
+    """Is the gradient of this parameter written in SCALED units (conv1.weight and the BatchNorm parameters of the 16-bit trainer)?"""
+    return name == 'conv1.weight' or t.dim() == 1 and not name.startswith('fc.')
 
 
 class _H8BN(_ResidentBN):
     """_ResidentBN on h8 maps: the two reductions and the two apply passes are csrc/l2i_train_h8.hip's, the [C]-sized algebra between them is the
-    fp32 model's (l2i_bn_finalize_f32 / l2i_bn_bwd_finalize_f32).  The parameter gradients land in the arena in SCALED units (the gradient
-    maps carry the loss scale); the owner unscales them with one multiply after the backward."""
+    fp32 model's (_finalize / _bwd_finalize).  The parameter gradients land in the arena in SCALED units (the gradient maps carry the loss
+    scale); the owner unscales them with one multiply after the backward."""
 
     def forward(self, x, residual=None, relu=True):
-        from . import kernels16 as K16
         b, g8, h, w, _ = x.shape
-        c, track = g8 * 8, self.owner.track_stats
         K16.bn_stats(x, self.fs, ws=self.owner.bn_ws(x))
-        _lib.call('l2i_bn_finalize_f32', _lib.fptr(self.mean), _lib.fptr(self.invstd), _lib.fptr(self.scale), _lib.fptr(self.shift),
-                  _lib.fptr(self.running_mean) if track else None, _lib.fptr(self.running_var) if track else None,
-                  _lib.ptr(self.num_batches_tracked) if track else None, _lib.ptr(self.fs[0]), _lib.ptr(self.fs[1]), _lib.fptr(self.weight),
-                  _lib.fptr(self.bias), b * h * w, c, BN_EPS, BN_MOMENTUM)
+        self._finalize(b * h * w, g8 * 8)
         return K16.bn_apply(x, self.scale, self.shift, residual=residual, relu=relu), (x, self.mean, self.invstd)
 
     def backward(self, gy, saved, out_mask=None, want_masked=False):
-        from . import kernels16 as K16
         x, mean, invstd = saved
         b, g8, h, w, _ = x.shape
         K16.bn_bwd_reduce(gy, out_mask, x, mean, invstd, self.bs, ws=self.owner.bn_ws(x))
-        _lib.call('l2i_bn_bwd_finalize_f32', _lib.fptr(self.g_bias), _lib.fptr(self.g_weight), _lib.fptr(self.m_dy), _lib.fptr(self.m_dyxh),
-                  _lib.ptr(self.bs[0]), _lib.ptr(self.bs[1]), b * h * w, g8 * 8)
+        self._bwd_finalize(b * h * w, g8 * 8)
         dx, gm = K16.bn_bwd_apply(gy, out_mask, x, mean, invstd, self.weight, self.m_dy, self.m_dyxh, want_masked=want_masked)
         return dx, self.g_weight, self.g_bias, gm
 
 
-class _H8Conv(_Conv):
-    """A trainable bias-free convolution of the 16-bit trainer: fp32 master weight; ``plan()`` rebuilds the forward and input-gradient planes of a
-    conv.H8Conv from it with conv.pack_weight_h8 ON THE DEVICE (torch ops; the device-side repack kernel is a follow-up); the weight gradient is
-    l2i_conv2d_wgrad_h8 straight into the gradient arena, overwritten and already unscaled."""
+class _H8Conv(_ResidentConv):
+    """A trainable bias-free convolution of the 16-bit trainer: fp32 master weight; ``plan()`` builds a conv.H8Conv of the element type once and
+    then has it repack its planes from the weight ON THE DEVICE (H8Conv.repack: torch ops; the device-side repack kernel is a follow-up); the
+    weight gradient is l2i_conv2d_wgrad_h8 straight into the gradient arena, overwritten and already unscaled."""
 
     def __init__(self, P, name, stride, padding, device, elem='f16'):
         super().__init__(P, name, stride, padding, device)
-        self.elem, self.h8 = elem, None
+        self.dtype, self.h8 = H8_DTYPES[elem], None
 
     def plan(self):
-        dt = H8_DTYPES[self.elem]
         w = self.weight.detach()
         if self.h8 is None:
-            with _precision(self.elem):
-                self.h8 = C.H8Conv(w, stride=self.stride, padding=self.padding, device=w.device)
-            return
-        wt = w.transpose(0, 1).contiguous()
-        self.h8.fwd_planes = C.pack_weight_h8(w, 32, dtype=dt)
-        self.h8.bwd_planes = C.pack_weight_h8(wt if self.stride == 2 else torch.flip(wt, [2, 3]), dtype=dt)
+            self.h8 = C.H8Conv(w, stride=self.stride, padding=self.padding, device=w.device, dtype=self.dtype)
+        else:
+            self.h8.repack(w)
 
     def forward(self, x):
         return self.h8.forward(x)
 
-    def dgrad(self, gy, in_hw, **kw):
-        return self.h8.dgrad(gy, in_hw, **kw)
+    def dgrad(self, gy, in_hw, residual=None):
+        if residual is not None and self.stride == 2:              # the strided 1x1 downsample: compact conv + zero insertion onto the residual
+            return K16.add_zero_insert(residual, self.h8.dgrad_compact(gy))
+        return self.h8.dgrad(gy, in_hw, residual=residual)          # stride 1: the residual rides on the conv's own operand
 
-    def wgrad(self, x, gy, owner):
-        from . import kernels16 as K16
-        return K16.conv_wgrad(x, gy, self.k, self.stride, self.padding, out=self.g_weight, ws=owner.wgrad_ws(x, gy, self), out_scale=owner.inv_static,
-                              out_scale_dev=owner.scaler.inv_dyn)
+    def wgrad(self, x, gy):
+        o = self.owner
+        return K16.conv_wgrad(x, gy, self.k, self.stride, self.padding, out=self.g_weight, ws=o.wgrad_ws(x, gy, self), out_scale=o.inv_static,
+                              out_scale_dev=o.scaler.inv_dyn)
 
 
 class _H8StemConv(_ResidentConv):
     """conv1 of the 16-bit trainer: conv.ImgConvH8 (7x7 stride 2, fp32 image in, h8 out), its 16-bit planes repacked from the master weight by
-    conv.pack_weight_img_h8 (a host pack of 9408 weights); the weight gradient is the fp32 kernel's (_ResidentConv.wgrad: atomics, in scaled units)."""
+    ImgConvH8.repack (a host pack of 9408 weights); the weight gradient is the fp32 kernel's on the h8 gradient map cast to fp32
+    (_ResidentConv.wgrad: atomics, in scaled units)."""
 
     def __init__(self, P, name, stride, padding, device, elem='f16'):
         super().__init__(P, name, stride, padding, device)
-        self.elem, self.img = elem, None
+        self.dtype, self.img = H8_DTYPES[elem], None
 
     def plan(self):
         if self.img is None:
-            with _precision(self.elem):
-                self.img = C.ImgConvH8(self.weight.detach(), self.stride, self.padding, device=self.weight.device)
+            self.img = C.ImgConvH8(self.weight.detach(), self.stride, self.padding, device=self.weight.device, dtype=self.dtype)
         else:
-            self.img.planes = C.pack_weight_img_h8(self.weight.detach().cpu(), dtype=H8_DTYPES[self.elem]).to(self.weight.device)
+            self.img.repack(self.weight.detach())
 
     def forward(self, x):
         return self.img.forward(x)
+
+    def wgrad(self, x, gy):
+        return super().wgrad(x, K16.cast_from_h8(gy))
 
 
 class TrainableResNet50H8(TrainableResNet50):
@@ -478,10 +501,12 @@ class TrainableResNet50H8(TrainableResNet50):
     the convolutions run on the 16-bit MFMA (conv.H8Conv / conv.ImgConvH8, l2i_conv2d_wgrad_h8), BatchNorm on csrc/l2i_train_h8.hip; master
     weights, gradients, BatchNorm statistics, the fc and the loss stay fp32 / float64.  Resident from the start (one gradient arena, the two
     float64 BatchNorm arenas, optim.GuardedAdam with ``self.scaler``): ``train_step_resident`` drives it, checkpoints are TrainableResNet50's.
+    The schedule is TrainableResNet50's: only the layer objects, ``maps`` and the hooks below differ.
 
     Loss scale: the gradient entering the maps is multiplied by 2^``loss_scale_log2`` (default regtrain_scale_for for fp16, 0 for bf16) times the
     scaler's dynamic factor; the weight gradients are unscaled by the kernel that writes them, conv1's and the BatchNorm parameters' by one
     multiply over their stretch of the arena, so ``p.grad`` is the true gradient — or non-finite after an overflow, which GuardedAdam skips."""
+    maps = K16
 
     def __init__(self, state, device='cuda', num_classes=40, precision='f16', loss_scale_log2=None, image_size=256, batch=32):
         from . import optim
@@ -507,18 +532,14 @@ class TrainableResNet50H8(TrainableResNet50):
 
     def _arena_order(self, named):
         """conv1.weight and the BatchNorm parameters at the end, in one stretch: their gradients are written in scaled units."""
-        tail = [(k, t) for k, t in named if k == 'conv1.weight' or t.dim() == 1 and not k.startswith('fc.')]
-        names = set(k for k, _ in tail)
-        return [(k, t) for k, t in named if k not in names] + tail
+        return [kt for kt in named if not _in_scaled_tail(*kt)] + [kt for kt in named if _in_scaled_tail(*kt)]
 
     def _make_resident(self):
         super()._make_resident()
-        order = self._arena_order(self.named_parameters())
-        tail = next(k for k, t in order if k == 'conv1.weight' or t.dim() == 1 and not k.startswith('fc.'))
-        self.scaled_grads = self.grad_arena[self.grad_offsets[tail]:]
+        first = next(k for k, t in self.named_parameters() if _in_scaled_tail(k, t))      # (the tail keeps the parameters' order)
+        self.scaled_grads = self.grad_arena[self.grad_offsets[first]:]
 
     def bn_ws(self, x):
-        from . import kernels16 as K16
         b, g8, h, w, _ = x.shape
         n = K16.bn_ws_bytes(b, g8 * 8, h * w, x.dtype) // 8
         if self._bn_ws is None or self._bn_ws.numel() < n:
@@ -526,84 +547,22 @@ class TrainableResNet50H8(TrainableResNet50):
         return self._bn_ws
 
     def wgrad_ws(self, x, gy, cv):
-        from . import kernels16 as K16
         n = K16.wgrad_ws_bytes(x.shape[0], x.shape[1] * 8, x.shape[2], x.shape[3], gy.shape[1] * 8, gy.shape[2], gy.shape[3], cv.k, cv.stride, cv.padding, x.dtype) // 4
         if self._wg_ws is None or self._wg_ws.numel() < n:
             self._wg_ws = torch.empty(n, device=x.device, dtype=torch.float32)
         return self._wg_ws
 
-    def forward(self, img, keep=True):
-        from . import kernels16 as K16
-        x = img.detach().float().contiguous()
-        self.fwd_sums.zero_()
-        z0 = self.stem.forward(x)
-        a0, s0 = self.stem_bn.forward(z0)
-        p0, idx0 = K16.maxpool2d_fwd(a0, 3, 2, 1)
-        self._probe('T.fwd.stem', z0, a0)
-        saved = dict(img=x, s0=s0, a0=a0, idx0=idx0, blocks=[])
-        cur = p0
-        for blk in self.blocks:
-            y1, s1 = blk['b1'].forward(blk['c1'].forward(cur))
-            y2, s2 = blk['b2'].forward(blk['c2'].forward(y1))
-            z3 = blk['c3'].forward(y2)
-            if blk['cd'] is not None:
-                idt, sd = blk['bd'].forward(blk['cd'].forward(cur), relu=False)
-            else:
-                idt, sd = cur, None
-            out, s3 = blk['b3'].forward(z3, residual=idt, relu=True)
-            self._probe('T.fwd.' + blk['c1'].name.split('.')[0], s1[0], y1, s2[0], y2, z3, out)
-            if keep:
-                saved['blocks'].append((cur, y1, s1, y2, s2, s3, sd, out))
-            cur = out
-        b, g8, h, w, _ = cur.shape
-        feat = K16.dot_reduce(cur) * (1.0 / (h * w))
-        self._saved = dict(saved, feat=feat, last=(b, g8, h, w)) if keep else None
-        return torch.addmm(self.fc_b, feat, self.fc_w.t())
+    def _input(self, img):
+        return img.detach().float().contiguous()
 
-    __call__ = forward
-
-    def backward(self, g_preds):
-        """dL/d preds [B,40] -> {parameter name: gradient}, every one a view of the arena holding the TRUE gradient."""
-        from . import kernels16 as K16
-        sv = self._saved
-        self.bwd_sums.zero_()
-        torch.mm(g_preds.t(), sv['feat'], out=self.grads['fc.weight'])
-        torch.sum(g_preds, 0, out=self.grads['fc.bias'])
-        b, g8, h, w = sv['last']
+    def _head_grad(self, g_preds, last):
+        """The head gradient in h8, times the static and the dynamic loss scale."""
+        b, g8, h, w = last
         g_feat = torch.mm(g_preds, self.fc_w) * (self.static / (h * w)) * self.scaler.dyn
-        g = g_feat.reshape(b, g8, 1, 1, 8).expand(b, g8, h, w, 8).contiguous().to(self.dtype)
-        self._probe('T.g.head', g)
-        for blk, saved in zip(reversed(self.blocks), reversed(sv['blocks'])):
-            g = self.block_backward_h8(blk, saved, g)
-        a0 = sv['a0']
-        g_a0 = K16.maxpool2d_bwd(g, sv['idx0'], (a0.shape[2], a0.shape[3]), 3, 2, 1)
-        g_z0 = self.stem_bn.backward(g_a0, sv['s0'], out_mask=a0)[0]
-        self._probe('T.g.stem', g_a0, g_z0)
-        self.stem.wgrad(sv['img'], K16.cast_from_h8(g_z0))
-        self.scaled_grads.mul_(self.scaler.inv_dyn * self.inv_static)          # conv1.weight and the BatchNorm parameters: scaled -> true gradients
-        self._saved = None
-        return self.grads
+        return g_feat.reshape(b, g8, 1, 1, 8).expand(b, g8, h, w, 8).contiguous().to(self.dtype)
 
-    def block_backward_h8(self, blk, saved, g):
-        """One bottleneck block on h8 maps: g = dL/d(block output), scaled -> dL/d(block input), scaled."""
-        from . import kernels16 as K16
-        cur, y1, s1, y2, s2, s3, sd, out = saved
-        hw = lambda t: (t.shape[2], t.shape[3])
-        g_z3, _, _, gm = blk['b3'].backward(g, s3, out_mask=out, want_masked=True)          # out = relu(bn3(z3) + idt): gm feeds the identity branch
-        blk['c3'].wgrad(y2, g_z3, self)
-        g_z2 = blk['b2'].backward(blk['c3'].dgrad(g_z3, hw(y2)), s2, out_mask=y2)[0]
-        blk['c2'].wgrad(y1, g_z2, self)
-        g_z1 = blk['b1'].backward(blk['c2'].dgrad(g_z2, hw(y1)), s1, out_mask=y1)[0]
-        blk['c1'].wgrad(cur, g_z1, self)
-        self._probe('T.g.' + blk['c1'].name.split('.')[0], g_z3, g_z2, g_z1)
-        if blk['cd'] is None:
-            return blk['c1'].dgrad(g_z1, hw(cur), residual=gm)                             # the identity gradient rides on the conv's residual operand
-        g_zd = blk['bd'].backward(gm, sd)[0]
-        blk['cd'].wgrad(cur, g_zd, self)
-        if blk['cd'].stride == 1:
-            return blk['cd'].dgrad(g_zd, hw(cur), residual=blk['c1'].dgrad(g_z1, hw(cur)))
-        g_in = blk['c1'].dgrad(g_z1, hw(cur))
-        return K16.add_zero_insert(g_in, blk['cd'].h8.dgrad_compact(g_zd))                  # strided 1x1: compact conv + zero insertion
+    def _end_backward(self):
+        self.scaled_grads.mul_(self.scaler.inv_dyn * self.inv_static)          # conv1.weight and the BatchNorm parameters: scaled -> true gradients
 
 
 def make_model(state, precision='f32', device='cuda', resident=False, **kw):
@@ -779,10 +738,7 @@ def main(data_path='/transient_scene/imageAlignedLD/', label_path='/transient_sc
     resident = resident or hip_graph or precision != 'f32'
     # the reference starts from torchvision's ImageNet weights (a download); offline the caller passes a state dict, or seeded random init
     state = state if state is not None else synth.resnet50_state(seed=300)
-    if precision == 'f32':
-        model = TrainableResNet50(state, device='cuda', resident=resident)
-    else:
-        model = TrainableResNet50H8(state, device='cuda', precision=precision, loss_scale_log2=loss_scale_log2, image_size=image_size, batch=batch_size)
+    model = make_model(state, precision, device='cuda', resident=resident, loss_scale_log2=loss_scale_log2, image_size=image_size, batch=batch_size)
     optimizer = make_optimizer(model, guarded=resident)
     step = train_step_resident if resident else train_step
     on_device = DeviceDataset(train) if device_data else None

@@ -86,30 +86,36 @@ def _rounders(dtype):
     return Store.apply, Fwd.apply, Bwd.apply, Scale.apply
 
 
-def forward16(P, x, dtype, scale, momentum=0.1):
-    """resnet50_train_forward with the stores; the parameter gradients below the head come out multiplied by ``scale``."""
-    store, wr, gstore, scaled = _rounders(dtype)
+def block16(P, x, p, s, down, rounders, running=True, momentum=0.1):
+    """One bottleneck block ``p`` ('layer2.0') of stride ``s`` with the stores (``rounders`` = _rounders(dtype)), ``down``: with a downsample branch.
+    ``running`` False: ``P`` holds no running statistics (tests/test_regtrain16_block_gpu.py runs single blocks through this)."""
+    store, wr, gstore, _ = rounders
 
     def bn(prefix, t):
-        return F.batch_norm(t, P[prefix + '.running_mean'], P[prefix + '.running_var'], P[prefix + '.weight'], P[prefix + '.bias'],
-                            training=True, momentum=momentum, eps=1e-5)
+        return F.batch_norm(t, P[prefix + '.running_mean'] if running else None, P[prefix + '.running_var'] if running else None,
+                            P[prefix + '.weight'], P[prefix + '.bias'], training=True, momentum=momentum, eps=1e-5)
     conv = lambda t, name, **kw: store(F.conv2d(t, wr(P[name]), **kw))
-    x = conv(x, 'conv1.weight', stride=2, padding=3)
-    x = store(F.relu(bn('bn1', x)))
+    idt = x
+    xin = gstore(x) if down else x                               # a downsample block stores conv1's input gradient before it adds the other branch
+    o = store(F.relu(bn(p + '.bn1', conv(xin, p + '.conv1.weight'))))
+    o = store(F.relu(bn(p + '.bn2', conv(o, p + '.conv2.weight', stride=s, padding=1))))
+    o = conv(o, p + '.conv3.weight')
+    if down:
+        xd = gstore(x) if s == 2 else x                          # stride 2: the compact gradient is stored too, then zero-inserted and added
+        idt = store(bn(p + '.downsample.1', conv(xd, p + '.downsample.0.weight', stride=s)))
+    return store(F.relu(bn(p + '.bn3', o) + idt))
+
+
+def forward16(P, x, dtype, scale, momentum=0.1):
+    """resnet50_train_forward with the stores; the parameter gradients below the head come out multiplied by ``scale``."""
+    rounders = _rounders(dtype)
+    store, wr, _, scaled = rounders
+    x = store(F.conv2d(x, wr(P['conv1.weight']), stride=2, padding=3))
+    x = store(F.relu(F.batch_norm(x, P['bn1.running_mean'], P['bn1.running_var'], P['bn1.weight'], P['bn1.bias'], training=True, momentum=momentum, eps=1e-5)))
     x = F.max_pool2d(x, 3, 2, 1)
     for li, (planes, blocks, stride) in enumerate(RESNET50_LAYERS):
         for b in range(blocks):
-            p = 'layer%d.%d' % (li + 1, b)
-            s = stride if b == 0 else 1
-            idt = x
-            xin = gstore(x) if b == 0 else x                     # a downsample block stores conv1's input gradient before it adds the other branch
-            o = store(F.relu(bn(p + '.bn1', conv(xin, p + '.conv1.weight'))))
-            o = store(F.relu(bn(p + '.bn2', conv(o, p + '.conv2.weight', stride=s, padding=1))))
-            o = conv(o, p + '.conv3.weight')
-            if b == 0:
-                xd = gstore(x) if s == 2 else x                  # stride 2: the compact gradient is stored too, then zero-inserted and added
-                idt = store(bn(p + '.downsample.1', conv(xd, p + '.downsample.0.weight', stride=s)))
-            x = store(F.relu(bn(p + '.bn3', o) + idt))
+            x = block16(P, x, 'layer%d.%d' % (li + 1, b), stride if b == 0 else 1, b == 0, rounders, momentum=momentum)
     x = scaled(F.adaptive_avg_pool2d(x, 1).flatten(1), scale)
     return F.linear(x, P['fc.weight'], P['fc.bias'])
 

@@ -982,7 +982,7 @@ def test_regressor_training_step_vs_oracle(tmp_path):
             (bi, int(flip.sum()), float(pre.detach()[flip].abs().max()) / float(pre.detach().abs().max()))
         gin = gin * (~flip).to(DEV)
         grads = {}
-        gx = RT.TrainableResNet50.block_backward(blk, saved, gin, grads)
+        gx = model.block_backward(blk, saved, gin, grads)
         ref = torch.autograd.grad(o, [x] + list(prm.values()), D(gin))
         assert rel(gx, ref[0]) < 1e-4, (bi, 'input', rel(gx, ref[0]))
         for k, r in zip(prm, ref[1:]):
