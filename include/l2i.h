@@ -370,6 +370,17 @@ int l2i_upfirdn2d_masked_f32(float* y, const float* x, const float* k, int64_t m
                              int channels, const float* noise, float noise_w, const float* bias, const float* addend,
                              int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream);
 
+/* The same launch with a second output: y is exactly what l2i_upfirdn2d_masked_f32 writes, and y2[idx] = y[idx] * (mask2[idx] > 0 ? pos2 : neg2), one fp32
+ * multiply on the value held in registers.  The discriminator's backward: the FIR that produces a block's gradient g also writes g through the leaky ReLU
+ * of the next block's stride-2 conv, so that conv's input gradient is an unmasked transposed launch (the DMA-fed kernels) while the skip path keeps reading
+ * g.  y2 and mask2 are shaped like y and are given together or not at all: one without the other returns L2I_E_ARG and nothing is written; both NULL =
+ * l2i_upfirdn2d_masked_f32.  Every fp32 FIR kernel has the second output; the vector paths want y2 and mask2 16-byte aligned like y (else the launch falls
+ * through to the next kernel, as for y).  Additive: the ABI version is unchanged. */
+int l2i_upfirdn2d_dual_f32(float* y, float* y2, const float* mask2, float pos2, float neg2, const float* x, const float* k, int64_t major,
+                           int in_h, int in_w, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                           int channels, const float* noise, float noise_w, const float* bias, const float* addend,
+                           int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream);
+
 /* upfirdn2d for half tensors (upfirdn2d_kernel.cu:225 dispatches half too): plain reference op, no fused epilogue.  y / x / k point to IEEE
  * binary16; like the reference kernel the taps and products are float and the accumulator is rounded to half after every tap, taps in
  * ascending input row / column order (upfirdn2d_kernel.cu:118-123): bit-identical results. */

@@ -249,10 +249,14 @@ struct PolyRule { int pad, masked, cin, cout, h; };
 constexpr PolyRule kPolyRules[] = {
     // the generator's up layers (forward form)
     {0, 0, 512, 512, 32}, {0, 0, 512, 256, 64}, {0, 0, 256, 128, 128}, {0, 0, 128, 64, 256}, {0, 0, 64, 32, 512},
-    // The masked launches (input gradients of the stride-2 convs of the discriminator and of ResNet-50) are faster per launch too (0.77 - 0.90 of the
-    // direct kernel's time, same file) but are not routed here yet: the step-output check that has to clear them (walk gradient against the parent
-    // build's dump) turned out to swing between 7e-5 and 9e-4 of the maximum between two dumps of the PARENT itself (section 4 of that file), so it
-    // could not tell their effect from none.  tile_hint 10 runs them here.
+    // The input gradients of the discriminator's stride-2 convs arrive UNMASKED on maps >= 32 wide (the FIR that produces the gradient writes it through
+    // the leaky-ReLU mask as a second output, l2i_upfirdn2d_dual_f32) and have exactly the five shapes above, outputs three larger included: no row of
+    // their own.  ResNet-50's three stride-2 bottlenecks arrive unmasked too (out_mask on c3's gradient GEMM), pad 1, natural size
+    // (profiles/premask_stride2_ab.txt section 1: 0.74 - 0.78 of the direct kernel's time, both repetitions).  512 -> 512 @32 pad 1 wins there as well
+    // (0.74) and is NOT listed: tests/test_convt_poly_cpu.py pins that struct to the direct kernel under tile_hint 0.
+    {1, 0, 128, 128, 128}, {1, 0, 256, 256, 64},
+    // No masked row: what still carries in_mask in the fp32 step (the deepest discriminator block, fed by the tail, and maps under 32 wide) is either too
+    // narrow for this kernel or a single launch of a few microseconds.  tile_hint 10 runs a masked struct here.
 };
 
 }  // namespace

@@ -89,10 +89,15 @@ struct UfdParams {
     long long major; int in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_y0, out_h, out_w;
     int channels; const float* noise; float noise_w; const float* bias; const float* addend; int act; float slope, gain;
     const float* mask; float mask_pos, mask_neg;       // [r5] l2i_upfirdn2d_masked_f32: y *= (mask > 0 ? mask_pos : mask_neg) after the activation (a gradient through a (leaky) ReLU)
+    float* y2; const float* mask2; float pos2, neg2;   // l2i_upfirdn2d_dual_f32 (the DUAL instantiations only): y2 = y * (mask2 > 0 ? pos2 : neg2), y's index space
 };
+
+// the second output of a DUAL launch from the value(s) just stored to y
+__device__ __forceinline__ float ufd_second(const UfdParams& p, float v, float m) { return v * (m > 0.f ? p.pos2 : p.neg2); }
 
 // one thread = one output pixel; a block covers a 16x64 output tile of one map so that the <=19x67 input footprint is
 // served from L1/L2 (the FIR taps sit in LDS).
+template <bool DUAL>
 __global__ __launch_bounds__(256) void upfirdn2d_kernel(const UfdParams p) {
     __shared__ float sk[64];
     const int ntap = p.kh * p.kw;
@@ -136,6 +141,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_kernel(const UfdParams p) {
             else if (p.act == L2I_ACT_RELU) v = v > 0.f ? v : 0.f;
             if (p.mask) v *= p.mask[oidx] > 0.f ? p.mask_pos : p.mask_neg;
             p.y[oidx] = v;
+            if (DUAL) p.y2[oidx] = ufd_second(p, v, p.mask2[oidx]);
         }
     }
 }
@@ -143,6 +149,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_kernel(const UfdParams p) {
 // Fast path for the hot case up = down = 1 with a 4x4 FIR (every Blur of the generator and discriminator, forward and
 // backward): one block = 32x64 outputs of one map; the 35x67 input footprint is staged once in LDS (coalesced rows),
 // each thread produces a 2x4 patch from a 5x7 register window (35 LDS dwords per 8 outputs), 16-byte stores.
+template <bool DUAL>
 __global__ __launch_bounds__(256) void upfirdn2d_k4_kernel(const UfdParams p) {
     constexpr int TH = 32, TW = 64, IH = TH + 3, PITCH = 72, NQ = PITCH / 4;   // 18 float4 per staged row
     __shared__ __attribute__((aligned(16))) float tile[IH * PITCH];
@@ -233,6 +240,18 @@ __global__ __launch_bounds__(256) void upfirdn2d_k4_kernel(const UfdParams p) {
                 for (int q = 0; q < 4; ++q)
                     if (ox + q < p.out_w) p.y[obase + q] = o[q];
             }
+            if (DUAL) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (ox + q < p.out_w) o[q] = ufd_second(p, o[q], p.mask2[obase + q]);
+                if (ox + 3 < p.out_w && ((obase & 3) == 0) && (((uintptr_t)p.y2 & 15) == 0)) {
+                    *reinterpret_cast<float4*>(p.y2 + obase) = make_float4(o[0], o[1], o[2], o[3]);
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (ox + q < p.out_w) p.y2[obase + q] = o[q];
+                }
+            }
         }
     }
 }
@@ -294,6 +313,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_k4_down2_stream_kernel(const Uf
 // up = 2, down = 1, 4x4 FIR, pad0 = 2 (the ToRGB skip upsample, networks.py:35-43 / :353-356, on 3-channel images): a thread owns a 2 x 4
 // patch of outputs (rows 2i, 2i + 1; columns 4j .. 4j + 3) = input rows i - 1 .. i + 1, columns 2j - 1 .. 2j + 2.  Every output sums its
 // 2 x 2 live taps in the generic kernel's (ky, kx) order (bit-identical results); 16-byte stores, addend read as 16-byte vectors.
+template <bool DUAL>
 __global__ __launch_bounds__(256) void upfirdn2d_up2k4_kernel(const UfdParams p) {
     float kf[16];
 #pragma unroll
@@ -351,6 +371,10 @@ __global__ __launch_bounds__(256) void upfirdn2d_up2k4_kernel(const UfdParams p)
                 else if (p.act == L2I_ACT_RELU) o[q] = o[q] > 0.f ? o[q] : 0.f;
             }
             *reinterpret_cast<float4*>(p.y + obase) = make_float4(o[0], o[1], o[2], o[3]);
+            if (DUAL) {
+                const float4 m2 = *reinterpret_cast<const float4*>(p.mask2 + obase);
+                *reinterpret_cast<float4*>(p.y2 + obase) = make_float4(ufd_second(p, o[0], m2.x), ufd_second(p, o[1], m2.y), ufd_second(p, o[2], m2.z), ufd_second(p, o[3], m2.w));
+            }
         }
     }
 }
@@ -361,7 +385,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_up2k4_kernel(const UfdParams p)
 // memory), so a wave reads 1 KiB of contiguous row per step and every input element is fetched once per 16-row band (+ 3 halo rows).
 // Taps are summed in the same (ky, kx) order as upfirdn2d_k4_kernel: bit-identical results.  (Measured, not kept: prefetching the next
 // LDS tile of the staged kernel into registers, 3.4 -> 3.0 TB/s.)
-template <int PX>       // pad_x0: 1 or 2 halo columns on the left, 3 - PX on the right
+template <int PX, bool DUAL>       // pad_x0: 1 or 2 halo columns on the left, 3 - PX on the right
 __global__ __launch_bounds__(256) void upfirdn2d_k4_stream_kernel(const UfdParams p, int bands, int strips) {
     constexpr int RS = 16;                                           // output rows per wave
     float kf[16];
@@ -437,20 +461,25 @@ __global__ __launch_bounds__(256) void upfirdn2d_k4_stream_kernel(const UfdParam
             o[2] *= mk.z > 0.f ? p.mask_pos : p.mask_neg; o[3] *= mk.w > 0.f ? p.mask_pos : p.mask_neg;
         }
         *reinterpret_cast<float4*>(p.y + obase) = make_float4(o[0], o[1], o[2], o[3]);
+        if (DUAL) {
+            const float4 m2 = *reinterpret_cast<const float4*>(p.mask2 + obase);
+            *reinterpret_cast<float4*>(p.y2 + obase) = make_float4(ufd_second(p, o[0], m2.x), ufd_second(p, o[1], m2.y), ufd_second(p, o[2], m2.z), ufd_second(p, o[3], m2.w));
+        }
     }
 }
 
 static int upfirdn2d_launch(float* y, const float* x, const float* k, int64_t major, int in_h, int in_w, int kh, int kw,
                             int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                             int channels, const float* noise, float noise_w, const float* bias, const float* addend,
-                            int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream);
+                            int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg,
+                            float* y2, const float* mask2, float pos2, float neg2, void* stream);
 
 extern "C" int l2i_upfirdn2d_f32(float* y, const float* x, const float* k, int64_t major, int in_h, int in_w, int kh, int kw,
                                  int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                                  int channels, const float* noise, float noise_w, const float* bias, const float* addend,
                                  int act, float act_slope, float act_gain, void* stream) {
     return upfirdn2d_launch(y, x, k, major, in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, channels, noise, noise_w, bias, addend,
-                            act, act_slope, act_gain, nullptr, 1.f, 0.f, stream);
+                            act, act_slope, act_gain, nullptr, 1.f, 0.f, nullptr, nullptr, 1.f, 0.f, stream);
 }
 
 extern "C" int l2i_upfirdn2d_masked_f32(float* y, const float* x, const float* k, int64_t major, int in_h, int in_w, int kh, int kw,
@@ -458,13 +487,25 @@ extern "C" int l2i_upfirdn2d_masked_f32(float* y, const float* x, const float* k
                                         int channels, const float* noise, float noise_w, const float* bias, const float* addend,
                                         int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream) {
     return upfirdn2d_launch(y, x, k, major, in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, channels, noise, noise_w, bias, addend,
-                            act, act_slope, act_gain, mask, mask_pos, mask_neg, stream);
+                            act, act_slope, act_gain, mask, mask_pos, mask_neg, nullptr, nullptr, 1.f, 0.f, stream);
+}
+
+// Two outputs from one pass: y as l2i_upfirdn2d_masked_f32 writes it and y2 = y * (mask2 > 0 ? pos2 : neg2) — a gradient and the same gradient through
+// the (leaky) ReLU of its next consumer, so that consumer's conv runs unmasked.  y2 and mask2 come together or not at all.
+extern "C" int l2i_upfirdn2d_dual_f32(float* y, float* y2, const float* mask2, float pos2, float neg2, const float* x, const float* k, int64_t major,
+                                      int in_h, int in_w, int kh, int kw, int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
+                                      int channels, const float* noise, float noise_w, const float* bias, const float* addend,
+                                      int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream) {
+    if ((y2 != nullptr) != (mask2 != nullptr)) return l2i_set_error(L2I_E_ARG, "upfirdn2d_dual: y2 and mask2 are given together or not at all");
+    return upfirdn2d_launch(y, x, k, major, in_h, in_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1, channels, noise, noise_w, bias, addend,
+                            act, act_slope, act_gain, mask, mask_pos, mask_neg, y2, mask2, pos2, neg2, stream);
 }
 
 static int upfirdn2d_launch(float* y, const float* x, const float* k, int64_t major, int in_h, int in_w, int kh, int kw,
                             int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                             int channels, const float* noise, float noise_w, const float* bias, const float* addend,
-                            int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg, void* stream) {
+                            int act, float act_slope, float act_gain, const float* mask, float mask_pos, float mask_neg,
+                            float* y2, const float* mask2, float pos2, float neg2, void* stream) {
     if (!y || !x || !k) return l2i_set_error(L2I_E_ARG, "upfirdn2d: null tensor");
     if (major <= 0 || in_h <= 0 || in_w <= 0) return l2i_set_error(L2I_E_ARG, "upfirdn2d: empty input");
     if (kh <= 0 || kw <= 0 || kh * kw > 64) return l2i_set_error(L2I_E_ARG, "upfirdn2d: FIR must have 1..64 taps");
@@ -478,25 +519,29 @@ static int upfirdn2d_launch(float* y, const float* x, const float* k, int64_t ma
     p.channels = channels > 0 ? channels : 1;
     p.noise = noise; p.noise_w = noise_w; p.bias = bias; p.addend = addend; p.act = act; p.slope = act_slope; p.gain = act_gain;
     p.mask = mask; p.mask_pos = mask_pos; p.mask_neg = mask_neg;
+    p.y2 = y2; p.mask2 = mask2; p.pos2 = pos2; p.neg2 = neg2;
+    const bool dual = y2 != nullptr;                                   // every kernel below has a DUAL instantiation; the vector paths want y2 / mask2 aligned like y
+    const bool al2 = (((uintptr_t)y2 | (uintptr_t)mask2) % 16) == 0;
     if (up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4 && (pad_x0 == 1 || pad_x0 == 2) && p.out_w >= 192 && (in_w % 4) == 0 &&
-        (p.out_w % 4) == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)noise | (uintptr_t)addend | (uintptr_t)mask) % 16) == 0) {
+        (p.out_w % 4) == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)noise | (uintptr_t)addend | (uintptr_t)mask) % 16) == 0 && al2) {
         const int strips = (p.out_w + 255) / 256, bands = (p.out_h + 63) / 64;
         const long long grid = major * bands * strips;
         if (grid > 0 && grid <= 0x7fffffffLL) {
-            if (pad_x0 == 1) hipLaunchKernelGGL((upfirdn2d_k4_stream_kernel<1>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, bands, strips);
-            else hipLaunchKernelGGL((upfirdn2d_k4_stream_kernel<2>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, bands, strips);
+            auto kern = pad_x0 == 1 ? (dual ? upfirdn2d_k4_stream_kernel<1, true> : upfirdn2d_k4_stream_kernel<1, false>)
+                                    : (dual ? upfirdn2d_k4_stream_kernel<2, true> : upfirdn2d_k4_stream_kernel<2, false>);
+            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p, bands, strips);
             L2I_CHECK_LAUNCH();
             return L2I_OK;
         }
     }
     if (up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4) {
         const long long nt = major * ((p.out_w + 63) / 64) * ((p.out_h + 31) / 32);
-        hipLaunchKernelGGL(upfirdn2d_k4_kernel, dim3(l2i_grid_for(nt, 1, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(dual ? upfirdn2d_k4_kernel<true> : upfirdn2d_k4_kernel<false>, dim3(l2i_grid_for(nt, 1, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
         L2I_CHECK_LAUNCH();
         return L2I_OK;
     }
     if (up_x == 1 && up_y == 1 && down_x == 2 && down_y == 2 && kh == 4 && kw == 4 && pad_x0 == 1 && pad_y0 == 1 && p.out_w >= 96 && (in_w % 4) == 0 &&
-        (p.out_w % 2) == 0 && !noise && !bias && !addend && !mask && act == L2I_ACT_NONE && (((uintptr_t)x) % 16) == 0 && (((uintptr_t)y) % 8) == 0) {
+        (p.out_w % 2) == 0 && !noise && !bias && !addend && !mask && !dual && act == L2I_ACT_NONE && (((uintptr_t)x) % 16) == 0 && (((uintptr_t)y) % 8) == 0) {
         const int strips = (p.out_w + 127) / 128, bands = (p.out_h + 31) / 32;
         const long long grid = major * bands * strips;
         if (grid > 0 && grid <= 0x7fffffffLL) {
@@ -506,14 +551,14 @@ static int upfirdn2d_launch(float* y, const float* x, const float* k, int64_t ma
         }
     }
     if (up_x == 2 && up_y == 2 && down_x == 1 && down_y == 1 && kh == 4 && kw == 4 && pad_x0 == 2 && pad_y0 == 2 && p.out_h == 2 * in_h && p.out_w == 2 * in_w &&
-        (p.out_w % 4) == 0 && !mask && (((uintptr_t)y | (uintptr_t)addend) % 16) == 0) {
+        (p.out_w % 4) == 0 && !mask && (((uintptr_t)y | (uintptr_t)addend) % 16) == 0 && al2) {
         const long long n = major * (p.out_h / 2) * (p.out_w / 4);
-        hipLaunchKernelGGL(upfirdn2d_up2k4_kernel, dim3(l2i_grid_for(n, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(dual ? upfirdn2d_up2k4_kernel<true> : upfirdn2d_up2k4_kernel<false>, dim3(l2i_grid_for(n, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
         L2I_CHECK_LAUNCH();
         return L2I_OK;
     }
     const long long ntiles = major * ((p.out_w + 63) / 64) * ((p.out_h + 15) / 16);
-    hipLaunchKernelGGL(upfirdn2d_kernel, dim3(l2i_grid_for(ntiles, 1, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(dual ? upfirdn2d_kernel<true> : upfirdn2d_kernel<false>, dim3(l2i_grid_for(ntiles, 1, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p);
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }

@@ -4,7 +4,8 @@ HIP kernels.  Reference: networks.py:517-645 (ConvLayer, ResBlock, Discriminator
 Body (from_rgb conv + residual blocks) = one autograd function with hand-scheduled input-gradient; the 4x4 tail
 (minibatch-stddev, final conv, two linears) runs on small torch ops + one FrozenConv2d call.
 EqualConv2d's 1/sqrt(fan_in) is folded into the packed weights; FusedLeakyReLU bias+activation, the residual add and
-the 1/sqrt(2) live in the conv epilogue; leaky-ReLU' is a prologue mask of the gradient convs.
+the 1/sqrt(2) live in the conv epilogue; leaky-ReLU' is a prologue mask of the gradient convs, except where the
+launch that produces a gradient also writes it through the mask of its stride-2 consumer (PREMASK).
 """
 import math
 
@@ -13,9 +14,15 @@ import torch
 
 from . import conv as C
 from . import kernels as K
+from . import _lib
 
 SQRT2 = math.sqrt(2.0)
 LRELU_MASK = (SQRT2, 0.2 * SQRT2)          # d/dx [lrelu(x, 0.2) * sqrt2] keyed on the sign of the saved output
+# True: the FIR that ends a block's backward writes its gradient g twice, plain (for the skip path) and through the leaky-ReLU mask of the next block's
+# conv2 output (l2i_upfirdn2d_dual_f32), and that block's stride-2 input gradient runs unmasked: the DMA-fed transposed kernels, on the shapes of
+# the generator's up layers the 25-product kernel.  False: the prologue mask on every block (the comparator the tests set).
+PREMASK = True
+PREMASK_MIN_W = 32                          # narrower gradient maps keep the prologue mask: neither transposed kernel feeds them by DMA
 
 
 def _eq_conv(P, name, stride, padding, device):
@@ -145,24 +152,36 @@ class _DBodyFn(torch.autograd.Function):
         if saved is None:
             raise RuntimeError('discriminator was run without a differentiable input')
         g = g.contiguous()
-        for blk, (y1, y2, in_hw) in zip(reversed(net.blocks), reversed(saved[1:])):
+        g2 = None                                                             # g through conv2's leaky-ReLU mask, where the producing FIR wrote it
+        premask = PREMASK and _lib.has('l2i_upfirdn2d_dual_f32')
+        for bi in range(len(net.blocks) - 1, -1, -1):
+            blk, (y1, y2, in_hw) = net.blocks[bi], saved[1 + bi]
             h = in_hw[0]
-            # conv2 path: lrelu' * 1/sqrt2 folded into the prologue mask
+            # conv2 path: lrelu' * 1/sqrt2 folded into the mask (the deepest block's g comes from the tail: it keeps the prologue mask)
             # (gradients of the padded blur maps of the forward: the extra rows / columns receive zeros and are cropped by the negative far pad)
-            g_t = blk['c2'].dgrad(g, (h + 4, h + 4), in_mask=y2, mask=(1.0, 0.2))
+            if g2 is not None:
+                g_t = blk['c2'].dgrad(g2, (h + 4, h + 4))
+                g2 = None
+            else:
+                g_t = blk['c2'].dgrad(g, (h + 4, h + 4), in_mask=y2, mask=(1.0, 0.2))
             g_y1 = K.upfirdn2d(g_t, blk['kf'], pad=(1, -2, 1, -2), mask=y1, mask_vals=LRELU_MASK)     # [r5] the leaky-ReLU mask of y1 rides on the FIR: the 3x3
                                                                                                      # gradient conv below is unmasked = the F(4x4) kernel
             del g_t
             g_a = blk['c1'].dgrad(g_y1, in_hw)
             del g_y1
-            # skip path
+            # skip path; its FIR produces the next (shallower) block's g, and with PREMASK that block's masked g too
+            m2 = {}
+            if premask and bi > 0 and saved[bi][1].shape[3] >= PREMASK_MIN_W:
+                m2 = dict(mask2=saved[bi][1], mask2_vals=(1.0, 0.2))
             if _skip_compact(h):
                 # adjoint of (blur, keep every second pixel): zero-insertion FIR (up = 2) of the compact gradient (op/upfirdn2d.py:105-115: g_pad = (2, 1))
                 g_ts = blk['sk1'].dgrad(g, (h // 2, h // 2), out_gain=1.0 / SQRT2)
-                g = K.upfirdn2d(g_ts, blk['kf'], up=(2, 2), pad=(2, 1, 2, 1), addend=g_a)
+                g = K.upfirdn2d(g_ts, blk['kf'], up=(2, 2), pad=(2, 1, 2, 1), addend=g_a, **m2)
             else:
                 g_ts = blk['sk'].dgrad(g, (h, h), out_gain=1.0 / SQRT2)
-                g = K.upfirdn2d(g_ts, blk['kf'], pad=(2, 1, 2, 1), addend=g_a)
+                g = K.upfirdn2d(g_ts, blk['kf'], pad=(2, 1, 2, 1), addend=g_a, **m2)
+            if m2:
+                g, g2 = g
             del g_ts, g_a
         g_img = net.conv0.dgrad(g, ctx.in_hw, in_mask=saved[0], mask=LRELU_MASK)
         ctx.saved = None

@@ -33,9 +33,11 @@ def upfirdn2d_out_hw(h, w, kh, kw, up, down, pad):
 
 
 def upfirdn2d(x, kernel, up=(1, 1), down=(1, 1), pad=(0, 0, 0, 0), noise=None, noise_w=0.0, bias=None, addend=None,
-              act=ACT_NONE, slope=0.2, gain=1.0, out=None, mask=None, mask_vals=(1.0, 0.0)):
+              act=ACT_NONE, slope=0.2, gain=1.0, out=None, mask=None, mask_vals=(1.0, 0.0), mask2=None, mask2_vals=(1.0, 0.0), out2=None):
     """x [N, C, H, W]; up/down = (x, y); pad = (x0, x1, y0, y1) as in op/upfirdn2d.cpp:12-23.  Optional fused
-    epilogue: act(fir(x) + noise*noise_w + bias[c] + addend) * gain, then [r5] * (mask > 0 ? mask_vals[0] : mask_vals[1]) (mask shaped like the output)."""
+    epilogue: act(fir(x) + noise*noise_w + bias[c] + addend) * gain, then [r5] * (mask > 0 ? mask_vals[0] : mask_vals[1]) (mask shaped like the output).
+    With ``mask2`` (shaped like the output) the launch writes a second map y2 = y * (mask2 > 0 ? mask2_vals[0] : mask2_vals[1]) and returns (y, y2)
+    (l2i_upfirdn2d_dual_f32)."""
     x = x.contiguous()
     n, c, h, w = x.shape
     kh, kw = kernel.shape
@@ -44,6 +46,16 @@ def upfirdn2d(x, kernel, up=(1, 1), down=(1, 1), pad=(0, 0, 0, 0), noise=None, n
     assert y.shape == (n, c, oh, ow), (y.shape, (n, c, oh, ow))
     if addend is not None:
         assert addend.shape == y.shape
+    if mask2 is not None:
+        assert mask2.shape == y.shape and (mask is None or mask.shape == y.shape)
+        y2 = torch.empty_like(y) if out2 is None else out2
+        assert y2.shape == y.shape
+        _lib.call('l2i_upfirdn2d_dual_f32', _lib.fptr(y), _lib.fptr(y2), _lib.fptr(mask2.contiguous()), float(mask2_vals[0]), float(mask2_vals[1]),
+                  _lib.fptr(x), _lib.fptr(kernel.contiguous()), n * c, h, w, kh, kw,
+                  up[0], up[1], down[0], down[1], pad[0], pad[1], pad[2], pad[3], c,
+                  _lib.fptr(noise), float(noise_w), _lib.fptr(bias), _lib.fptr(addend),
+                  int(act), float(slope), float(gain), _lib.fptr(None if mask is None else mask.contiguous()), float(mask_vals[0]), float(mask_vals[1]))
+        return y, y2
     if mask is not None:
         assert mask.shape == y.shape
         _lib.call('l2i_upfirdn2d_masked_f32', _lib.fptr(y), _lib.fptr(x), _lib.fptr(kernel.contiguous()), n * c, h, w, kh, kw,

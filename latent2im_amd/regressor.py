@@ -62,6 +62,9 @@ class ResNet50:
 
 
 PREMASK = True      # False: the consumer-side masking reference of the backward (the comparator the tests set)
+# True: the three stride-2 bottlenecks take the mask of y2 in the epilogue of c3's gradient GEMM (out_mask) like every other block, and c2's
+# input gradient, the one-launch transposed kernel, runs unmasked: its DMA-fed instantiation.  False: that launch masks on load (in_mask), as before.
+PREMASK_STRIDE2 = True
 
 
 def _backward_consumer_masked(net, saved, g):
@@ -149,12 +152,16 @@ class _ResNetFeatFn(torch.autograd.Function):
             # [r4] The masks of y2 / y1 are applied by the PRODUCING launch's epilogue (out_mask: a select on values it holds in registers) instead
             # of the consuming launch's prologue (in_mask): the same numbers, and the 3x3 gradient conv becomes an unmasked launch — the F(4x4,3x3)
             # Winograd kernel (csrc/l2i_wino4.hip) and the unmasked transposed instantiation take those
-            # (the three stride-2 blocks keep the prologue masks: their c2 gradient is the one-launch transposed kernel, which fuses in_mask only)
+            # (the three stride-2 blocks: their c2 gradient is the one-launch transposed kernel, which fuses no out_mask, so y1's mask stays a prologue
+            #  mask of c1's gradient GEMM; y2's mask is c3's out_mask like everywhere else, and the transposed launch is unmasked: PREMASK_STRIDE2)
             pre = blk['c2'].conv.stride == 1
-            g_y2 = blk['c3'].conv.dgrad(G, (y2.shape[2], y2.shape[3]), **(dict(out_mask=y2) if pre else {}))
+            g_y2 = blk['c3'].conv.dgrad(G, (y2.shape[2], y2.shape[3]), **(dict(out_mask=y2) if pre or PREMASK_STRIDE2 else {}))
             if pre:
                 g_y1 = blk['c2'].conv.dgrad(g_y2, (y1.shape[2], y1.shape[3]), out_mask=y1)
                 m1 = {}
+            elif PREMASK_STRIDE2:
+                g_y1 = blk['c2'].conv.dgrad(g_y2, (y1.shape[2], y1.shape[3]))
+                m1 = dict(in_mask=y1, mask=(1.0, 0.0))
             else:
                 g_y1 = blk['c2'].conv.dgrad(g_y2, (y1.shape[2], y1.shape[3]), in_mask=y2, mask=(1.0, 0.0))
                 m1 = dict(in_mask=y1, mask=(1.0, 0.0))

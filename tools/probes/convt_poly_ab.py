@@ -1,6 +1,7 @@
 """Stride-2 transposed 3x3 conv, fp32: the direct kernel (tile_hint 9: convt_mfma_kernel, its automatic tile) against the 25-product kernel (tile_hint 10:
 convt_poly_kernel) on the transposed shapes of the c3 step at batch 8 — the generator's up layers (forward form: in_scale, out_scale, outputs padded
-by 3) and the input gradients of the stride-2 convs of the discriminator (pad 0, masked, outputs padded by 3) and of ResNet-50 (pad 1, masked).  The
+by 3) and the input gradients of the stride-2 convs of the discriminator (pad 0, masked, outputs padded by 3) and of ResNet-50 (pad 1, masked, and
+'plain': unmasked, the mask applied by the launch that produces the gradient).  The
 two kernels are interleaved in one process, two alternating repetitions each (A B A B), so the spread between repetitions of one kernel stands beside
 the difference between the kernels.  ms per launch and TFLOP/s of the dense form (2 B Cout Cin 9 H W).  This file fixes kPolyRules
 (csrc/l2i_convt_poly.hip): a shape enters the table only where both repetitions of the new kernel beat both of the direct kernel."""
@@ -15,6 +16,7 @@ SHAPES = [  # cin, cout, res, pad, masked, extra
     (512, 512, 32, 0, False, 3), (512, 256, 64, 0, False, 3), (256, 128, 128, 0, False, 3), (128, 64, 256, 0, False, 3), (64, 32, 512, 0, False, 3),
     (512, 512, 32, 0, True, 3), (512, 256, 64, 0, True, 3), (256, 128, 128, 0, True, 3), (128, 64, 256, 0, True, 3), (64, 32, 512, 0, True, 3),
     (128, 128, 64, 1, True, 1), (256, 256, 32, 1, True, 1), (128, 128, 128, 1, True, 1), (256, 256, 64, 1, True, 1), (512, 512, 32, 1, True, 1),
+    (128, 128, 128, 1, None, 1), (256, 256, 64, 1, None, 1), (512, 512, 32, 1, None, 1),          # None: no prologue or epilogue operand at all
 ]
 
 
@@ -40,7 +42,9 @@ for cin, cout, res, pad, masked, extra in SHAPES:
     x = torch.randn(B, cin, res, res, device='cuda')
     oh, ow = fc.out_hw(res, res)
     y = torch.empty(B, cout, oh + extra, ow + extra, device='cuda')
-    if masked:
+    if masked is None:
+        kw = {}
+    elif masked:
         kw = dict(in_mask=torch.randn(B, cin, res, res, device='cuda'), mask=(1.0, 0.2))
     else:
         kw = dict(in_scale=torch.rand(B, cin, device='cuda') + 0.5, out_scale=torch.rand(B, cout, device='cuda') + 0.5)
@@ -53,5 +57,5 @@ for cin, cout, res, pad, masked, extra in SHAPES:
     fl = 2.0 * B * cout * cin * 9 * res * res
     wins = max(t[1], t[3]) < min(t[0], t[2])
     print('%4d->%-4d @%-4d pad %d %-8s direct %.4f %.4f ms (%.0f TF)  poly %.4f %.4f ms (%.0f TF)  poly/direct %.3f  %s  max dev %.1e' % (
-        cin, cout, res, pad, 'masked' if masked else 'forward', t[0], t[2], fl / min(t[0], t[2]) / 1e9, t[1], t[3], fl / min(t[1], t[3]) / 1e9,
+        cin, cout, res, pad, 'plain' if masked is None else ('masked' if masked else 'forward'), t[0], t[2], fl / min(t[0], t[2]) / 1e9, t[1], t[3], fl / min(t[1], t[3]) / 1e9,
         (t[1] + t[3]) / (t[0] + t[2]), 'POLY' if wins else 'direct', dev), flush=True)
