@@ -753,6 +753,20 @@ int l2i_linear_rows_bwd_f32(float* gw, float* gb, float* gx, float* ws, const fl
 #define L2I_RANGE_N 259
 int l2i_range_stats(uint64_t* row, const void* x, int64_t n, int kind, void* stream);
 
+/* Panel grids as uint8 on the device (csrc/l2i_panels.hip; the reference's utils/image.py: clip_ims and imgrid).
+ * out [G][GH][GW][C] uint8, channel-last, GH = rows * (H + pad) - pad, GW = cols * (W + pad) - pad: G grids of rows x cols tiles, every tile
+ * padded by `pad` pixels on its bottom and right, the last gutter cropped.  x [N][C][H][W] fp32, C in {1, 3}.  tile_src [G * rows * cols] int32 on
+ * the device, row-major over (grid, tile row, tile column), names the image of each tile; an image may be named by several tiles; any value
+ * outside [0, N) is an empty tile (defined output, nothing read).  A tile pixel is clip_ims in float32 with numpy's operation order,
+ *   t = ((x + 1) * 0.5) * 255 (each operation rounded), clamp to [0, 255], truncate; NaN -> 0,
+ * gutters and empty tiles are `fill` (0..255).  The launch owns out: every byte of it is written exactly once, from its sources alone (out is
+ * never read, so neighbouring tiles may share a dword), and nothing outside it is touched.  out may have any byte alignment (16-byte stores
+ * between its first and last 16-byte boundary, byte stores in front of and behind them), x any 4-byte alignment; every offset is 64-bit.
+ * L2I_E_UNSUPPORTED: another C, pad < 0, fill outside 0..255, a dimension (G, rows, cols, H, W, N) < 1, x off a 4-byte boundary, or a grid side
+ * in bytes, a plane or the tile table beyond 2^30.  L2I_E_ARG: a null pointer.  Nothing is launched then.  Additive: the ABI version did not move. */
+int l2i_panels_u8(uint8_t* out, const float* x, const int32_t* tile_src, int G, int rows, int cols, int C, int H, int W, int pad, int fill, int N,
+                  void* stream);
+
 const char* l2i_last_error(void);
 /* Bumped whenever a struct of this header grows or an entry point changes meaning (1: round 1-2; 2: round 3, l2i_conv_params gained w_bstride /
  * out_f32; 3: round 4: l2i_conv2d_wino4_f32, l2i_sizeof_conv_params; 4: round 5: the l2i_*_h8_f16 entry points, wino4 tile_hint / CoutP % 32; 5: round 5: in_h8 / rgb_* fields, l2i_conv_img_h8; 6: round 6: l2i_nonfinite_flag_f32 / l2i_adam_guarded_f32, mask_out / mask_bits fields, l2i_mask_mul_bits_h8, the mask_bits argument of l2i_upfirdn2d_h8; 7: round 6: l2i_conv1x1_pair_h8, l2i_conv_chain3_h8, l2i_conv1x1_pair_f32, l2i_reg_bce_f32; 8: l2i_face_resize_f32, l2i_face_head_f32; 9: l2i_wino4s_epilogue_class; 10: l2i_gram_loss_f32, l2i_gram_bwd_f32; 11: l2i_gram_loss_h8, l2i_gram_bwd_h8 and their _f16 twins; 12: l2i_sgd_guarded_f32).  The ctypes binding (latent2im_amd/_lib.py) refuses a library whose version or struct size differs from its own mirror. */

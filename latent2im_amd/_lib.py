@@ -207,6 +207,7 @@ _SIGNATURES = {
     'l2i_bn_apply_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_reduce_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_apply_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
+    'l2i_panels_u8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
     'l2i_sizeof_conv_params': (c_i, []),
@@ -223,7 +224,7 @@ TRAIN_H8 = ('l2i_conv2d_wgrad_h8', 'l2i_conv2d_wgrad_ws_h8', 'l2i_bn_ws_h8', 'l2
 # Entry points added without an ABI bump: a library of the same ABI version built before them (L2I_LIB = a parent build, for A/B runs) still loads;
 # has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
 ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for', 'l2i_bn_finalize_f32', 'l2i_bn_bwd_finalize_f32',
-                      'l2i_repack_taps_f32', 'l2i_repack_wino_f32', 'l2i_batch_from_u8_f32', 'l2i_upfirdn2d_dual_f32')
+                      'l2i_repack_taps_f32', 'l2i_repack_wino_f32', 'l2i_batch_from_u8_f32', 'l2i_upfirdn2d_dual_f32', 'l2i_panels_u8')
                      + tuple(n + t for n in TRAIN_H8 for t in ('', '_f16')))
 
 EXPORTS = tuple(_SIGNATURES)

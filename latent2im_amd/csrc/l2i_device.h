@@ -152,4 +152,13 @@ __device__ __forceinline__ T block_max(T v, T* red) {
 }
 __device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }   // magic 0 encodes d == 1; else ceil(2^32 / d)
 
+// ---- image quantisation ---------------------------------------------------------------------------------------------------------------
+// clip_ims in float32 with numpy's operation order (x + 1, / 2, * 255; / 2 is exact), np.clip, then the truncating uint8 cast (l2i_face.hip: the
+// face resize reads its pixels through it; l2i_panels.hip: the panel grids)
+__device__ __forceinline__ int quant8(float v) {
+    float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.0f), 0.5f), 255.0f);
+    t = fminf(fmaxf(t, 0.0f), 255.0f);          // (NaN -> 0)
+    return (int)t;
+}
+
 #endif

@@ -23,13 +23,6 @@ constexpr int FR_ROWS = 16;            // output rows per block
 constexpr int FR_LDS = 48 * 1024;      // bytes of uint8 intermediate rows per block
 constexpr int FR_THREADS = 256;
 
-// clip_ims in float32 with numpy's operation order (x + 1, / 2, * 255; / 2 is exact), np.clip, then the truncating uint8 cast
-__device__ __forceinline__ int quant8(float v) {
-    float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.0f), 0.5f), 255.0f);
-    t = fminf(fmaxf(t, 0.0f), 255.0f);          // (NaN -> 0)
-    return (int)t;
-}
-
 // Resample.c clip8: the 22-bit fixed-point sum back to a byte
 __device__ __forceinline__ int clip8(int acc) {
     if (acc >= (1 << 30)) return 255;

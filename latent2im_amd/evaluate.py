@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import constants, dist, facenet, hostutil
-from .vis import VisOptions
+from .vis import VisOptions, add_precision_flag, resolve_precision
 
 
 def attribute_preservation(multi_attrs, original_attrs, index_):
@@ -53,15 +53,28 @@ def eval_options():
                           help='identity preservation (facenet cosine similarity): auto = when the face checkpoint exists')
     v.parser.add_argument('--facenet_ckpt', type=str, default=None,
                           help='facenet_pytorch InceptionResnetV1 state_dict (vggface2); default constants.facenet_path')
+    add_precision_flag(v.parser)
     return v
 
 
 def main(argv=None, all_batches=False):
-    from . import graph as graph_mod
+    """``--precision``: the generator and the regressor of that precision (so that a walk trained on the 16-bit path is scored on the networks
+    it was trained on); the face network stays fp32 whatever it says (facenet.py runs it under its own fp32 context)."""
+    from . import conv
     v = eval_options()
     opt, conf = v.parse(argv)
     dist.select_gpu(opt.gpu)                         # before the first torch.cuda call (vis_w.py / eval.py set CUDA_VISIBLE_DEVICES)
     dist.init_from_env()
+    saved = conv.PRECISION
+    conv.PRECISION = resolve_precision(opt.precision, conf)       # before the graph is built: load_networks picks the network classes by it
+    try:
+        return _evaluate(opt, conf, all_batches)
+    finally:
+        conv.PRECISION = saved
+
+
+def _evaluate(opt, conf, all_batches):
+    from . import graph as graph_mod
     if getattr(conf, 'synthetic_weights', False):    # the training run's explicit choice travels in its opt.yml
         constants.ALLOW_SYNTHETIC_WEIGHTS = True
     if getattr(conf, 'resolution', None):

@@ -606,6 +606,145 @@ class TransformGraph(WalkGraph):
             written.append(path)
         return written
 
+    # -- inference: several attributes at once, whole sweeps, uint8 grids made on the device ------------------------
+    def _walk_column(self, index):
+        """The walk column of attribute-table index ``index`` (apply_alpha's mapping: the index itself with the full table)."""
+        return index if len(self.attrIdx) == len(self.attrTable) else self.attrIdx.index(index)
+
+    def _combine_delta(self, alpha_org, alpha_to_graph, index_):
+        """transform_base.py:784-790: zero except column k of each index_[k], alpha_to_graph[k][:, 0] - alpha_org[:, col]."""
+        alpha_delta = torch.zeros_like(alpha_org)
+        for k, i in enumerate(index_):
+            col = self._walk_column(i)
+            alpha_delta[:, col] = torch.Tensor(np.asarray(alpha_to_graph[k])[:, 0]).to(self.device) - alpha_org[:, col]
+        return alpha_delta
+
+    def _sweep_delta(self, alpha_org, alpha_to_graph, index_):
+        """alpha_delta of one panel: apply_alpha's for ``index_`` None or an int, apply_alpha_combine's for a list."""
+        if isinstance(index_, (list, tuple)):
+            return self._combine_delta(alpha_org, alpha_to_graph, index_)
+        target = torch.Tensor(np.asarray(alpha_to_graph)).to(self.device)
+        alpha_delta = self.get_alphas(alpha_org, target)
+        if index_ is not None:
+            if len(self.attrIdx) == len(self.attrTable):
+                alpha_delta[:, index_] = target - alpha_org[:, index_]
+            else:
+                i = self.attrIdx.index(index_)
+                alpha_delta[:, i] = torch.Tensor(np.asarray(alpha_to_graph)[:, 0]).to(self.device) - alpha_org[:, i]
+        return alpha_delta
+
+    def apply_alpha_combine(self, graph_inputs, alpha_to_graph, layers=None, name=None, trainEmbed=False, index_=None, given_w=None):
+        """transform_base.py:769-811 (w branch): edit several attributes at once.  ``index_``: attribute-table indices (mapped to walk columns as
+        in apply_alpha), ``alpha_to_graph[k]`` [B, >= 1]: the target of index_[k]; every other attribute keeps a zero delta.  Returns (edited
+        image, alpha_org, original image)."""
+        with torch.no_grad():
+            zs_batch = graph_inputs['z']
+            if not torch.is_tensor(zs_batch):
+                zs_batch = torch.Tensor(zs_batch).to(self.device)
+            latent_w = given_w if given_w is not None else self.get_w(zs_batch)
+            out_zs = self.get_logits({'w': latent_w})
+            alpha_org = self.get_reg_preds(out_zs)
+            alpha_delta = self._combine_delta(alpha_org, alpha_to_graph, index_)
+            latent_w_new = self.get_w_new_tensor(latent_w, alpha_delta, layers=layers, name=name, trainEmbed=trainEmbed, index_=index_)
+            best_im_out = self.get_logits({'w': latent_w_new})
+        return best_im_out, alpha_org, out_zs
+
+    def _sweep(self, graph_inputs, alphas_to_graph, layers=None, given_w=None, index_=None, chunk=None):
+        """sweep's work: (buf [P + 1, B, 3, R, R] fp32 on the device — the P panels, then the original —, alpha_org).  One buffer, so that a
+        panel grid which also shows the original reads all its tiles from one tensor."""
+        with torch.no_grad():
+            zs_batch = graph_inputs['z']
+            if not torch.is_tensor(zs_batch):
+                zs_batch = torch.Tensor(zs_batch).to(self.device)
+            latent_w = given_w if given_w is not None else self.get_w(zs_batch)
+            out_zs = self.get_logits({'w': latent_w})
+            alpha_org = self.get_reg_preds(out_zs)
+            P, B = len(alphas_to_graph), out_zs.shape[0]
+            buf = torch.empty((P + 1,) + tuple(out_zs.shape), device=self.device, dtype=torch.float32)
+            buf[P].copy_(out_zs)
+            chunk = B if chunk is None else int(chunk)
+            if chunk < 1:
+                raise ValueError('sweep: chunk must be >= 1 (got %d)' % chunk)
+            new_ws = (self.get_w_new_tensor(latent_w, self._sweep_delta(alpha_org, ag, index_), layers=layers, index_=index_) for ag in alphas_to_graph)
+            if chunk == B:                                     # one panel per generator call: apply_alpha's launches
+                for p, w_new in enumerate(new_ws):
+                    buf[p].copy_(self.get_logits({'w': w_new}))
+            else:
+                ws = torch.cat([torch.stack(list(w_new)) for w_new in new_ws], 1)          # [n_latent, P * B, dim_z], panel-major
+                flat = buf[:P].view((P * B,) + tuple(out_zs.shape[1:]))
+                for s in range(0, P * B, chunk):
+                    flat[s:s + chunk].copy_(self.get_logits({'w': ws[:, s:s + chunk]}))
+        return buf, alpha_org
+
+    def sweep(self, graph_inputs, alphas_to_graph, layers=None, given_w=None, index_=None, chunk=None):
+        """Every panel of an alpha sweep from one pass over the original: returns (panels [P, B, 3, R, R] fp32 on the device, alpha_org, out_zs).
+        panels[p] is what ``apply_alpha(graph_inputs, alphas_to_graph[p], index_=index_)`` returns (``index_`` None or an int), or
+        ``apply_alpha_combine(graph_inputs, alphas_to_graph[p], index_=index_)`` (``index_`` a list, every alphas_to_graph[p] a list with one
+        target per index); get_w, the original image and its regressor pass run once instead of once per panel (P + 1 generator passes for
+        2P).  The generator runs ``chunk`` images a call; the default, B, is one panel a call: the launches of apply_alpha, bit for bit."""
+        buf, alpha_org = self._sweep(graph_inputs, alphas_to_graph, layers=layers, given_w=given_w, index_=index_, chunk=chunk)
+        return buf[:-1], alpha_org, buf[-1]
+
+    @staticmethod
+    def _save_png(arr, path):
+        from PIL import Image
+        print('Save in ', path)
+        Image.fromarray(arr).save(path)
+        return path
+
+    def vis_sweep_strips(self, graph_inputs, filename, alphas_to_graph, alphas_to_target, batch_start, layers=None, name=None, wgt=False,
+                         given_w=None, index_=None, pad=0, chunk=None):
+        """vis_multi_image_batch_alphas from one ``sweep`` and one l2i_panels_u8 launch: the same file names, one strip of P panels per sample
+        (``pad`` > 0: imgrid's white gutters between them), quantised and laid out on the device and copied to the host once, as uint8.
+        ``index_`` None or an int: apply_alpha's panels (an int still moves every attribute of the walk, as in the reference); a list: only the
+        listed attributes move, every other one keeps a zero delta (apply_alpha_combine with the panel's alpha for each of them)."""
+        from . import kernels
+        only = isinstance(index_, (list, tuple))                # move these attributes alone, all of them to the panel's alpha
+        if only:
+            alphas_to_graph = [[ag] * len(index_) for ag in alphas_to_graph]
+        buf, alpha_org = self._sweep(graph_inputs, alphas_to_graph, layers=layers, given_w=given_w, index_=index_, chunk=chunk)
+        P, B = buf.shape[0] - 1, buf.shape[1]
+        shown = index_[0] if only else index_                   # the attribute whose original value names the file
+        tiles = [p * B + ii for ii in range(B) for p in range(P)]
+        strips = kernels.panels_u8(buf.view((-1,) + tuple(buf.shape[2:])), tiles, B, 1, P, pad=pad, fill=255).cpu().numpy()
+        written = []
+        for ii in range(B):
+            a = alpha_org[ii, self._walk_column(shown)].item() if (shown is not None and len(self.attrList) > 1) else alpha_org[ii].reshape(-1)[0].item()
+            path = filename + '_sample{}'.format(ii + batch_start) + ('_wgt' if wgt else '') + '_%.2f.png' % a
+            written.append(self._save_png(strips[ii], path))
+        return written
+
+    def vis_multi_image_batch_alphas_combine(self, graph_inputs, filename, alphas_to_graph, alphas_to_target, batch_start, layers=None,
+                                             name=None, given_w=None, index_=None, pad=1):
+        """transform_base.py:814-869, the paper's two-attribute figure: one PNG per sample, a P x P grid whose row follows index_[0]'s alpha and
+        whose column follows index_[1]'s, with imgrid's white gutters of ``pad`` pixels; file ``<filename>_idx{a}_idx{b}_sample{i}.png``, and
+        ``org_img/<same>_org.png`` for the unedited image.  One ``sweep`` of the P * P panels and one l2i_panels_u8 launch per batch (the
+        originals ride in a spare tile column that is cut off on the host), then one device-to-host copy of uint8.  Returns the written paths.
+        Two differences from the reference: it writes the grid as P separate strips (one file per row, the row's alpha in the name), here the
+        grid is one file; and it saves the original as a JPEG through torchvision, here it is a PNG of the same clip_ims bytes."""
+        from . import kernels
+        if index_ is None or len(index_) != 2:
+            raise ValueError('vis_multi_image_batch_alphas_combine: index_ names two attributes (got %r)' % (index_,))
+        P = len(alphas_to_graph)
+        pairs = [[ag1, ag2] for ag1 in alphas_to_graph for ag2 in alphas_to_graph]
+        buf, _ = self._sweep(graph_inputs, pairs, layers=layers, given_w=given_w, index_=list(index_))
+        B, R = buf.shape[1], buf.shape[-1]
+        tiles = []
+        for ii in range(B):
+            for r in range(P):
+                tiles += [(r * P + c) * B + ii for c in range(P)] + [P * P * B + ii if r == 0 else -1]
+        grids = kernels.panels_u8(buf.view((-1,) + tuple(buf.shape[2:])), tiles, B, P, P + 1, pad=pad, fill=255).cpu().numpy()
+        side = P * (R + pad) - pad
+        org_dir = os.path.join(os.path.dirname(filename), 'org_img')
+        os.makedirs(org_dir, exist_ok=True)
+        written = []
+        for ii in range(B):
+            stem = filename + '_idx{}_idx{}_sample{}'.format(index_[0], index_[1], ii + batch_start)
+            written.append(self._save_png(np.ascontiguousarray(grids[ii, :, :side]), stem + '.png'))
+            written.append(self._save_png(np.ascontiguousarray(grids[ii, :R, side + pad:side + pad + R]),
+                                          os.path.join(org_dir, os.path.basename(stem) + '_org.png')))
+        return written
+
     def vis_multi_image_batch_alphas_compute_multi_attr(self, graph_inputs, filename, alphas_to_graph, alphas_to_target,
                                                         batch_start, layers=None, name=None, wgt=False, wmask=False,
                                                         trainEmbed=False, computeL2=False, given_w=None, index_=None):

@@ -329,3 +329,27 @@ def face_head(feat, w_t, bias, npairs=0):
     _lib.call('l2i_face_head_f32', _lib.fptr(emb), _lib.ptr(dist), _lib.fptr(feat), _lib.fptr(w_t), _lib.fptr(bias), b, c,
               feat[0, 0].numel(), e, int(npairs))
     return emb, dist
+
+
+def panels_grid_hw(rows, cols, h, w, pad):
+    """(GH, GW) of one l2i_panels_u8 grid: imgrid's size, every tile padded on its bottom and right and the last gutter cropped."""
+    return rows * (h + pad) - pad, cols * (w + pad) - pad
+
+
+def panels_u8(x, tile_src, G, rows, cols, pad=0, fill=0, out=None):
+    """l2i_panels_u8: x [N, C, H, W] fp32 (C in {1, 3}) -> G channel-last uint8 grids [G, GH, GW, C] of rows x cols tiles on the device, one
+    launch: clip_ims (the reference's float32 quantiser, bit for bit) and imgrid (``pad`` pixels of ``fill`` below and right of every tile, the
+    last gutter cropped).  tile_src: int32 [G * rows * cols] on the device (or a sequence of ints), the image of each tile, row-major over
+    (grid, tile row, tile column); an index outside [0, N) is an empty tile of ``fill``.  ``out``: a contiguous uint8 tensor of that size, at any
+    byte alignment; every byte of it is written."""
+    x = x.contiguous()
+    n, c, h, w = x.shape
+    if not torch.is_tensor(tile_src):
+        tile_src = torch.tensor(list(tile_src), dtype=torch.int32, device=x.device)
+    assert tile_src.dtype == torch.int32 and tile_src.numel() == G * rows * cols
+    gh, gw = panels_grid_hw(rows, cols, h, w, pad)
+    if out is None:
+        out = torch.empty(G, gh, gw, c, device=x.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.numel() == G * gh * gw * c
+    _lib.call('l2i_panels_u8', _lib.ptr(out), _lib.fptr(x), _lib.ptr(tile_src), int(G), int(rows), int(cols), c, h, w, int(pad), int(fill), n)
+    return out

@@ -28,18 +28,27 @@ def _configure_logging(path, append=False):
 
 
 def make_samples(img_tensor, output_dir, epoch, optim_iter, batch_size, pre_path='results', name='test'):
-    """PNG grid of a batch (train.py:137-144); off the timed path (every save_freq iterations)."""
+    """PNG grid of a batch (train.py:137-144), every save_freq iterations.  A batch on the GPU is quantised and laid out there by one
+    l2i_panels_u8 launch and crosses to the host as the finished uint8 grid (1 byte a value instead of 4, no numpy pass on the training thread);
+    a CPU tensor, or a library without that entry point, takes the host path.  The same pixels either way."""
     from PIL import Image
+    from . import _lib
+    cols = max(int(math.sqrt(batch_size)), 1)
+    rows = (img_tensor.shape[0] + cols - 1) // cols
+    path = '{}/{}/{}_{}_{}.png'.format(output_dir, pre_path, epoch, optim_iter, name)
+    if img_tensor.is_cuda and img_tensor.shape[1] == 3 and _lib.has('l2i_panels_u8'):
+        from . import kernels
+        grid = kernels.panels_u8(img_tensor.detach().float(), range(rows * cols), 1, rows, cols, pad=0, fill=0)[0].cpu().numpy()
+        Image.fromarray(grid).save(path)
+        return
     img = img_tensor.detach().cpu().numpy()
     img = np.uint8(np.clip(((img + 1) / 2.0) * 255, 0, 255)).transpose(0, 2, 3, 1)
-    cols = max(int(math.sqrt(batch_size)), 1)
-    rows = (img.shape[0] + cols - 1) // cols
     h, w = img.shape[1], img.shape[2]
     grid = np.zeros((rows * h, cols * w, 3), np.uint8)
     for i in range(img.shape[0]):
         r, c = divmod(i, cols)
         grid[r * h:(r + 1) * h, c * w:(c + 1) * w] = img[i]
-    Image.fromarray(grid).save('{}/{}/{}_{}_{}.png'.format(output_dir, pre_path, epoch, optim_iter, name))
+    Image.fromarray(grid).save(path)
 
 
 def train_step(graphs, zs_batch, attrList, layers=None, trainEmbed=False, updateGAN=False, opt=None, multi_attr=False):
