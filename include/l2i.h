@@ -711,6 +711,45 @@ int l2i_bn_bwd_apply_h8(void* dx, void* dy_masked, const void* gy, const void* o
 int l2i_bn_bwd_apply_h8_f16(void* dx, void* dy_masked, const void* gy, const void* out_mask, const void* x, const float* mean, const float* invstd,
                             const float* gamma, const float* mean_dy, const float* mean_dyxh, int B, int C, int64_t HW, void* stream);
 
+/* ---- [ABI 12, additive] The 16-bit trainer's stem gradient and its weight planes (csrc/l2i_train_h8.hip; bf16 elements, IEEE fp16 with _f16) --------
+ * l2i_conv2d_wgrad_img_h8: dw[co,ci,ky,kx] = sum_{b,oy,ox} gy[b,co,oy,ox] * x[b,ci,2 oy+ky-3,2 ox+kx-3] for the 7x7 / stride 2 / pad 3 stem.  x is
+ *   the fp32 NCHW image [B][3][H][W] and enters the products as the fp32 value it is (reads in the padding give 0); gy is an h8 map
+ *   [B][8][OH][OW][8] on a 16-byte boundary, OH = (H-1)/2+1, OW = (W-1)/2+1; dw fp32 [64][3][7][7] is OVERWRITTEN, in the units of gy (no scale).
+ *   v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation in a fixed order (pixel pairs of a wave, the four waves of a block, then the
+ *   pixel slices in slice order through ws): no atomics, equal inputs give equal bits.  Built for Cin == 3, Cout == 64, K == 7, stride == 2,
+ *   pad == 3, any H, W >= 1, x and gy below 4 GiB each: everything else, a NULL ws and a ws smaller than the query's answer return
+ *   L2I_E_UNSUPPORTED, a NULL tensor or a misaligned pointer L2I_E_ARG, with a message; nothing is launched then.
+ * l2i_conv2d_wgrad_img_ws_h8 (host only): *bytes = the workspace of the shape = slices * L2I_WGRAD_IMG_SLICE_BYTES (0 and L2I_E_UNSUPPORTED for a
+ *   refused shape).
+ * l2i_repack_planes_h8: every 16-bit weight plane set of a net, rewritten in place from fp32 weights by ONE launch on `stream`.  `table` (device,
+ *   8-byte aligned): nseg rows of eight int64 — destination (device address, 16-byte aligned), weight (device address of fp32
+ *   [Cout][Cin][K][K]), Cout, Cin, K, mode, contraction padding qpad, first block of the segment (ascending, row 0 = 0); `nblocks` = grid size
+ *   (blocks of a segment = the next row's first block - its own, each at least 1; they walk the segment grid-stride).
+ *     mode L2I_PLANES_FWD   dst [ceil(Cin/qpad)*qpad/16][K*K][2][ceil32(Cout)][8], qpad in {16, 32}:
+ *                           element (g, t, half, co, e) = rnd(w[co][16g+8half+e][t/K][t%K])
+ *     mode L2I_PLANES_SWAP  the same with co and ci exchanged (dst [ceil32(Cout)/16][K*K][2][ceil32(Cin)][8]; qpad 32): the input-gradient planes of
+ *                           stride-2 and transposed layers
+ *     mode L2I_PLANES_FLIP  exchanged and the taps reversed (t -> K*K-1-t; qpad 32): the input-gradient planes of stride-1 layers
+ *     mode L2I_PLANES_IMG   l2i_conv_img_h8's planes for Cin <= 4, K <= 8: dst [ceil(Cin*K/2)][1][2][ceil32(Cout)][8],
+ *                           element (s, half, co, e) = rnd(w[co][c][ky][e]) with (c, ky) = divmod(2s+half, K)
+ *   Every slot of dst is written; padding rows, padding channels and e >= K are zeros.  rnd = round to nearest even to the element type
+ *   (subnormals kept, overflow to inf).  One lane writes one 16-byte slot; nothing is allocated.  The table lives on the device and is not read by
+ *   the host: its rows are the caller's responsibility (conv.PlaneTable builds and checks them).  A NULL or misaligned table, nseg < 1 or
+ *   nblocks < nseg return L2I_E_ARG and launch nothing. */
+#define L2I_WGRAD_IMG_SLICE_BYTES (64 * 160 * 4)
+#define L2I_PLANES_FWD 0
+#define L2I_PLANES_SWAP 1
+#define L2I_PLANES_FLIP 2
+#define L2I_PLANES_IMG 3
+int l2i_conv2d_wgrad_img_h8(float* dw, const float* x, const void* gy, float* ws, int64_t ws_bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW,
+                            int K, int stride, int pad, void* stream);
+int l2i_conv2d_wgrad_img_h8_f16(float* dw, const float* x, const void* gy, float* ws, int64_t ws_bytes, int B, int Cin, int H, int W, int Cout, int OH,
+                                int OW, int K, int stride, int pad, void* stream);
+int l2i_conv2d_wgrad_img_ws_h8(int64_t* bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad);
+int l2i_conv2d_wgrad_img_ws_h8_f16(int64_t* bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad);
+int l2i_repack_planes_h8(const void* table, int nseg, int nblocks, void* stream);
+int l2i_repack_planes_h8_f16(const void* table, int nseg, int nblocks, void* stream);
+
 /* ---- [ABI 12, additive] the linear layers of the PGGAN graph's MLP walk (csrc/l2i_walk.hip; WalkMlpZ3, graphs/pggan/transform_base.py:167-188) ------
  * Skinny products on plain fp32 VALU: B rows (any B >= 1, taken in chunks of at most 16) against W in nn.Linear's own [N = out, K = in] layout.
  * l2i_linear_rows_f32:      y[B, N] = epi(x[B, K] W^T + bias[N]).  epi = L2I_LINEAR_NONE; L2I_LINEAR_LRELU: v > 0 ? v : v * slope; L2I_LINEAR_WALK: the

@@ -207,6 +207,9 @@ _SIGNATURES = {
     'l2i_bn_apply_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_reduce_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_l, c_p]),
     'l2i_bn_bwd_apply_h8': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_p]),
+    'l2i_conv2d_wgrad_img_h8': (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'l2i_conv2d_wgrad_img_ws_h8': (c_i, [ctypes.POINTER(c_l), c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    'l2i_repack_planes_h8': (c_i, [c_p, c_i, c_i, c_p]),
     'l2i_panels_u8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_last_error': (ctypes.c_char_p, []),
     'l2i_abi_version': (c_i, []),
@@ -221,11 +224,15 @@ for _n in [k for k in _SIGNATURES if k in _F16_TWINS]:
 ABI_VERSION = 12         # L2I_ABI_VERSION of include/l2i.h this binding mirrors
 # csrc/l2i_train_h8.hip: the weight gradient and the training-mode BatchNorm on h8 maps, and their two host-only workspace queries
 TRAIN_H8 = ('l2i_conv2d_wgrad_h8', 'l2i_conv2d_wgrad_ws_h8', 'l2i_bn_ws_h8', 'l2i_bn_stats_h8', 'l2i_bn_apply_h8', 'l2i_bn_bwd_reduce_h8', 'l2i_bn_bwd_apply_h8')
+# the same file's later additions: the stem's weight gradient from the fp32 image (fixed summation order) with its host-only workspace query, and the
+# in-place repack of every 16-bit weight plane of a net in one launch.  Without them (a library built before them) the 16-bit trainer keeps the
+# fp32 atomics kernel for conv1 and the torch repack.
+TRAIN_H8_STEM = ('l2i_conv2d_wgrad_img_h8', 'l2i_conv2d_wgrad_img_ws_h8', 'l2i_repack_planes_h8')
 # Entry points added without an ABI bump: a library of the same ABI version built before them (L2I_LIB = a parent build, for A/B runs) still loads;
 # has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
 ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for', 'l2i_bn_finalize_f32', 'l2i_bn_bwd_finalize_f32',
                       'l2i_repack_taps_f32', 'l2i_repack_wino_f32', 'l2i_batch_from_u8_f32', 'l2i_upfirdn2d_dual_f32', 'l2i_panels_u8')
-                     + tuple(n + t for n in TRAIN_H8 for t in ('', '_f16')))
+                     + tuple(n + t for n in TRAIN_H8 + TRAIN_H8_STEM for t in ('', '_f16')))
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -174,7 +174,8 @@ class CapturedZStep(_CapturedWalkStep):
 
 
 class CapturedRegressorStep(_StagedInputs):
-    """One optimiser step of the attribute regressor (regressor_train.train_step_resident on a resident TrainableResNet50) recorded into ONE
+    """One optimiser step of the attribute regressor (regressor_train.train_step_resident on a resident TrainableResNet50, or on the 16-bit
+    TrainableResNet50H8 of a library with l2i_repack_planes_h8: its loss scaler then runs inside the graph as well) recorded into ONE
     stream of one hipGraph: (gather,) forward, loss, backward, guarded Adam, in-place repack.  The optimiser is inside the graph because its
     state is on the device (optim.GuardedAdam: counters included) and its table of pointers never changes (the model's gradient arena);
     ``record``'s rule holds: the warm-up runs forward, loss and backward only — no update, no repack, and the BatchNorm running statistics
@@ -190,6 +191,8 @@ class CapturedRegressorStep(_StagedInputs):
             raise ValueError('CapturedRegressorStep records a resident model (TrainableResNet50(..., resident=True))')
         if not hasattr(optimizer, 'init_state'):
             raise ValueError('CapturedRegressorStep records a device-side optimiser (regressor_train.make_optimizer(model, guarded=True))')
+        if getattr(model, 'planes_kernel', True) is False or getattr(model, 'stem_kernel', True) is False:
+            raise ValueError('CapturedRegressorStep: this library repacks the 16-bit planes with torch ops that allocate; it cannot be recorded')
         optimizer.init_state()                                             # moments, counters and guard words outside the graph's pool
         self.model, self.optimizer, self.dataset, self.batch = model, optimizer, dataset, batch
         n_out = model.fc_w.shape[0]

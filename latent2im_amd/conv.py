@@ -755,6 +755,61 @@ def pack_weight_img_h8(w, dtype=None):
     return pack_weight_h8(rows.reshape(cout, 16 * ns, 1, 1), cin_pad=16, dtype=dtype)
 
 
+PLANES_FWD, PLANES_SWAP, PLANES_FLIP, PLANES_IMG = 0, 1, 2, 3      # L2I_PLANES_*: the modes of l2i_repack_planes_h8
+
+
+def plane_set_shape(cout, cin, k, mode, qpad=32):
+    """The shape [groups][taps][2][rows padded to 32][8] of the 16-bit plane set l2i_repack_planes_h8 writes for a [cout, cin, k, k] weight."""
+    if mode == PLANES_IMG:
+        return ((cin * k + 1) // 2, 1, 2, (cout + 31) // 32 * 32, 8)
+    rows, contr = (cout, cin) if mode == PLANES_FWD else (cin, cout)
+    return ((contr + qpad - 1) // qpad * qpad // 16, k * k, 2, (rows + 31) // 32 * 32, 8)
+
+
+class PlaneTable:
+    """The device table of l2i_repack_planes_h8 over ``segments`` = [(planes, weight, mode, qpad)]: ``run()`` rewrites every plane set in place from
+    its fp32 weight with ONE launch on the current stream (no allocation, no pointer moves: a captured graph replays it).  The table holds raw
+    addresses, so it is valid for as long as the tensors it was built from stay where they are — they are kept alive here; an optimiser that
+    updates the weights in place and planes that are only ever rewritten in place never invalidate it.  The rows are checked here, on the host:
+    the library does not read the table."""
+    BLOCK_SLOTS, MAX_BLOCKS = 256, 1024                  # slots per block and pass; blocks of one segment at most (grid-stride beyond)
+
+    def __init__(self, segments, dtype):
+        assert segments and dtype in (torch.float16, torch.bfloat16), dtype
+        rows, first = [], 0
+        dev = segments[0][0].device
+        for planes, weight, mode, qpad in segments:
+            cout, cin, k, k2 = weight.shape
+            if weight.dtype != torch.float32 or not weight.is_cuda or not weight.is_contiguous() or k != k2 or weight.device != dev:
+                raise _lib.L2IError('PlaneTable takes contiguous float32 [Cout, Cin, K, K] weights on the device of the planes')
+            if mode not in (PLANES_FWD, PLANES_SWAP, PLANES_FLIP, PLANES_IMG) or (mode == PLANES_FWD and qpad not in (16, 32)) or (
+                    mode in (PLANES_SWAP, PLANES_FLIP) and qpad != 32) or (mode == PLANES_IMG and (cin > 4 or k > 8)):
+                raise _lib.L2IError('PlaneTable: mode %r with contraction padding %r on a %s weight' % (mode, qpad, tuple(weight.shape)))
+            shape = plane_set_shape(cout, cin, k, mode, qpad)
+            if (tuple(planes.shape) != shape or planes.element_size() != 2 or not planes.is_cuda or not planes.is_contiguous() or planes.device != dev
+                    or planes.data_ptr() % 16):
+                raise _lib.L2IError('PlaneTable: planes %s (%s) where mode %d of a %s weight writes 16-bit %s on a 16-byte boundary'
+                                    % (tuple(planes.shape), planes.dtype, mode, tuple(weight.shape), shape))
+            slots = planes.numel() // 8
+            rows.append([planes.data_ptr(), weight.data_ptr(), cout, cin, k, mode, qpad, first])
+            first += max(1, min((slots + self.BLOCK_SLOTS - 1) // self.BLOCK_SLOTS, self.MAX_BLOCKS))
+        self.dtype, self.nseg, self.nblocks, self.segments = dtype, len(rows), first, list(segments)
+        self.slots = sum(p.numel() // 8 for p, _, _, _ in segments)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
+
+    def run(self):
+        _lib.call('l2i_repack_planes_h8', _lib.ptr(self.table), self.nseg, self.nblocks, dtype=self.dtype)
+
+
+def _repack_planes_(self, weight):
+    """``repack_`` of ImgConvH8 / H8Conv: the object's planes rewritten in place from ``weight`` (l2i_repack_planes_h8; the table is built once
+    per weight tensor)."""
+    if self._table is None or self._table.segments[0][1].data_ptr() != weight.data_ptr():
+        self._table = PlaneTable(self.segments(weight), self.dtype)
+    self._table.run()
+    return self
+
+
 class ImgConvH8:
     """[r5] An image-side convolution of the 16-bit path (csrc/l2i_img_h8.hip): fp32 NCHW image in, h8 map out; forward only (the input gradients
     land on the fp32 image through the generic kernels: H8Conv.dgrad(out_f32=True), FrozenConv2d.dgrad_h8in)."""
@@ -765,6 +820,7 @@ class ImgConvH8:
         assert (self.k, stride) in ((1, 1), (3, 1), (7, 2)) and self.cout % 8 == 0, (self.k, stride, self.cout)
         self.stride, self.padding, self.device = stride, padding, device
         self.dtype = dtype or h8_dtype()
+        self._table = None
         self.repack(w)
 
     def repack(self, weight):
@@ -773,6 +829,13 @@ class ImgConvH8:
         w = _weight_f32(weight)
         assert tuple(w.shape) == (self.cout, self.cin, self.k, self.k), tuple(w.shape)
         self.planes = pack_weight_img_h8(w, dtype=self.dtype).to(self.device)
+
+    def segments(self, weight):
+        """This object's rows of a PlaneTable that packs from ``weight`` (contiguous float32 on the device of the planes)."""
+        assert tuple(weight.shape) == (self.cout, self.cin, self.k, self.k), tuple(weight.shape)
+        return [(self.planes, weight, PLANES_IMG, 16)]
+
+    repack_ = _repack_planes_          # ``planes`` rewritten where it lies (bit-equal to ``repack``): its pointer stays, a captured graph replays it
 
     def out_hw(self, h, w):
         return (h + 2 * self.padding - self.k) // self.stride + 1, (w + 2 * self.padding - self.k) // self.stride + 1
@@ -801,6 +864,7 @@ class H8Conv:
         assert cin_pad == 32 or (cin_pad == 16 and self.k == 3 and stride == 1 and not transposed), 'a 16-channel chunk exists for 3x3 stride-1 layers only'
         self.cinp, self.coutp_in = (self.cin + cin_pad - 1) // cin_pad * cin_pad, (self.cout + 31) // 32 * 32
         self.dtype = dtype or h8_dtype()                              # element type of the weight planes: the maps it is called with must have it
+        self._table = None
         self.repack(w)                                                # (packed on the host)
         self.fwd_planes, self.bwd_planes = self.fwd_planes.to(device), self.bwd_planes.to(device)
 
@@ -812,6 +876,15 @@ class H8Conv:
         self.fwd_planes = pack_weight_h8(weight, self.cin_pad, dtype=self.dtype)
         # transposed fwd: dx = corr_s2(gy, wt); stride-2 fwd: dx = transposed(gy, wt); stride 1: the correlation with the flipped taps
         self.bwd_planes = pack_weight_h8(wt if self.transposed or self.stride == 2 else torch.flip(wt, [2, 3]), dtype=self.dtype)
+
+    def segments(self, weight):
+        """This object's rows of a PlaneTable that packs from ``weight`` (contiguous float32 on the device of the planes): the forward planes, and
+        the input-gradient planes with the roles of the channel axes exchanged (stride 1: and the taps reversed)."""
+        assert tuple(weight.shape) == (self.cout, self.cin, self.k, self.k), tuple(weight.shape)
+        return [(self.fwd_planes, weight, PLANES_FWD, self.cin_pad),
+                (self.bwd_planes, weight, PLANES_SWAP if self.transposed or self.stride == 2 else PLANES_FLIP, 32)]
+
+    repack_ = _repack_planes_          # ``fwd_planes`` and ``bwd_planes`` rewritten where they lie (bit-equal to ``repack``): one launch, pointers stay
 
     def out_hw(self, h, w):
         if self.transposed:

@@ -1,6 +1,6 @@
 // l2i_train_h8.hip — what TRAINING a conv net needs on 16-bit h8 maps [B][C/8][H][W][8] (gfx950): the weight gradient of a convolution and
 // training-mode BatchNorm.  Entry points l2i_conv2d_wgrad_h8, l2i_conv2d_wgrad_ws_h8, l2i_bn_stats_h8, l2i_bn_apply_h8, l2i_bn_bwd_reduce_h8,
-// l2i_bn_bwd_apply_h8, l2i_bn_ws_h8 and, compiled with -DL2I_H8_F16, their _f16 twins (include/l2i.h).  The fp32 relatives are in l2i_train.hip;
+// l2i_bn_bwd_apply_h8, l2i_bn_ws_h8, l2i_conv2d_wgrad_img_h8, l2i_conv2d_wgrad_img_ws_h8, l2i_repack_planes_h8 and, compiled with -DL2I_H8_F16, their _f16 twins (include/l2i.h).  The fp32 relatives are in l2i_train.hip;
 // l2i_bn_finalize_f32 / l2i_bn_bwd_finalize_f32 of that file do the [C]-sized algebra for both.  No floating-point atomics anywhere: every sum has
 // a fixed order, equal inputs give equal bits; nothing is allocated, the caller passes the workspaces (sizes: the two host-only *_ws_h8 queries).
 //
@@ -23,6 +23,22 @@
 // BatchNorm.  A lane owns one 16-byte slot (8 channels of one pixel), a block one channel group; the grid's other dimensions are pixel blocks and,
 // for the two apply kernels, the sample: no index is ever divided.  The two reductions sum in float64 per lane, then lanes, waves (fixed tree) and
 // write one row of 16 partials per block; bn_finish_h8_kernel adds the rows in block order into the [C] sums l2i_bn_finalize_f32 reads.
+//
+// Stem weight gradient (l2i_conv2d_wgrad_img_h8, l2i_conv2d_wgrad_img_ws_h8).  conv1 of the regressor reads the fp32 IMAGE, so its gradient
+// dw[co][ci][ky][kx] = sum_{b,oy,ox} gy[b,co,oy,ox] * x[b,ci,2 oy+ky-3,2 ox+kx-3] pairs an h8 map with fp32 NCHW: a 64 x 147 GEMM over the pixels with
+// x taken as the fp32 value it is.  v_mfma_f32_32x32x2_f32 multiplies fp32 exactly and accumulates like an fmaf chain; gy is converted on load (exact).
+//   slice    (sample, range of output rows, block of 128 output columns): one block.  It walks its rows in tiles of 4: the image strip a tile needs,
+//            3 x 13 x 261 fp32 zero-padded, is staged once in LDS (40.7 KB) and every tap of every pixel reads it from there; gy goes through LDS one
+//            output row at a time (8 channel-group planes of 128 slots, 16.6 KB, planes 32 bytes apart in bank so that the 2-byte reads do not collide).
+//   product  a wave owns every fourth PAIR of pixels of the row; the lane halves are the two pixels (K = 2).  A = gy[co = 32 m + lane % 32], B = the
+//            image at tap n = 32 t + lane % 32 (n = ci * 49 + ky * 7 + kx; n >= 147 and pixels past the row feed zeros): 2 x 5 MFMAs into ten 32 x 32
+//            accumulators, 160 registers, 57.6 KB of LDS: two blocks per CU, no scratch.
+//   sum      the four waves' tiles are added in wave order in LDS into the slice's [64][160] tile of the workspace; wgrad_img_reduce_kernel adds the
+//            slices in slice order and OVERWRITES dw.  The slice count (wgrad_img_plan) aims at 512 blocks, two per CU.
+//
+// Weight planes (l2i_repack_planes_h8).  Every 16-bit plane set of a net that is being trained, rewritten IN PLACE from the fp32 master weights by
+// one launch: a device table of segments (destination, weight, sizes, mode, contraction padding, first block), one lane per 16-byte slot, every slot
+// of a destination written (padding = zeros), conversions = the packing convert of the path (round to nearest even, subnormals kept, overflow to inf).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "l2i.h"
@@ -322,6 +338,214 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_h8_kernel(u32x4* __restrict_
     }
 }
 
+// ---- the stem's weight gradient: fp32 image x h8 gradient map ------------------------------------------------------------------------------------------
+namespace wi {
+constexpr int R = 4;                       // output rows per staged image tile
+constexpr int CW = 128;                    // output columns per slice
+constexpr int XH = 2 * R + 5;              // image rows of a tile
+constexpr int XP = 2 * CW + 5;             // image columns of a tile = the row pitch in floats (odd: taps of neighbouring rows fall in different banks)
+constexpr int NT = 147;                    // 3 x 7 x 7 taps
+constexpr int NTP = 160;                   // ... in five MFMA tiles
+constexpr int CO = 64;
+constexpr int TILE = CO * NTP;             // floats of a slice's partial tile
+constexpr int GP = CW * 16 + 32;           // bytes between the staged channel-group planes of gy
+constexpr int G_OFF = TILE * 4;            // the image tile (3 * XH * XP * 4 = 40716 bytes), afterwards the partial tile, lie in front of gy
+constexpr int LDS = G_OFF + 8 * GP;
+constexpr int TARGET_BLOCKS = 512;
+static_assert(3 * XH * XP * 4 <= G_OFF, "the image tile must fit in front of the gy planes");
+}
+
+struct WgradImg {
+    const float* x; const void* gy; float* ws;
+    int H, W, OH, OW, ncb, nrs, rows_per;
+};
+
+__global__ __launch_bounds__(256, 2) void wgrad_img_partial_kernel(const WgradImg p) {
+    using namespace wi;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* xs = reinterpret_cast<float*>(smem);
+    char* gs = smem + G_OFF;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, r = lane & 31;
+    int s = blockIdx.x;
+    const int cb = s % p.ncb;
+    s /= p.ncb;
+    const int rs = s % p.nrs, b = s / p.nrs;
+    const int ox0 = cb * CW, cw = min(CW, p.OW - ox0);
+    const int oy_begin = rs * p.rows_per, oy_end = min(p.OH, oy_begin + p.rows_per);
+    int toff[5];
+    bool tlive[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+        const int n = 32 * t + r;
+        tlive[t] = n < NT;
+        const int ci = n / 49, rem = n - ci * 49, ky = rem / 7, kx = rem - ky * 7;
+        toff[t] = tlive[t] ? (ci * XH + ky) * XP + kx : 0;
+    }
+    f32x16 acc[2][5];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 5; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[m][t][e] = 0.f;
+    const u32x4* gyp = reinterpret_cast<const u32x4*>(p.gy);
+
+    for (int ty = oy_begin; ty < oy_end; ty += R) {
+        const int nr = min(R, oy_end - ty);
+        const int iy0 = 2 * ty - 3, ix0 = 2 * ox0 - 3, nrow = 2 * nr + 5, ncol = 2 * cw + 5;
+        __syncthreads();                           // the previous tile has been read
+        for (int row = wave; row < 3 * nrow; row += 4) {
+            const int c = row / nrow, rr = row - c * nrow, iy = iy0 + rr;
+            const bool yin = iy >= 0 && iy < p.H;
+            const float* src = p.x + (((size_t)b * 3 + c) * p.H + (yin ? iy : 0)) * p.W;
+            float* dst = xs + (c * XH + rr) * XP;
+            for (int cc = lane; cc < ncol; cc += 64) {
+                const int ix = ix0 + cc;
+                dst[cc] = (yin && ix >= 0 && ix < p.W) ? src[ix] : 0.f;
+            }
+        }
+        for (int ry = 0; ry < nr; ++ry) {
+            if (ry) __syncthreads();               // the previous row of gy has been read
+            const size_t grow = (size_t)(ty + ry) * p.OW + ox0;
+#pragma unroll
+            for (int i = 0; i < 8 * CW / 256; ++i) {
+                const int sl = tid + 256 * i, cg = sl / CW, ox = sl - cg * CW;
+                if (ox < cw) *reinterpret_cast<u32x4*>(gs + cg * GP + ox * 16) = gyp[((size_t)b * 8 + cg) * p.OH * p.OW + grow + ox];
+            }
+            __syncthreads();
+            const float* xrow = xs + 2 * ry * XP;
+            for (int pp = wave; 2 * pp < cw; pp += 4) {
+                const int px = 2 * pp + half;
+                const bool live = px < cw;
+                const int pxs = live ? px : 0;
+                float a[2];
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const int co = 32 * m + r;
+                    const unsigned h = *reinterpret_cast<const unsigned short*>(gs + (co >> 3) * GP + pxs * 16 + (co & 7) * 2);
+                    a[m] = live ? h8_lo(h) : 0.f;
+                }
+                const float* xb = xrow + 2 * pxs;
+#pragma unroll
+                for (int t = 0; t < 5; ++t) {
+                    const float xv = xb[toff[t]];
+                    const float bv = (live && tlive[t]) ? xv : 0.f;
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], bv, acc[m][t], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // the four waves' tiles in wave order.  D[i][j]: lane column j = tap, register e -> output channel (e & 3) + 8 (e >> 2) + 4 half
+    __syncthreads();
+    float* tile = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 5; ++t)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        float* q = tile + (32 * m + (e & 3) + 8 * (e >> 2) + 4 * half) * NTP + 32 * t + r;
+                        *q = w ? *q + acc[m][t][e] : acc[m][t][e];
+                    }
+        }
+        __syncthreads();
+    }
+    float* out = p.ws + (size_t)blockIdx.x * TILE;
+    for (int i = tid; i < TILE; i += 256) out[i] = tile[i];
+}
+
+// one thread per element of dw: the slices in slice order
+__global__ __launch_bounds__(256) void wgrad_img_reduce_kernel(float* __restrict__ dw, const float* __restrict__ ws, int nslices) {
+    using namespace wi;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= CO * NT) return;
+    const int co = idx / NT, n = idx - co * NT;
+    const float* src = ws + co * NTP + n;
+    float s = 0.f;
+#pragma unroll 8
+    for (int sl = 0; sl < nslices; ++sl) s += src[(size_t)sl * TILE];
+    dw[idx] = s;
+}
+
+struct WgradImgPlan { int ncb, nrs, rows_per, nslices; int64_t ws_bytes; };
+
+// shape checks shared by the entry and the workspace query; nullptr = accepted
+static const char* wgrad_img_plan(WgradImgPlan& pl, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return "non-positive dimension";
+    if (Cin != 3 || Cout != 64) return "built for the stem: Cin == 3 and Cout == 64";
+    if (K != 7 || stride != 2 || pad != 3) return "built for the stem: 7x7, stride 2, pad 3";
+    if ((H - 1) / 2 + 1 != OH || (W - 1) / 2 + 1 != OW) return "OH / OW are not the conv's output size";
+    if ((size_t)B * 3 * H * W * 4 >= 0xFFFFFFF0ull || (size_t)B * 64 * OH * OW * 2 >= 0xFFFFFFF0ull) return "x and gy must stay below 4 GiB each";
+    pl.ncb = (OW + wi::CW - 1) / wi::CW;
+    const int tiles = (OH + wi::R - 1) / wi::R;                            // row tiles of a sample
+    const long per = (long)B * pl.ncb;
+    long want = wi::TARGET_BLOCKS / per;                                  // row slices of a sample
+    if (want < 1) want = 1;
+    if (want > tiles) want = tiles;
+    const int tiles_per = (int)((tiles + want - 1) / want);
+    pl.rows_per = tiles_per * wi::R;
+    pl.nrs = (OH + pl.rows_per - 1) / pl.rows_per;                        // no empty slice
+    const long long ns = (long long)per * pl.nrs;
+    if (ns > 0x7FFFFFFFll) return "more than 2^31 slices";
+    pl.nslices = (int)ns;
+    pl.ws_bytes = (int64_t)ns * wi::TILE * 4;
+    return nullptr;
+}
+
+// ---- weight planes of a net in one launch --------------------------------------------------------------------------------------------------------
+// a row of the device table: eight int64
+struct PlaneSeg { long long dst, src, Cout, Cin, K, mode, qpad, first; };
+
+__global__ __launch_bounds__(256) void repack_planes_kernel(const PlaneSeg* __restrict__ table, int nseg, int nblocks) {
+    int sg = 0;
+    while (sg + 1 < nseg && (long long)blockIdx.x >= table[sg + 1].first) ++sg;
+    const PlaneSeg t = table[sg];
+    const long long nb = (sg + 1 < nseg ? table[sg + 1].first : (long long)nblocks) - t.first;
+    const int Cout = (int)t.Cout, Cin = (int)t.Cin, K = (int)t.K, mode = (int)t.mode, qpad = (int)t.qpad, KK = K * K;
+    // rows = the slot index of a plane, contr = the contraction index (16 per group); mode 3: contr counts (channel, ky) rows of 8 elements
+    const int rows = (mode == 0 || mode == 3) ? Cout : Cin;
+    const int contr = mode == 0 ? Cin : mode == 3 ? Cin * K : Cout;
+    const int groups = mode == 3 ? (contr + 1) / 2 : (contr + qpad - 1) / qpad * qpad / 16;
+    const int taps = mode == 3 ? 1 : KK;
+    const int rowsP = (rows + 31) / 32 * 32;
+    const long long total = (long long)groups * taps * 2 * rowsP;
+    const float* __restrict__ w = reinterpret_cast<const float*>(t.src);
+    u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(t.dst);
+    for (long long i = ((long long)blockIdx.x - t.first) * 256 + threadIdx.x; i < total; i += nb * 256) {
+        const int row = (int)(i % rowsP);
+        long long q = i / rowsP;
+        const int half = (int)(q & 1);
+        q >>= 1;
+        const int tp = (int)(q % taps), g = (int)(q / taps);
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.f;
+        if (row < rows) {
+            if (mode == 3) {
+                const int j = 2 * g + half;
+                if (j < contr) {
+                    const float* src = w + ((size_t)row * Cin * K + j) * K;          // w[row][c][ky][.], (c, ky) = divmod(j, K)
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (e < K) v[e] = src[e];
+                }
+            } else {
+                const int tt = mode == 2 ? KK - 1 - tp : tp;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int k = 16 * g + 8 * half + e;
+                    if (k < contr) v[e] = mode == 0 ? w[((size_t)row * Cin + k) * KK + tt] : w[((size_t)k * Cin + row) * KK + tt];
+                }
+            }
+        }
+        dst[i] = h8_pack(v);
+    }
+}
+
 static bool al16(const void* q) { return (((uintptr_t)q) % 16) == 0; }
 // nullptr = accepted
 static const char* bn_shape(int B, int C, int64_t HW) {
@@ -370,6 +594,48 @@ extern "C" int H8_NAME(l2i_conv2d_wgrad_h8)(float* dw, const void* x, const void
     L2I_CHECK_LAUNCH();
     const unsigned total = (unsigned)pl.tiles * pl.taps * wg::TILE;
     hipLaunchKernelGGL(wgrad_reduce_h8_kernel, dim3((total + 255) / 256), dim3(256), 0, st, dw, ws, out_scale, out_scale_dev, Cin, Cout, K, pl.ntn, pl.nslices, total);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}
+
+extern "C" int H8_NAME(l2i_conv2d_wgrad_img_ws_h8)(int64_t* bytes, int B, int Cin, int H, int W, int Cout, int OH, int OW, int K, int stride, int pad) {
+    using namespace H8_NS;
+    if (!bytes) return l2i_set_error(L2I_E_ARG, "conv2d_wgrad_img_ws_h8: null bytes");
+    WgradImgPlan pl;
+    if (const char* why = wgrad_img_plan(pl, B, Cin, H, W, Cout, OH, OW, K, stride, pad)) {
+        *bytes = 0;
+        return l2i_set_error(L2I_E_UNSUPPORTED, why);
+    }
+    *bytes = pl.ws_bytes;
+    return L2I_OK;
+}
+
+extern "C" int H8_NAME(l2i_conv2d_wgrad_img_h8)(float* dw, const float* x, const void* gy, float* ws, int64_t ws_bytes, int B, int Cin, int H, int W, int Cout,
+                                                int OH, int OW, int K, int stride, int pad, void* stream) {
+    using namespace H8_NS;
+    WgradImgPlan pl;
+    if (const char* why = wgrad_img_plan(pl, B, Cin, H, W, Cout, OH, OW, K, stride, pad)) return l2i_set_error(L2I_E_UNSUPPORTED, why);
+    if (!dw || !x || !gy) return l2i_set_error(L2I_E_ARG, "conv2d_wgrad_img_h8: null tensor");
+    if (!ws) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wgrad_img_h8: null workspace (size: l2i_conv2d_wgrad_img_ws_h8)");
+    if (ws_bytes < pl.ws_bytes) return l2i_set_error(L2I_E_UNSUPPORTED, "conv2d_wgrad_img_h8: workspace smaller than l2i_conv2d_wgrad_img_ws_h8 asks for");
+    if (!al16(gy)) return l2i_set_error(L2I_E_ARG, "conv2d_wgrad_img_h8: gy must be 16-byte aligned");
+    if ((((uintptr_t)dw) | ((uintptr_t)x) | ((uintptr_t)ws)) % 4) return l2i_set_error(L2I_E_ARG, "conv2d_wgrad_img_h8: dw, x and ws must be 4-byte aligned");
+    WgradImg p;
+    p.x = x; p.gy = gy; p.ws = ws; p.H = H; p.W = W; p.OH = OH; p.OW = OW; p.ncb = pl.ncb; p.nrs = pl.nrs; p.rows_per = pl.rows_per;
+    hipStream_t st = (hipStream_t)stream;
+    L2I_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_img_partial_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wi::LDS));
+    hipLaunchKernelGGL(wgrad_img_partial_kernel, dim3((unsigned)pl.nslices), dim3(256), (size_t)wi::LDS, st, p);
+    L2I_CHECK_LAUNCH();
+    hipLaunchKernelGGL(wgrad_img_reduce_kernel, dim3((wi::CO * wi::NT + 255) / 256), dim3(256), 0, st, dw, ws, pl.nslices);
+    L2I_CHECK_LAUNCH();
+    return L2I_OK;
+}
+
+extern "C" int H8_NAME(l2i_repack_planes_h8)(const void* table, int nseg, int nblocks, void* stream) {
+    using namespace H8_NS;
+    if (!table || (((uintptr_t)table) % 8) != 0) return l2i_set_error(L2I_E_ARG, "repack_planes_h8: the table must be a device pointer on an 8-byte boundary");
+    if (nseg <= 0 || nblocks < nseg) return l2i_set_error(L2I_E_ARG, "repack_planes_h8: nseg >= 1 and at least one block per segment");
+    hipLaunchKernelGGL(repack_planes_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const PlaneSeg*>(table), nseg, nblocks);
     L2I_CHECK_LAUNCH();
     return L2I_OK;
 }

@@ -317,6 +317,35 @@ def conv_wgrad(x, gy, k, stride, pad, out=None, ws=None, out_scale=1.0, out_scal
     return out
 
 
+WGRAD_IMG_SLICE_BYTES = 64 * 160 * 4      # L2I_WGRAD_IMG_SLICE_BYTES: the workspace of l2i_conv2d_wgrad_img_h8 per pixel slice
+
+
+def wgrad_img_ws_bytes(b, h, w, dtype=None, cin=3, cout=64, k=7, stride=2, pad=3):
+    """l2i_conv2d_wgrad_img_ws_h8: bytes of workspace the stem's weight gradient needs for a [b, 3, h, w] image (host only; = slices *
+    WGRAD_IMG_SLICE_BYTES); raises for a shape it refuses."""
+    n = ctypes.c_int64(0)
+    oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    _lib.check(_twin('l2i_conv2d_wgrad_img_ws_h8', dtype)(ctypes.byref(n), b, cin, h, w, cout, oh, ow, k, stride, pad), 'l2i_conv2d_wgrad_img_ws_h8')
+    return n.value
+
+
+def conv_wgrad_img(x, gy, out=None, ws=None):
+    """l2i_conv2d_wgrad_img_h8: dw [64, 3, 7, 7] fp32 = sum gy * x over (b, pixel) for the 7x7 / stride 2 / pad 3 stem: x the fp32 NCHW image (taken
+    as the fp32 value it is), gy the h8 gradient of the conv's output; ``out`` is OVERWRITTEN, in the units of gy; fixed summation order; ``ws`` a
+    float32 workspace of at least wgrad_img_ws_bytes (allocated when absent)."""
+    b, cin, h, w = x.shape
+    _, go, oh, ow, _ = gy.shape
+    assert gy.shape[0] == b and x.dtype == torch.float32
+    if ws is None:
+        ws = torch.empty(wgrad_img_ws_bytes(b, h, w, gy.dtype) // 4, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(go * 8, cin, 7, 7, device=x.device, dtype=torch.float32)
+    assert out.numel() == go * 8 * cin * 49
+    _lib.call('l2i_conv2d_wgrad_img_h8', _lib.fptr(out), _lib.fptr(x), _h8(gy), _lib.fptr(ws), ws.numel() * 4, b, cin, h, w, go * 8, oh, ow, 7, 2, 3,
+              dtype=gy.dtype)
+    return out
+
+
 def _bn_ws(x, ws):
     b, g8, h, w, _ = x.shape
     if ws is None:

@@ -18,9 +18,11 @@ the network; what a step launches is decided by the layer objects ``_layer_types
                                 place (csrc/l2i_repack.hip), the [C]-sized algebra as kernels, one gradient arena, optim.GuardedAdam, batches gathered
                                 from uint8 crops on the device — which capture.CapturedRegressorStep records into one hipGraph (DESIGN.md section 5.2);
   _H8StemConv / _H8Conv / _H8BN ``TrainableResNet50H8`` (``main(precision='f16' / 'bf16')``): the resident step on 16-bit h8
-                                maps — conv.ImgConvH8 / H8Conv forward and input gradients (planes rebuilt by their ``repack``), ``l2i_conv2d_wgrad_h8``
-                                and the h8 BatchNorm kernels of csrc/l2i_train_h8.hip, fp32 master weights, a static x dynamic loss scale
-                                (optim.LossScaler) — with the fp32 model's interface and checkpoints.
+                                maps — conv.ImgConvH8 / H8Conv forward and input gradients (every plane rewritten in place by one launch of
+                                ``l2i_repack_planes_h8``), ``l2i_conv2d_wgrad_h8``, ``l2i_conv2d_wgrad_img_h8`` for conv1 and the h8 BatchNorm kernels
+                                of csrc/l2i_train_h8.hip (every sum in a fixed order: a bit-reproducible step), fp32 master weights, a static x
+                                dynamic loss scale (optim.LossScaler) — with the fp32 model's interface and checkpoints; capture.CapturedRegressorStep
+                                records it too (the driver's ``hip_graph`` flag does not reach it yet).
 """
 import csv
 import os
@@ -445,9 +447,10 @@ class _H8BN(_ResidentBN):
 
 
 class _H8Conv(_ResidentConv):
-    """A trainable bias-free convolution of the 16-bit trainer: fp32 master weight; ``plan()`` builds a conv.H8Conv of the element type once and
-    then has it repack its planes from the weight ON THE DEVICE (H8Conv.repack: torch ops; the device-side repack kernel is a follow-up); the
-    weight gradient is l2i_conv2d_wgrad_h8 straight into the gradient arena, overwritten and already unscaled."""
+    """A trainable bias-free convolution of the 16-bit trainer: fp32 master weight; ``plan()`` builds a conv.H8Conv of the element type once; after
+    that the owner rewrites the planes of every convolution in place with one launch (TrainableResNet50H8.replan: conv.PlaneTable) and ``plan()``
+    is only the path of a library without that kernel (H8Conv.repack: torch ops that allocate); the weight gradient is l2i_conv2d_wgrad_h8
+    straight into the gradient arena, overwritten and already unscaled."""
 
     def __init__(self, P, name, stride, padding, device, elem='f16'):
         super().__init__(P, name, stride, padding, device)
@@ -475,9 +478,10 @@ class _H8Conv(_ResidentConv):
 
 
 class _H8StemConv(_ResidentConv):
-    """conv1 of the 16-bit trainer: conv.ImgConvH8 (7x7 stride 2, fp32 image in, h8 out), its 16-bit planes repacked from the master weight by
-    ImgConvH8.repack (a host pack of 9408 weights); the weight gradient is the fp32 kernel's on the h8 gradient map cast to fp32
-    (_ResidentConv.wgrad: atomics, in scaled units)."""
+    """conv1 of the 16-bit trainer: conv.ImgConvH8 (7x7 stride 2, fp32 image in, h8 out), its 16-bit planes rewritten with every other
+    convolution's by the owner's one launch; the weight gradient is l2i_conv2d_wgrad_img_h8 on the h8 gradient map as it lies and the fp32 image
+    (fixed summation order, OVERWRITES its view of the arena, in scaled units).  A library without those entry points: ImgConvH8.repack (a host
+    pack of 9408 weights) and the fp32 atomics kernel on the gradient map cast to fp32 (_ResidentConv.wgrad)."""
 
     def __init__(self, P, name, stride, padding, device, elem='f16'):
         super().__init__(P, name, stride, padding, device)
@@ -493,7 +497,9 @@ class _H8StemConv(_ResidentConv):
         return self.img.forward(x)
 
     def wgrad(self, x, gy):
-        return super().wgrad(x, K16.cast_from_h8(gy))
+        if not self.owner.stem_kernel:
+            return super().wgrad(x, K16.cast_from_h8(gy))
+        return K16.conv_wgrad_img(x, gy, out=self.g_weight, ws=self.owner.stem_ws(x, gy))
 
 
 class TrainableResNet50H8(TrainableResNet50):
@@ -517,7 +523,9 @@ class TrainableResNet50H8(TrainableResNet50):
         self.loss_scale_log2 = int(loss_scale_log2)
         self.static, self.inv_static = float(2.0 ** self.loss_scale_log2), float(2.0 ** -self.loss_scale_log2)
         self.scaler = optim.LossScaler(dict(T=self.loss_scale_log2), device)
-        self._bn_ws = self._wg_ws = None
+        self._bn_ws = self._wg_ws = self.planes = None
+        # the stem's fixed-order weight gradient and the one-launch repack, where the library has them (an older build through L2I_LIB: today's path)
+        self.stem_kernel, self.planes_kernel = _lib.has('l2i_conv2d_wgrad_img_h8'), _lib.has('l2i_repack_planes_h8')
         self.monitor = None                                       # a nets16.RangeMonitor: every stored map of a step is added to it by stage (tools/bench_regressor_train.py --ranges)
         super().__init__(state, device=device, num_classes=num_classes, resident=True)
 
@@ -546,11 +554,30 @@ class TrainableResNet50H8(TrainableResNet50):
             self._bn_ws = torch.empty(n, device=x.device, dtype=torch.float64)
         return self._bn_ws
 
-    def wgrad_ws(self, x, gy, cv):
-        n = K16.wgrad_ws_bytes(x.shape[0], x.shape[1] * 8, x.shape[2], x.shape[3], gy.shape[1] * 8, gy.shape[2], gy.shape[3], cv.k, cv.stride, cv.padding, x.dtype) // 4
+    def _wg_room(self, n, device):
+        """The one float32 workspace of every weight gradient of the step, grown to ``n`` elements (the first step of a shape grows it to the
+        largest need; nothing grows after that, so a recording's warm-up leaves it final)."""
         if self._wg_ws is None or self._wg_ws.numel() < n:
-            self._wg_ws = torch.empty(n, device=x.device, dtype=torch.float32)
+            self._wg_ws = torch.empty(n, device=device, dtype=torch.float32)
         return self._wg_ws
+
+    def wgrad_ws(self, x, gy, cv):
+        return self._wg_room(K16.wgrad_ws_bytes(x.shape[0], x.shape[1] * 8, x.shape[2], x.shape[3], gy.shape[1] * 8, gy.shape[2], gy.shape[3], cv.k, cv.stride,
+                                                cv.padding, x.dtype) // 4, x.device)
+
+    def stem_ws(self, x, gy):
+        return self._wg_room(K16.wgrad_img_ws_bytes(x.shape[0], x.shape[2], x.shape[3], gy.dtype) // 4, x.device)
+
+    def replan(self):
+        """The first call builds every convolution's planes (packed on the host) and, once, the table of all 53 convolutions plus the stem; every
+        later call is ONE launch that rewrites them in place from the master weights (conv.PlaneTable: the optimiser updates the masters in
+        place and the planes never move, so the table stays valid)."""
+        if self.planes is not None:
+            return self.planes.run()
+        super().replan()
+        if self.planes_kernel:
+            convs = self._convs()
+            self.planes = C.PlaneTable(convs[0].img.segments(convs[0].weight) + [sg for cv in convs[1:] for sg in cv.h8.segments(cv.weight)], self.dtype)
 
     def _input(self, img):
         return img.detach().float().contiguous()

@@ -18,7 +18,12 @@ pack — against 6.3 TB/s, with the time per launch.
 (the time Python and the torch packing ops take to ISSUE it, against the time the GPU takes to run it).  --wgrad_table: every distinct weight-
 gradient shape of ResNet-50 at that batch and size, l2i_conv2d_wgrad_h8 (fp16) against l2i_conv2d_wgrad_f32 on the same maps cast to fp32.
 L2I_LIB=<another build> --precision f32 times the fp32 side on that build (the parent's, for the comparison of the same session).
---only f16 / bf16 runs a few steps of the 16-bit trainer alone (the run to put under a kernel trace).
+--only f16 / bf16 runs a few steps of the 16-bit trainer alone (the run to put under a kernel trace); with --hip_graph those steps are replays of
+capture.CapturedRegressorStep.  --precision ... --hip_graph adds, per 16-bit side, the same step replayed from a hipGraph (its own model, same
+state), and the in-place repack of the 16-bit planes alone (replan(): GPU time and GB/s of its least traffic).  --stem_table: conv1's weight
+gradient alone, l2i_conv2d_wgrad_img_h8 against cast_from_h8 + l2i_conv2d_wgrad_f32 on the same maps, both element types
+(profiles/regressor_train16_repro_bench.txt).  L2I_LIB=<the parent's build> runs the same Python on the parent's kernels: the 16-bit trainer then
+takes the path it had (fp32 atomics for conv1, torch repack) and --hip_graph / --stem_table have nothing to run.
 """
 import argparse
 import os
@@ -106,7 +111,43 @@ def wgrad_table(B, S, say):
     say('  rows on which the new kernel is slower: %s' % (slower or 'none'))
 
 
-def precision_bench(precisions, B, S, st, data, label, say):
+def stem_table(B, S, say):
+    """conv1's weight gradient alone at batch B, S^2: the fixed-order kernel on the h8 gradient map as it lies against the pair it replaces (the
+    map cast to fp32, then the fp32 atomics kernel), alternating runs in one process."""
+    from latent2im_amd import _lib
+    from latent2im_amd import kernels16 as K16
+    say('stem weight gradient alone, batch %d at %d^2: l2i_conv2d_wgrad_img_h8 against cast_from_h8 + l2i_conv2d_wgrad_f32; %s' % (B, S, torch.cuda.get_device_name(0)))
+    if not _lib.has('l2i_conv2d_wgrad_img_h8'):
+        return say('  this library has no l2i_conv2d_wgrad_img_h8')
+    g = torch.Generator(device='cuda').manual_seed(1)
+    oh = (S - 1) // 2 + 1
+    x = torch.randn(B, 3, S, S, device='cuda', generator=g) * 0.5
+    least = B * 64 * oh * oh * 2 + x.numel() * 4
+    flop = 2.0 * B * oh * oh * 64 * 147
+    for dtype in (torch.float16, torch.bfloat16):
+        gy = (torch.randn(B, 8, oh, oh, 8, device='cuda', generator=g) * 0.1).to(dtype)
+        nbytes = K16.wgrad_img_ws_bytes(B, S, S, dtype)
+        ws, dw, dw32 = torch.empty(nbytes // 4, device='cuda'), torch.empty(64, 3, 7, 7, device='cuda'), torch.zeros(64, 3, 7, 7, device='cuda')
+
+        def pair():
+            dw32.zero_()
+            _lib.call('l2i_conv2d_wgrad_f32', _lib.fptr(dw32), _lib.fptr(x), _lib.fptr(K16.cast_from_h8(gy)), B, 3, S, S, 64, oh, oh, 7, 7, 2, 3, 3)
+        new = lambda: K16.conv_wgrad_img(x, gy, out=dw, ws=ws)
+        runs = {'new': [], 'pair': []}
+        for _ in range(3):
+            runs['new'].append(timed(new))
+            runs['pair'].append(timed(pair))
+        tn, tp = statistics.median(runs['new']), statistics.median(runs['pair'])
+        spread = max((max(v) - min(v)) / statistics.median(v) for v in runs.values())
+        rel = float((dw - dw32).norm() / dw32.norm())
+        say('  %-8s new %s ms (median %.3f) = %.0f GB/s of the %.1f MB least traffic (%.1f %% of 6.3 TB/s), %.1f TFLOP/s; %d slices, %.1f MB workspace'
+            % (str(dtype).split('.')[1], ' '.join('%.3f' % (t * 1e3) for t in runs['new']), tn * 1e3, least / tn / 1e9, least / 1e6, 100 * least / tn / HBM,
+               flop / tn / 1e12, nbytes // K16.WGRAD_IMG_SLICE_BYTES, nbytes / 1e6))
+        say('  %-8s cast + fp32 atomics %s ms (median %.3f); pair / new %.2fx; largest run-to-run spread %.1f %%; relative L2 difference of the two dw %.2e'
+            % ('', ' '.join('%.3f' % (t * 1e3) for t in runs['pair']), tp * 1e3, tp / tn, 100 * spread, rel))
+
+
+def precision_bench(precisions, B, S, st, data, label, say, hip_graph=False, data_h=None, label_h=None):
     """The resident fp32 step and the 16-bit trainer of each listed element type: losses, step times, the host's share."""
     import time
     from latent2im_amd import _lib
@@ -117,6 +158,15 @@ def precision_bench(precisions, B, S, st, data, label, say):
         m = RT.make_model(st, precision=p, resident=True, **({} if p == 'f32' else dict(image_size=S, batch=B)))
         o = RT.make_optimizer(m, guarded=True)
         sides[p] = (m, o, (lambda m=m, o=o: RT.train_step_resident(m, o, data, label)))
+        if hip_graph and p != 'f32':
+            from latent2im_amd import capture
+            if not (m.stem_kernel and m.planes_kernel):
+                say('  %s: this library has no in-place repack: the 16-bit step cannot be recorded' % p)
+                continue
+            m2 = RT.make_model(st, precision=p, resident=True, image_size=S, batch=B)
+            o2 = RT.make_optimizer(m2, guarded=True)
+            g = capture.CapturedRegressorStep(m2, o2, B, S)
+            sides[p + '+graph'] = (m2, o2, (lambda g=g: g(data_h, label_h)))
     for p, (m, o, fn) in sides.items():
         say('  first three losses, %-5s %s%s' % (p, ' '.join('%.6f' % float(fn()) for _ in range(3)), '' if p == 'f32' else '   (static scale 2^%d)' % m.loss_scale_log2))
     runs = {p: [] for p in sides}
@@ -131,6 +181,8 @@ def precision_bench(precisions, B, S, st, data, label, say):
     for p in sides:
         if p != 'f32' and 'f32' in med:
             say('  f32 resident / %-5s %.2fx' % (p, med['f32'] / med[p]))
+        if p.endswith('+graph'):
+            say('  %s eager / replayed %.2fx' % (p[:-6], med[p[:-6]] / med[p]))
     say('  host share: time to ISSUE one step from Python (no synchronisation inside; median of 10) against the GPU time above')
     for p, (m, o, fn) in sides.items():
         hs, rp = [], []
@@ -147,6 +199,14 @@ def precision_bench(precisions, B, S, st, data, label, say):
                                                                                     'HOST-BOUND' if statistics.median(hs) > 0.9 * med[p] else 'GPU-bound'))
         if p != 'f32':
             say('    %-5s scaler %s' % (p, o.scaler.stats()))
+        if p in ('f16', 'bf16'):
+            # the repack alone: every plane written once, every master weight read once per plane set made from it
+            byt = sum(t.numel() * 2 for cv in m._convs()[1:] for t in (cv.h8.fwd_planes, cv.h8.bwd_planes)) + m.stem.img.planes.numel() * 2
+            byt += sum(cv.weight.numel() * 4 * 2 for cv in m._convs()[1:]) + m.stem.weight.numel() * 4
+            t = timed(m.replan)
+            say('    %-5s replan() alone: %s, %.1f MB least traffic, GPU %.3f ms = %.0f GB/s (%.1f %% of 6.3 TB/s)'
+                % (p, 'one launch over %d segments' % m.planes.nseg if m.planes is not None else 'torch ops per convolution', byt / 1e6, t * 1e3, byt / t / 1e9,
+                   100 * byt / t / HBM))
 
 
 def ranges(say):
@@ -180,6 +240,8 @@ def main():
     ap.add_argument('--ranges', action='store_true', help='stored ranges of one fp16 step at 8 x 128^2 and 32 x 256^2 (the static exponent rule)')
     ap.add_argument('--precision', help='comma list of f32, f16, bf16: the 16-bit comparison instead of the fp32 sides')
     ap.add_argument('--wgrad_table', action='store_true', help='the per-shape weight-gradient table')
+    ap.add_argument('--stem_table', action='store_true', help="conv1's weight gradient alone: the fixed-order h8 kernel against cast + fp32 atomics")
+    ap.add_argument('--hip_graph', action='store_true', help='with --precision: add the 16-bit step replayed from a hipGraph; with --only f16 / bf16: replay')
     ap.add_argument('--out')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--size', type=int, default=256)
@@ -202,14 +264,16 @@ def main():
 
     def finish():
         if a.out:
-            with open(a.out, 'a' if (a.precision or a.wgrad_table or a.ranges) else 'w') as f:
+            with open(a.out, 'a' if (a.precision or a.wgrad_table or a.ranges or a.stem_table) else 'w') as f:
                 f.write('\n'.join(lines) + '\n')
 
-    if a.precision or a.wgrad_table or a.ranges:
+    if a.precision or a.wgrad_table or a.ranges or a.stem_table:
         if a.ranges:
             ranges(say)
         if a.precision:
-            precision_bench(a.precision.split(','), B, S, st, data, label, say)
+            precision_bench(a.precision.split(','), B, S, st, data, label, say, hip_graph=a.hip_graph, data_h=data_h, label_h=label_h)
+        if a.stem_table:
+            stem_table(B, S, say)
         if a.wgrad_table:
             wgrad_table(B, S, say)
         return finish()
@@ -218,6 +282,9 @@ def main():
         if side in ('f16', 'bf16'):
             m = RT.TrainableResNet50H8(st, device='cuda', precision=side, image_size=S, batch=B)
             o = RT.make_optimizer(m, guarded=True)
+            if a.hip_graph:
+                g16 = capture.CapturedRegressorStep(m, o, B, S)
+                return m, (lambda: g16(data_h, label_h))
             return m, (lambda: RT.train_step_resident(m, o, data, label))
         if side == 'eager':
             m = RT.TrainableResNet50(st, device='cuda')
