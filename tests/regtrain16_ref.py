@@ -33,7 +33,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from tests.stream_ref import U23, ELEM_DTYPES, bound16, from_h8, rnd_for, to_h8, worst      # noqa: F401 (shared, re-exported)
+from tests.stream_ref import U23, ELEM_DTYPES, bound16, bound_elem, from_h8, rnd_for, to_h8, worst      # noqa: F401 (shared, re-exported)
 
 ELEMS = ('bf16', 'f16')
 SENTINEL = -7680.0            # exactly representable in fp32, bf16 and fp16
@@ -81,6 +81,12 @@ def _f(v):
     return float(np.float32(v))
 
 
+def bound_store(want, M, k, elem):
+    """The bound of a stored element formed by k rounded fp32 operations: with the half ulp of a 16-bit store, or ('f32': the value is
+    stored as computed) without it."""
+    return bound_elem(M.double(), k) if elem == 'f32' else bound16(want, M, k, elem)
+
+
 # ---- data -----------------------------------------------------------------------------------------------------------------------------------------
 def wgrad_data(case, seed=0):
     """(x [B,Cin,H,W], gy [B,Cout,OH,OW]) float32, seeded by the case's name."""
@@ -106,33 +112,41 @@ def _tap_view(xp, ky, kx, stride, oh, ow):
     return xp[:, :, ky:ky + stride * (oh - 1) + 1:stride, kx:kx + stride * (ow - 1) + 1:stride]
 
 
-def wgrad(x, gy, k, stride, pad, out_scale, elem, dt=torch.float64, _mistake=None):
+def wgrad(x, gy, k, stride, pad, out_scale, elem, dt=torch.float64, _mistake=None, kw=None, pad_x=None, dw0=None):
     """(want, bound): dw [Cout, Cin, K, K] in ``dt`` (float64: the model; float32: the emulation the CPU test holds against the bound) and the
-    bound per element.  ``out_scale`` = the product of the host and the device factor, as float32 values."""
+    bound per element.  ``out_scale`` = the product of the host and the device factor, as float32 values.
+
+    What only the fp32 entry point allows (tests/regtrain32_ref.py): ``kw``: the kernel's width where it is not ``k`` (``k`` is then its height);
+    ``pad_x``: the padding along x where it is not ``pad`` (then that along y); ``dw0`` [Cout, Cin, K, KW]: what dw holds before the call, which the
+    result is added to (its magnitude joins M in the bound: the add into it is one of the roundings)."""
     assert _mistake is None or _mistake in MISTAKES, _mistake
     rnd = rnd_for(elem)
     xx, gg = _d(x, rnd).to(dt), _d(gy, rnd).to(dt)
     b, cin, h, w = xx.shape
     _, cout, oh, ow = gg.shape
+    kh, kw = k, (k if kw is None else kw)
+    pad_y, pad_x = pad, (pad if pad_x is None else pad_x)
     s = 1 if _mistake == 'stride_ignored' else stride
     margin = 1 + (stride * max(oh, ow) if _mistake == 'stride_ignored' else 0)          # room for the shifted / unstrided reads of the mistakes
+    # (and for a gy that reaches past the padded map, as the fp32 entry point takes OH and OW as given: those pixels are padding, zeros)
+    margin = max(margin, kh + stride * (oh - 1) + 1 - (h + 2 * pad_y), kw + stride * (ow - 1) + 1 - (w + 2 * pad_x))
     mode = 'replicate' if _mistake == 'padding_as_data' else 'constant'
 
     def padded(t):
-        if mode == 'replicate' and pad > 0:
-            t = torch.nn.functional.pad(t, (pad, pad, pad, pad), mode='replicate')
+        if mode == 'replicate' and (pad_y > 0 or pad_x > 0):
+            t = torch.nn.functional.pad(t, (pad_x, pad_x, pad_y, pad_y), mode='replicate')
             return torch.nn.functional.pad(t, (0, margin, 0, margin))
-        return torch.nn.functional.pad(t, (pad, pad + margin, pad, pad + margin))
+        return torch.nn.functional.pad(t, (pad_x, pad_x + margin, pad_y, pad_y + margin))
     xp, xa = padded(xx), padded(xx.abs())
     if _mistake == 'slice_tail_dropped':                  # the pixels of the last, partial 256-pixel chunk contribute nothing
         keep = torch.ones(b * oh * ow, dtype=dt)
         keep[(b * oh * ow) // 256 * 256:] = 0
         gg = gg * keep.view(b, 1, oh, ow)
     sc = 1.0 if _mistake == 'out_scale_forgotten' else float(out_scale)
-    want, M = torch.zeros(cout, cin, k, k, dtype=dt), torch.zeros(cout, cin, k, k, dtype=torch.float64)
-    for ky in range(k):
-        for kx in range(k):
-            if _mistake == 'dropped_tap' and (ky, kx) == (k - 1, k - 1):
+    want, M = torch.zeros(cout, cin, kh, kw, dtype=dt), torch.zeros(cout, cin, kh, kw, dtype=torch.float64)
+    for ky in range(kh):
+        for kx in range(kw):
+            if _mistake == 'dropped_tap' and (ky, kx) == (kh - 1, kw - 1):
                 continue
             sx = kx + 1 if (_mistake == 'tap_shifted' and (ky, kx) == (0, 0)) else kx
             want[:, :, ky, kx] = torch.einsum('bohw,bihw->oi', gg, _tap_view(xp, ky, sx, s, oh, ow))
@@ -142,6 +156,9 @@ def wgrad(x, gy, k, stride, pad, out_scale, elem, dt=torch.float64, _mistake=Non
         want = want.transpose(0, 1).contiguous()
     want = want * sc
     bound = U23 * (b * oh * ow + 2) * M * abs(float(out_scale))
+    if dw0 is not None:
+        want = want + _d(dw0).to(dt)
+        bound = U23 * (b * oh * ow + 2) * (M * abs(float(out_scale)) + _d(dw0).abs())
     return want, bound
 
 
@@ -155,7 +172,8 @@ def bn_stats(x, elem):
     xx = _d(x, rnd_for(elem))
     n = xx.numel() // xx.shape[1]
     s, q = xx.sum((0, 2, 3)), (xx * xx).sum((0, 2, 3))
-    return (s, q), (U52 * n * xx.abs().sum((0, 2, 3)), U52 * n * q)
+    k = n + 1 if elem == 'f32' else n                     # (the fp32 contract counts one more: see tests/regtrain32_ref.py)
+    return (s, q), (U52 * k * xx.abs().sum((0, 2, 3)), U52 * k * q)
 
 
 def bn_finalize(s, q, n, gamma, beta, eps=BN_EPS, _mistake=None):
@@ -185,7 +203,7 @@ def bn_apply(x, scale, shift, residual, relu, elem, dt=torch.float64, k=3, _mist
         v = torch.relu(v)
     if rr is not None and _mistake == 'residual_after_relu':
         v = v + rr
-    return v, bound16(v.double(), M, k, elem)
+    return v, bound_store(v.double(), M, k, elem)
 
 
 def bn_forward(x, gamma, beta, residual, relu, elem, _mistake=None):
@@ -199,7 +217,7 @@ def bn_forward(x, gamma, beta, residual, relu, elem, _mistake=None):
     rnd = rnd_for(elem)
     c = lambda v: v.view(1, -1, 1, 1)
     M = (_d(x, rnd).abs() + c(mean0).abs()) * c(scale0).abs() + c(_d(beta)).abs() + (0 if residual is None else _d(residual, rnd).abs())
-    return want, bound16(want0, M, 8, elem)
+    return want, bound_store(want0, M, 8, elem)
 
 
 def _masked(gy, out, x, rnd, dt, _mistake=None):
@@ -234,4 +252,4 @@ def bn_bwd_apply(gy, out, x, mean, invstd, gamma, m_dy, m_dyxh, elem, dt=torch.f
     gi = ga * isd
     v = gi * (dy - md - xh * mx)
     M = (gi.abs() * (dy.abs() + md.abs() + (xx.abs() + mu.abs()) * isd.abs() * mx.abs())).double()
-    return v, bound16(v.double(), M, 7, elem), dy
+    return v, bound_store(v.double(), M, 7, elem), dy

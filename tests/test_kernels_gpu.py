@@ -845,7 +845,8 @@ def test_half_precision_entry_points_of_the_reference_ops():
                                                          (40, 72, 3, 2, 1, 17, 19, 3), (128, 256, 1, 2, 0, 16, 16, 2), (512, 512, 3, 1, 1, 2, 2, 8)])
 def test_conv_weight_gradient(cin, cout, k, stride, pad, h, w, b):
     """l2i_conv2d_wgrad_f32 against torch autograd (float64): every conv shape class of ResNet-50 (7x7 stem on 3 channels, 1x1, 3x3, strides
-    1 / 2, channel counts that are not multiples of 32, tiny maps), and accumulation into a non-zero dw."""
+    1 / 2, channel counts that are not multiples of 32, tiny maps).  Accumulation into a non-zero dw, rectangular kernels, the second trip of
+    the row loop and per-element bounds: tests/test_regtrain32_kernels_gpu.py."""
     from latent2im_amd import regressor_train as RT
     rs = np.random.RandomState(cin + cout + k)
     x = T(rs.randn(b, cin, h, w))
