@@ -620,6 +620,29 @@ int l2i_face_resize_f32(float* y, const float* x, int64_t planes, int H, int W, 
 int l2i_face_head_f32(float* emb, double* dist, const float* feat, const float* w_t, const float* bias, int B, int C, int HW, int E, int npairs,
                       void* stream);
 
+/* The differentiable twin of the pair above: the face branch of walk training's identity loss (--id_loss; latent2im_amd/facenet.py:FaceIdFn).
+ * Additive: the ABI version did not move.  No floating-point atomics; every sum has a fixed order, so two launches give equal bits.
+ * l2i_face_resize_lin_f32: the arguments, tables and shape range of l2i_face_resize_f32 (it refuses the same shapes, nothing written).
+ *   u = min(max(((x + 1) * 0.5) * 255, 0), 255) in fp32 (NaN -> 0: clip_ims without the truncating cast), y = Ry u Rx^T per plane with
+ *   R = the table / 2^22, horizontal pass first, taps in ascending order: the same taps without the uint8 intermediate, the rounding and the clips.
+ *   Both columns of ybounds (first input row, first + count) must be non-decreasing in the output index, as PIL's are: a block takes the input rows of
+ *   its output rows from the first row's start and the last row's end, and taps of a table that breaks the rule outside that range are not read (not
+ *   checked: the tables live on the device).
+ * l2i_face_resize_lin_bwd_f32: its adjoint as a gather, gx = 127.5 * [0 < ((x + 1) * 0.5) * 255 < 255] * Rx^T (Ry^T gy); gx, x [planes, H, W], gy
+ *   [planes, OH, OW].  ixbounds [W, 2] / iybounds [H, 2] = (first output, count) of the outputs whose support holds the input pixel, ixcoef
+ *   [W, ixk] / iycoef [H, iyk] int32 their coefficients (the forward tables transposed: latent2im_amd/facenet.py:inverse_tables).  Every gx
+ *   element is written once, by one lane.  Inputs <= 4096 and outputs <= 256 pixels a side, <= 256 taps; else L2I_E_UNSUPPORTED.
+ * l2i_face_head_bwd_f32: the gradient of dist[b] = 1 - cos(e[b], v[b]) down to the trunk's output.  With p = mean_hw feat, t = w_t^T p + bias,
+ *   n = max(|t|, 1e-12), e = t / n (l2i_face_head_f32's embedding, recomputed), v^ = v / |v| (v [B, E]: the other half's embedding, a constant)
+ *   and c = e . v^:  g_t = -g_dist[b] (v^ - c e) / n,  g_p = w_t g_t,  g_feat[b, c, :] = g_p[c] / HW;  g_feat [B, C, HW], g_dist [B].  The limits
+ *   of l2i_face_head_f32 (C <= 2048, E <= 512). */
+int l2i_face_resize_lin_f32(float* y, const float* x, int64_t planes, int H, int W, int OH, int OW, const int32_t* xbounds, const int32_t* xcoef,
+                            int xk, const int32_t* ybounds, const int32_t* ycoef, int yk, void* stream);
+int l2i_face_resize_lin_bwd_f32(float* gx, const float* gy, const float* x, int64_t planes, int H, int W, int OH, int OW, const int32_t* ixbounds,
+                                const int32_t* ixcoef, int ixk, const int32_t* iybounds, const int32_t* iycoef, int iyk, void* stream);
+int l2i_face_head_bwd_f32(float* g_feat, const float* feat, const float* w_t, const float* bias, const float* v, const float* g_dist, int B, int C,
+                          int HW, int E, void* stream);
+
 /* [ABI 10] The Gram-matrix term of BP.py's inversion loss and its gradient (csrc/l2i_gram.hip; BP.py:68-73, :173-184).
  * l2i_gram_loss_f32: c [B, C, HW] is a tap's PRE-ReLU conv output.  G[b] = relu(c[b]) relu(c[b])^T / (C HW) -> G [B, C, C] (the ReLU is applied on
  *   load; only tile pairs i <= j are contracted, on v_mfma_f32_32x32x2_f32, and the lower triangle is the mirror of the upper one, so G is

@@ -374,9 +374,12 @@ class WalkGraph:
 
 class TransformGraph(WalkGraph):
     def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, stylegan_opts,
-                 nets=None):
+                 nets=None, id_weight=0.0, facenet_ckpt=None):
         WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
         self.img_size = constants.resolution
+        # --id_loss W: a fourth loss term W * mean_b (1 - cos(face(edited), face(original))) on the face network of eval.py's identity metric
+        # (facenet.FaceIdFn).  0 (the default): nothing is built, launched or changed.
+        self.id_weight, self.facenet_ckpt, self._face_net = float(id_weight or 0.0), facenet_ckpt, None
         if nets is None:
             nets = load_networks(self.img_size, self.device)
         netG, netD, self.regressor, self.vgg19, self.weight_sources = nets
@@ -482,6 +485,27 @@ class TransformGraph(WalkGraph):
         losses = self.vgg19.content_losses(org_img, shifted_img, org_taps=taps)
         return [losses[i] for i in range(4)]
 
+    def face_net(self):
+        """The face network of the identity term, loaded on first use from ``facenet_ckpt`` / constants.facenet_path (synthetic weights under
+        the rule of the other networks; a missing checkpoint without them is an error)."""
+        if self._face_net is None:
+            from . import facenet
+            self._face_net, src = facenet.load(self.facenet_ckpt, device=self.device)
+            self.weight_sources['F'] = src
+        return self._face_net
+
+    def check_id_loss(self):
+        """The refusals of the identity term, raised where the term is trained with (get_w_loss, captured_step, trainer.main), not where a graph
+        is built: eval.py / vis_w.py rebuild the graph from a run's opt.yml, id_loss included, at whatever --precision they are asked for."""
+        from . import conv
+        if self.id_weight and conv.PRECISION == 'f16':
+            raise NotImplementedError('id_loss with --precision f16: the face branch would need a fifth static gradient-scale exponent '
+                                      '(nets16.loss_scale_for has R, V, D, G), which is not calibrated; use f32, bf16x3 or bf16')
+
+    def get_id_loss(self, org, logit):
+        """mean_b (1 - cos(e(logit[b]), e(org[b]))): the embedding of the original is a constant, the edit's is differentiable."""
+        return self.face_net().id_distances(logit, org.detach()).mean()
+
     # -- loss / optimiser ----------------------------------------------------------------------------------------
     def _side_streams(self):
         if getattr(self, '_streams', None) is None:
@@ -491,6 +515,7 @@ class TransformGraph(WalkGraph):
     def get_w_loss(self, feed_dict, no_content_loss=False, no_gan_loss=False):
         """Total walk loss of optimizeParametersAll (transform_base.py:459-486) without the optimiser step."""
         logit = feed_dict['logit']
+        self.check_id_loss()
         gan_loss = content_losses = None
         # The three loss branches (discriminator, VGG content, regressor) are independent forward+backward chains over
         # the same image: each runs on its own HIP stream (autograd replays every node's backward on its forward
@@ -508,6 +533,7 @@ class TransformGraph(WalkGraph):
                 content_loss_list = self.get_content_loss(feed_dict['org'], feed_dict['logit'])
                 content_losses = sum(content_loss_list) / len(content_loss_list)
         reg_loss = self.get_reg_loss(feed_dict)
+        id_loss = self.get_id_loss(feed_dict['org'], logit) if self.id_weight else None
         if side[0] is not cur:
             cur.wait_stream(side[0])
             cur.wait_stream(side[1])
@@ -516,8 +542,10 @@ class TransformGraph(WalkGraph):
             loss = loss + 0.05 * content_losses
         if not no_gan_loss:
             loss = loss + 0.05 * gan_loss
+        if id_loss is not None:
+            loss = loss + self.id_weight * id_loss
         self.last_terms = dict(reg=reg_loss.detach(), cont=None if content_losses is None else content_losses.detach(),
-                               gan=None if gan_loss is None else gan_loss.detach())
+                               gan=None if gan_loss is None else gan_loss.detach(), id=None if id_loss is None else id_loss.detach())
         return loss
 
     # -- the step as the drivers run it ----------------------------------------------------------------------------
@@ -549,6 +577,13 @@ class TransformGraph(WalkGraph):
     def captured_step(self, batch, n_attr, *, clamp=False, layers=None, no_content_loss=False, no_gan_loss=False):
         """The same step as a hipGraph for ``batch`` samples a replay (capture.CapturedStep): what trainer.train_step asks for under --hip_graph."""
         from . import capture
+        self.check_id_loss()
+        if self.id_weight:                   # the face branch is not recorded: trainer.train_step takes its eager route
+            if not getattr(self, '_id_eager_logged', False):
+                import logging
+                logging.info('--hip_graph with --id_loss: the identity branch is not recorded into the hipGraph; the step runs eagerly')
+                self._id_eager_logged = True
+            return None
         return capture.CapturedStep(self, batch, n_attr, clamp=clamp, layers=layers, no_content_loss=no_content_loss, no_gan_loss=no_gan_loss)
 
     # -- checkpoints ---------------------------------------------------------------------------------------------

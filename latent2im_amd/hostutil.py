@@ -60,6 +60,9 @@ def set_graph_kwargs(opt):
         kw['stylegan_opts'] = opt.stylegan
     if opt.model == 'pggan':
         kw['pgan_opts'] = opt.pggan
+    if getattr(opt, 'id_loss', 0.0):                       # --id_loss W (and its checkpoint): only a run that asks for the term carries them
+        kw['id_weight'] = float(opt.id_loss)
+        kw['facenet_ckpt'] = getattr(opt, 'facenet_ckpt', None)
     return kw
 
 

@@ -331,6 +331,51 @@ def face_head(feat, w_t, bias, npairs=0):
     return emb, dist
 
 
+def _resize_tables_ok(n_b, n_c, *tables):
+    xb, xc, yb, yc = tables
+    assert xb.shape[0] == xc.shape[0] == n_b and yb.shape[0] == yc.shape[0] == n_c, ([tuple(t.shape) for t in tables], n_b, n_c)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in tables)
+
+
+def face_resize_lin(x, xbounds, xcoef, ybounds, ycoef):
+    """l2i_face_resize_lin_f32: x [B, C, H, W] fp32 -> Ry clip(((x + 1) 0.5) 255, 0, 255) Rx^T, [B, C, OH, OW] fp32 (the taps of face_resize
+    without the byte intermediate, the rounding and the clips); the tables of face_resize."""
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    oh, ow = ybounds.shape[0], xbounds.shape[0]
+    _resize_tables_ok(ow, oh, xbounds, xcoef, ybounds, ycoef)
+    y = torch.empty(b, c, oh, ow, device=x.device, dtype=torch.float32)
+    _lib.call('l2i_face_resize_lin_f32', _lib.fptr(y), _lib.fptr(x), b * c, h, w, oh, ow, _lib.ptr(xbounds), _lib.ptr(xcoef), xcoef.shape[1],
+              _lib.ptr(ybounds), _lib.ptr(ycoef), ycoef.shape[1])
+    return y
+
+
+def face_resize_lin_bwd(gy, x, ixbounds, ixcoef, iybounds, iycoef):
+    """l2i_face_resize_lin_bwd_f32: the adjoint of face_resize_lin at x, gy [B, C, OH, OW] -> gx like x.  The inverse tables of each axis
+    (facenet.inverse_tables): int32 [in, 2] = (first output, count) and [in, k] coefficients per input pixel, on the device."""
+    x, gy = x.contiguous(), gy.contiguous()
+    b, c, h, w = x.shape
+    oh, ow = gy.shape[2], gy.shape[3]
+    assert gy.shape[:2] == x.shape[:2]
+    _resize_tables_ok(w, h, ixbounds, ixcoef, iybounds, iycoef)
+    gx = torch.empty_like(x)
+    _lib.call('l2i_face_resize_lin_bwd_f32', _lib.fptr(gx), _lib.fptr(gy), _lib.fptr(x), b * c, h, w, oh, ow, _lib.ptr(ixbounds), _lib.ptr(ixcoef),
+              ixcoef.shape[1], _lib.ptr(iybounds), _lib.ptr(iycoef), iycoef.shape[1])
+    return gx
+
+
+def face_head_bwd(feat, w_t, bias, v, g_dist):
+    """l2i_face_head_bwd_f32: d sum_b g_dist[b] (1 - cos(e[b], v[b])) / d feat, with e = face_head(feat)'s embedding and v [B, E] a constant."""
+    feat = feat.contiguous()
+    b, c = feat.shape[:2]
+    e = w_t.shape[1]
+    assert w_t.shape[0] == c and bias.numel() == e and tuple(v.shape) == (b, e) and g_dist.numel() == b
+    g_feat = torch.empty_like(feat)
+    _lib.call('l2i_face_head_bwd_f32', _lib.fptr(g_feat), _lib.fptr(feat), _lib.fptr(w_t), _lib.fptr(bias), _lib.fptr(v.contiguous()),
+              _lib.fptr(g_dist.contiguous()), b, c, feat[0, 0].numel(), e)
+    return g_feat
+
+
 def panels_grid_hw(rows, cols, h, w, pad):
     """(GH, GW) of one l2i_panels_u8 grid: imgrid's size, every tile padded on its bottom and right and the last gutter cropped."""
     return rows * (h + pad) - pad, cols * (w + pad) - pad

@@ -65,6 +65,11 @@ class TrainOptions:
         p.add_argument('--f16_watch', type=int, default=0,
                        help='keep the device-side range monitor on while training and log one line per loss branch every N iterations (a host read every N '
                             'iterations), with a WARNING for non-finite entries, subnormal gradient maps or vanishing headroom; 0 = off; --precision f16 or bf16')
+        p.add_argument('--id_loss', type=float, default=0.0,
+                       help='weight W of the identity-preservation term W * mean(1 - cos(face(edited), face(original))) added to the walk loss, on the '
+                            'face network of eval.py\'s identity metric; 0 = off (the reference\'s loss); StyleGAN2 graphs, --precision f32 / bf16x3 / bf16')
+        p.add_argument('--facenet_ckpt', type=str, default=None,
+                       help='facenet_pytorch InceptionResnetV1 (vggface2) state dict for --id_loss (default: constants.facenet_path)')
         g = p.add_argument_group('nn', 'parameters used to specify NN walk')
         g.add_argument('--eps', type=float, help='step size of each NN block')
         g.add_argument('--num_steps', type=int, help='number of NN blocks')
@@ -154,7 +159,11 @@ class TrainOptions:
         if opt.f16_watch and opt.precision not in ('f16', 'bf16'):
             self.parser.error('--f16_watch reads the stored 16-bit maps: it needs --precision f16 or bf16 (got %s)' % (opt.precision or 'f32'))
         # a run without these flags keeps the namespace, opt.txt and opt.yml it had before they existed: an unset one is not carried (readers use getattr)
-        for name in ('f16_scales', 'f16_calibrate', 'f16_watch'):
+        if (opt.id_loss or 0.0) < 0:
+            self.parser.error('--id_loss takes a weight >= 0')
+        if opt.facenet_ckpt and not opt.id_loss:
+            self.parser.error('--facenet_ckpt names the face network of the identity term: it needs --id_loss W with W > 0')
+        for name in ('f16_scales', 'f16_calibrate', 'f16_watch', 'id_loss', 'facenet_ckpt'):
             if not getattr(opt, name):
                 delattr(opt, name)
 

@@ -269,7 +269,10 @@ def load_networks(device, need_vgg=True):
 
 
 class TransformGraph(WalkGraph):
-    def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, pgan_opts=None, nets=None):
+    def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, pgan_opts=None, nets=None,
+                 id_weight=0.0, facenet_ckpt=None):
+        if id_weight:
+            raise NotImplementedError('id_loss: the identity term is built for the StyleGAN2 graph (graph.TransformGraph); the PGGAN graph has none')
         WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
         if nets is None:
             nets = load_networks(self.device)

@@ -190,6 +190,9 @@ def main(multi_attr=False, argv=None):
         g = model(**graph_kwargs)
     finally:
         nets16.F16_SCALES_FLAG = None
+    if getattr(g, 'id_weight', 0.0):                 # --id_loss: the face network now, so that a missing checkpoint stops the run here and its source is recorded
+        g.check_id_loss()
+        g.face_net()
     if world > 1:                                    # one source of truth for the trainable state
         dist.broadcast_parameters(g.walk.parameters())
     if getattr(opt, 'f16_calibrate', 0):             # before the first step and the first capture: a recorded graph has the static scales baked in
