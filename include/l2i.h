@@ -597,7 +597,9 @@ int l2i_sgd_guarded_f32(float* p, const float* g, float* buf, float* step, int64
 /* [ABI 7] The regressor head and its BCE term in one launch (csrc/l2i_loss.hip) — transform_base.py:416-424: pred = fc(feat)[:, cols]; loss =
  * -mean(y log(max(pred, eps)) + (1 - y) log(max(1 - pred, eps))) (fp32 logs, float64 sum, like the torch expression on an fp32 pred and a float64 y).
  * feat [B, F], fc_w [A, F], fc_b [A] fp32; cols [K] int64 (K <= 64); target [B, K] float64 (target_f64 = 1) or fp32.  Writes loss[0] (float64), preds [B, K] and
- * g_feat [B, F] = d loss / d feat for an upstream gradient of 1 (clamp passes the gradient where its argument >= eps, as torch.clamp does). */
+ * g_feat [B, F] = d loss / d feat for an upstream gradient of 1 (clamp passes the gradient where its argument >= eps, as torch.clamp does).
+ * A NaN prediction (a non-finite feature) is kept by the clamp, as torch.clamp keeps it: preds holds the NaN, loss[0] is NaN, and that
+ * prediction contributes 0 to g_feat (neither comparison with eps holds).  Held to tests/regbce_ref.py. */
 int l2i_reg_bce_f32(double* loss, float* preds, float* g_feat, const float* feat, const float* fc_w, const float* fc_b, const int64_t* cols,
                     const void* target, int target_f64, int B, int F, int K, float eps, void* stream);
 

@@ -56,7 +56,9 @@ __global__ __launch_bounds__(256) void reg_bce_kernel(double* loss, float* preds
                 const float p = logit(bb, k);
                 if (tid == 0) {
                     const double y = tgt(bb, k);
-                    acc += y * (double)logf(fmaxf(p, eps)) + (1.0 - y) * (double)logf(fmaxf(1.f - p, eps));
+                    const float q = 1.f - p;
+                    // clamp(min = eps) as a select: torch.clamp keeps a NaN prediction and the loss is NaN; fmaxf would return eps for it
+                    acc += y * (double)logf(p < eps ? eps : p) + (1.0 - y) * (double)logf(q < eps ? eps : q);
                 }
             }
         if (tid == 0) loss[0] = -acc * inv_n;
