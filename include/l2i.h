@@ -603,6 +603,21 @@ int l2i_sgd_guarded_f32(float* p, const float* g, float* buf, float* step, int64
 int l2i_reg_bce_f32(double* loss, float* preds, float* g_feat, const float* feat, const float* fc_w, const float* fc_b, const int64_t* cols,
                     const void* target, int target_f64, int B, int F, int K, float eps, void* stream);
 
+/* [ABI 12, additive] l2i_reg_bce_f32 with the attribute-preservation term of walk training in the same launch (csrc/l2i_loss.hip; --attr_keep):
+ * feat1 / feat0 [B, F] fp32 are the pooled features of the edited and of the original image, keep_cols [M] int64 (1 <= M <= 64) the regressor
+ * outputs to hold still.  p1[b, j] / p0[b, j] = fc(feat1[b]) / fc(feat0[b]) at keep_cols[j], both by one dot-product routine in one summation order
+ * (bitwise equal rows give bitwise equal outputs); d = fl32(p1 - p0); keep = sum_bj |d| / (B M), a float64 sum of fp32 values in a fixed order (b then j
+ * ascending; no float atomics: two launches give equal bits); d keep / d p1 = sign(d) / (B M) in fp32, 0 where d == 0 (torch.abs's subgradient) and
+ * where d is NaN (keep is then NaN).  The BCE part is l2i_reg_bce_f32's arithmetic on feat1, cols [K], target [B, K]; K = 0: no BCE part, preds, cols
+ * and target may be NULL.  Writes loss[3] (float64) = {reg, keep, c_reg reg + w_keep keep} ({0, keep, w_keep keep} for K = 0), preds [B, K], pkeep
+ * [B, M, 2] = (p1, p0), and g_feat [B, F] = sum_k c_reg g_bce_pred[b, k] fc_w[cols[k]] + sum_j w_keep g_keep_pred[b, j] fc_w[keep_cols[j]] =
+ * d loss[2] / d feat1 for an upstream gradient of 1.  Refused with L2I_E_ARG before any launch, nothing written: a null loss, pkeep, g_feat, feat1,
+ * feat0, fc_w, fc_b or keep_cols; B or F <= 0; M < 1, M > 64, K < 0, K > 64; K > 0 with a null preds, cols or target.  Every entry of cols and
+ * keep_cols is a row of fc_w: the caller checks that.  Held to tests/regkeep_ref.py. */
+int l2i_reg_bce_keep_f32(double* loss, float* preds, float* pkeep, float* g_feat, const float* feat1, const float* feat0, const float* fc_w,
+                         const float* fc_b, const int64_t* cols, const void* target, int target_f64, const int64_t* keep_cols, int B, int F, int K,
+                         int M, float c_reg, float w_keep, float eps, void* stream);
+
 /* [ABI 8] The identity-preservation half of eval.py (csrc/l2i_face.hip; eval.py:170-209, latent2im_amd/facenet.py).
  * l2i_face_resize_f32: the generator's image -> the face network's input, bit-identical to the reference's clip_ims followed by PIL's
  *   Image.resize((OW, OH)) (bicubic a = -0.5, antialiased): x [planes, H, W] fp32 in [-1, 1] is quantised with clip_ims' float32 arithmetic

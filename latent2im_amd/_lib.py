@@ -184,6 +184,7 @@ _SIGNATURES = {
     'l2i_modulate_planes_multi_h8': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     'l2i_segmented_matvec_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     'l2i_reg_bce_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p]),
+    'l2i_reg_bce_keep_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p]),
     'l2i_face_resize_f32': (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     'l2i_face_head_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'l2i_face_resize_lin_f32': (c_i, [c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
@@ -235,7 +236,7 @@ TRAIN_H8_STEM = ('l2i_conv2d_wgrad_img_h8', 'l2i_conv2d_wgrad_img_ws_h8', 'l2i_r
 # has(name) tells, and the callers then stay on what that library knows (conv.run_fused_transposed: the direct transposed kernel).
 ADDITIVE = frozenset(('l2i_conv_transpose2d_family', 'l2i_convt_poly_plan_for', 'l2i_conv_h8_plan_for', 'l2i_bn_finalize_f32', 'l2i_bn_bwd_finalize_f32',
                       'l2i_repack_taps_f32', 'l2i_repack_wino_f32', 'l2i_batch_from_u8_f32', 'l2i_upfirdn2d_dual_f32', 'l2i_panels_u8',
-                      'l2i_face_resize_lin_f32', 'l2i_face_resize_lin_bwd_f32', 'l2i_face_head_bwd_f32')
+                      'l2i_face_resize_lin_f32', 'l2i_face_resize_lin_bwd_f32', 'l2i_face_head_bwd_f32', 'l2i_reg_bce_keep_f32')
                      + tuple(n + t for n in TRAIN_H8 + TRAIN_H8_STEM for t in ('', '_f16')))
 
 EXPORTS = tuple(_SIGNATURES)

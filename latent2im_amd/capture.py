@@ -42,7 +42,7 @@ def forward(g, z, alpha_for_graph, clamp=False, layers=None, content=False):
     x0 = g.get_logits({'w': w})
     if content:
         g.prefetch_content_taps(x0)
-    a0 = g.get_reg_preds(x0)
+    a0 = g.get_reg_preds(x0, keep_feats=True)         # --attr_keep: the original's pooled features stay for the loss (graph.get_keep_feats)
     if clamp:
         target, eps = g.get_alphas_clamped(a0, alpha_for_graph)
     else:

@@ -256,6 +256,41 @@ class _RegBceFn(torch.autograd.Function):
         return torch.mul(g, g_loss), None, None, None, None          # (fp32 tensor x 0-dim float64 tensor -> fp32: one launch)
 
 
+class _RegBceKeepFn(torch.autograd.Function):
+    """c_reg * _RegBceFn's loss on ``feat1`` + w_keep * mean_bj |fc(feat1) - fc(feat0)| over the columns ``keep_cols`` (--attr_keep), forward and
+    d total / d feat1 in one launch (l2i_reg_bce_keep_f32).  ``cols`` / ``target`` None: no BCE part (the PGGAN graph, whose BCE keeps its own
+    broadcast).  Returns (total, reg, keep, pkeep): three float64 scalars and the launch's read-out pkeep [B, M, 2] = (fc(feat1), fc(feat0)) at the
+    kept columns; only ``total`` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat0, fc_w, fc_b, cols, target, keep_cols, c_reg, w_keep):
+        from . import _lib
+        feat1, feat0 = feat1.detach().contiguous(), feat0.detach().contiguous()
+        assert feat1.dtype == feat0.dtype == torch.float32 and feat1.is_cuda and feat0.shape == feat1.shape and fc_w.shape[1] == feat1.shape[1]
+        B, F = feat1.shape
+        K, M = (0 if cols is None else int(cols.numel())), int(keep_cols.numel())
+        preds = None
+        if K:
+            target = target.detach().contiguous()
+            assert target.dtype in (torch.float32, torch.float64) and tuple(target.shape) == (B, K), (target.shape, B, K)
+            preds = torch.empty(B, K, dtype=torch.float32, device=feat1.device)
+        loss = torch.empty(3, dtype=torch.float64, device=feat1.device)
+        pkeep = torch.empty(B, M, 2, dtype=torch.float32, device=feat1.device)
+        g = torch.empty_like(feat1)
+        _lib.call('l2i_reg_bce_keep_f32', _lib.ptr(loss), _lib.fptr(preds), _lib.fptr(pkeep), _lib.fptr(g), _lib.fptr(feat1), _lib.fptr(feat0),
+                  _lib.fptr(fc_w), _lib.fptr(fc_b), _lib.ptr(cols) if K else None, _lib.ptr(target) if K else None,
+                  int(K > 0 and target.dtype == torch.float64), _lib.ptr(keep_cols), B, F, K, M, float(c_reg), float(w_keep), 1e-12)
+        ctx.save_for_backward(g)
+        total, reg, keep = loss[2], loss[0], loss[1]
+        ctx.mark_non_differentiable(reg, keep, pkeep)
+        return total, reg, keep, pkeep
+
+    @staticmethod
+    def backward(ctx, g_total, g_reg, g_keep, g_pkeep):
+        (g,) = ctx.saved_tensors
+        return torch.mul(g, g_total), None, None, None, None, None, None, None, None          # one launch, as _RegBceFn
+
+
 class WalkGraph:
     """What the StyleGAN2 graph (TransformGraph below) and the PGGAN graph (pggan.TransformGraph) share: bookkeeping, the walk's optimiser, the
     regressor read-out, the tail of the step, the fp16 calibration and the checkpoints.  A subclass builds its networks and its walk and supplies
@@ -278,6 +313,7 @@ class WalkGraph:
         self.ContentLoss = ContentLoss()
         self.trainEmbed = trainEmbed
         self.last_terms = None
+        self.attr_keep, self.attr_keep_attrs, self.keepIdx = 0.0, None, None          # the attribute-preservation term: off until _init_attr_keep
 
     def _make_optimizer(self, netG):
         """fp16 elements (the networks carry a scaler, load_networks): Adam with GradScaler semantics on the device — a step whose gradient holds an
@@ -301,8 +337,82 @@ class WalkGraph:
             t = self._attr_index = torch.tensor(list(self.attrIdx), dtype=torch.long, device=self.device)
         return t
 
-    def get_reg_preds(self, logit):
-        preds = self.regressor(logit).index_select(1, self._attr_columns())        # integer column select: bit-exact
+    def _init_attr_keep(self, attr_keep, attr_keep_attrs):
+        """--attr_keep W [--attr_keep_attrs A,B,...]: the term W * mean_bj |regressor(edited)[b, j] - regressor(original)[b, j]| over the regressor
+        outputs j the walk is NOT trained on — eval.py's attribute-preservation metric as a training term.  The kept columns: the table indices of
+        ``attr_keep_attrs``, by default every regressor output that is not in attrIdx, ascending.  0 (the default): nothing is built, stashed or
+        launched.  Called by the subclasses once regressor, attrTable and attrIdx exist."""
+        self.attr_keep = float(attr_keep or 0.0)
+        self.attr_keep_attrs = None if attr_keep_attrs is None else list(attr_keep_attrs)
+        self.keepIdx, self._org_feat, self.last_keep_preds = None, None, None
+        if self.attr_keep < 0 or self.attr_keep != self.attr_keep:
+            raise ValueError('attr_keep takes a weight >= 0 (got %r)' % (attr_keep,))
+        if self.attr_keep_attrs is not None and not self.attr_keep:
+            raise ValueError('attr_keep_attrs names the attributes of the attribute-preservation term: it needs attr_keep W with W > 0')
+        if not self.attr_keep:
+            return
+        n_out = int(self.regressor.fc_w.shape[0])
+        if self.attr_keep_attrs is None:
+            trained = set(self.attrIdx)
+            idx = [i for i in range(n_out) if i not in trained]
+        else:
+            idx = []
+            for name in self.attr_keep_attrs:
+                if name not in self.attrTable:
+                    raise ValueError('attr_keep_attrs: %r is not in the attribute table' % (name,))
+                if name in self.attrList:
+                    raise ValueError('attr_keep_attrs: %r is trained by this walk (attrList); it cannot be held still as well' % (name,))
+                idx.append(int(self.attrTable[name]))
+        if not idx:
+            raise ValueError('attr_keep: no regressor output is left to hold still (all %d are in attrList)' % n_out)
+        if len(idx) > 64 or len(self.attrIdx) > 64:
+            raise ValueError('attr_keep: l2i_reg_bce_keep_f32 takes at most 64 kept and 64 trained attributes (got %d and %d)' % (len(idx), len(self.attrIdx)))
+        if min(idx) < 0 or max(idx) >= n_out:
+            raise ValueError('attr_keep: attribute index %d outside the regressor\'s %d outputs' % (max(idx) if max(idx) >= n_out else min(idx), n_out))
+        if not hasattr(self.regressor, 'features'):
+            raise ValueError('attr_keep: the regressor has no pooled-feature read-out (features) for the fused head')
+        self.keepIdx = idx
+
+    def _keep_columns(self):
+        """keepIdx as a device index tensor, built once (as _attr_columns)."""
+        t = getattr(self, '_keep_index', None)
+        if t is None or t.numel() != len(self.keepIdx) or t.device != self.device:
+            t = self._keep_index = torch.tensor(list(self.keepIdx), dtype=torch.long, device=self.device)
+        return t
+
+    def _regressor_outputs(self, logit, keep_feats=False):
+        """All regressor outputs of ``logit``.  ``keep_feats`` (the training step's pass over the original image) with the attribute-preservation
+        term on: the pooled features are computed once and remembered with the image (as prefetch_content_taps remembers ``_org_taps``);
+        ``get_keep_feats`` picks them up.  The values are the regressor's own addmm.  Inference (apply_alpha, sweep, eval.py, vis_w.py) never asks:
+        nothing is stashed there."""
+        reg = self.regressor
+        if not (keep_feats and getattr(self, 'attr_keep', 0.0)):
+            return reg(logit)
+        feat = reg.features(logit)
+        self._org_feat = (logit, feat.detach())
+        return torch.addmm(reg.fc_b, feat, reg.fc_w.t())
+
+    def get_keep_feats(self, org):
+        """The regressor's pooled features of the original image, a constant of the step: what get_reg_preds left when it was handed the same
+        tensor, otherwise recomputed without a gradient."""
+        pre, self._org_feat = self._org_feat, None
+        if pre is not None and pre[0] is org:
+            return pre[1]
+        with torch.no_grad():
+            return self.regressor.features(org.detach())
+
+    def get_keep_loss(self, org, feat1, cols=None, target=None, c_reg=0.0):
+        """(total, reg, keep) of _RegBceKeepFn on ``feat1`` = regressor.features(edited image) and the original's features (get_keep_feats):
+        total = c_reg * reg + attr_keep * keep; ``cols`` None: no BCE part, total = attr_keep * keep.  ``last_keep_preds`` [B, M, 2]: the kept
+        outputs of the edited and the original image as the launch formed them."""
+        reg = self.regressor
+        total, reg_loss, keep, self.last_keep_preds = _RegBceKeepFn.apply(feat1, self.get_keep_feats(org), reg.fc_w, reg.fc_b, cols, target,
+                                                                          self._keep_columns(), float(c_reg), self.attr_keep)
+        return total, reg_loss, keep
+
+    def get_reg_preds(self, logit, keep_feats=False):
+        """The regressor outputs of ``logit`` at attrIdx.  ``keep_feats``: the training step's call on the original image (_regressor_outputs)."""
+        preds = self._regressor_outputs(logit, keep_feats).index_select(1, self._attr_columns())        # integer column select: bit-exact
         if len(preds.size()) == 1:
             preds = preds.unsqueeze(1)
         return preds
@@ -374,7 +484,7 @@ class WalkGraph:
 
 class TransformGraph(WalkGraph):
     def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, stylegan_opts,
-                 nets=None, id_weight=0.0, facenet_ckpt=None):
+                 nets=None, id_weight=0.0, facenet_ckpt=None, attr_keep=0.0, attr_keep_attrs=None):
         WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
         self.img_size = constants.resolution
         # --id_loss W: a fourth loss term W * mean_b (1 - cos(face(edited), face(original))) on the face network of eval.py's identity metric
@@ -388,6 +498,7 @@ class TransformGraph(WalkGraph):
         self.attrTable = attrTable
         self.attrList = attrList
         self.attrIdx = self.get_attr_idx()
+        self._init_attr_keep(attr_keep, attr_keep_attrs)
 
         # the reference hard-codes step = 6 (256^2, transform_base.py:285); generalised: n_latent = 2*(step+1)
         self.step = int(math.log2(self.img_size)) - 2
@@ -532,12 +643,22 @@ class TransformGraph(WalkGraph):
             with torch.cuda.stream(side[1]):
                 content_loss_list = self.get_content_loss(feed_dict['org'], feed_dict['logit'])
                 content_losses = sum(content_loss_list) / len(content_loss_list)
-        reg_loss = self.get_reg_loss(feed_dict)
+        keep_loss = None
+        if self.attr_keep:
+            # --attr_keep: the regressor branch through the one launch that also holds the other attributes still (l2i_reg_bce_keep_f32); its total
+            # already carries the 10 / 1 of the weight rule below and the option's weight
+            head, reg_loss, keep_loss = self.get_keep_loss(feed_dict['org'], self.regressor.features(logit), self._attr_columns(), feed_dict['alpha'],
+                                                           c_reg=1.0 if (no_content_loss and no_gan_loss) else 10.0)
+        else:
+            reg_loss = self.get_reg_loss(feed_dict)
         id_loss = self.get_id_loss(feed_dict['org'], logit) if self.id_weight else None
         if side[0] is not cur:
             cur.wait_stream(side[0])
             cur.wait_stream(side[1])
-        loss = reg_loss if (no_content_loss and no_gan_loss) else 10 * reg_loss
+        if keep_loss is not None:
+            loss = head
+        else:
+            loss = reg_loss if (no_content_loss and no_gan_loss) else 10 * reg_loss
         if not no_content_loss:
             loss = loss + 0.05 * content_losses
         if not no_gan_loss:
@@ -545,7 +666,8 @@ class TransformGraph(WalkGraph):
         if id_loss is not None:
             loss = loss + self.id_weight * id_loss
         self.last_terms = dict(reg=reg_loss.detach(), cont=None if content_losses is None else content_losses.detach(),
-                               gan=None if gan_loss is None else gan_loss.detach(), id=None if id_loss is None else id_loss.detach())
+                               gan=None if gan_loss is None else gan_loss.detach(), id=None if id_loss is None else id_loss.detach(),
+                               keep=None if keep_loss is None else keep_loss.detach())
         return loss
 
     # -- the step as the drivers run it ----------------------------------------------------------------------------
@@ -562,7 +684,7 @@ class TransformGraph(WalkGraph):
         out_zs = self.get_logits({'z': z_global, 'w': w_global})                 # :66
         if not no_content_loss:
             self.prefetch_content_taps(out_zs)                                   # the VGG taps of the original start beside the regressor / second generator pass
-        alpha_org = self.get_reg_preds(out_zs)                                   # :69
+        alpha_org = self.get_reg_preds(out_zs, keep_feats=True)                  # :69
         ag = torch.tensor(alpha_for_graph).float().to(self.device)               # :84-85
         if clamp:
             alpha_target, epsilon = self.get_alphas_clamped(alpha_org, ag)

@@ -63,6 +63,10 @@ def set_graph_kwargs(opt):
     if getattr(opt, 'id_loss', 0.0):                       # --id_loss W (and its checkpoint): only a run that asks for the term carries them
         kw['id_weight'] = float(opt.id_loss)
         kw['facenet_ckpt'] = getattr(opt, 'facenet_ckpt', None)
+    if getattr(opt, 'attr_keep', 0.0):                     # --attr_keep W [--attr_keep_attrs A,B,...]: likewise
+        kw['attr_keep'] = float(opt.attr_keep)
+        names = getattr(opt, 'attr_keep_attrs', None)
+        kw['attr_keep_attrs'] = None if not names else [n.strip() for n in str(names).split(',') if n.strip()]
     return kw
 
 

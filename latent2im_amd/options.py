@@ -70,6 +70,13 @@ class TrainOptions:
                             'face network of eval.py\'s identity metric; 0 = off (the reference\'s loss); StyleGAN2 graphs, --precision f32 / bf16x3 / bf16')
         p.add_argument('--facenet_ckpt', type=str, default=None,
                        help='facenet_pytorch InceptionResnetV1 (vggface2) state dict for --id_loss (default: constants.facenet_path)')
+        p.add_argument('--attr_keep', type=float, default=0.0,
+                       help='weight W of the attribute-preservation term W * mean|regressor(edited) - regressor(original)| over the regressor outputs the '
+                            'walk is not trained on (eval.py\'s attribute-preservation metric), added to the walk loss in the fused regressor head; 0 = off '
+                            '(the reference\'s loss); every graph and --precision')
+        p.add_argument('--attr_keep_attrs', type=str, default=None,
+                       help='comma-separated attribute names the term holds still (default: every attribute of the table that is not in --attrList); '
+                            'needs --attr_keep W with W > 0')
         g = p.add_argument_group('nn', 'parameters used to specify NN walk')
         g.add_argument('--eps', type=float, help='step size of each NN block')
         g.add_argument('--num_steps', type=int, help='number of NN blocks')
@@ -163,7 +170,11 @@ class TrainOptions:
             self.parser.error('--id_loss takes a weight >= 0')
         if opt.facenet_ckpt and not opt.id_loss:
             self.parser.error('--facenet_ckpt names the face network of the identity term: it needs --id_loss W with W > 0')
-        for name in ('f16_scales', 'f16_calibrate', 'f16_watch', 'id_loss', 'facenet_ckpt'):
+        if not (opt.attr_keep or 0.0) >= 0:
+            self.parser.error('--attr_keep takes a weight >= 0')
+        if opt.attr_keep_attrs and not opt.attr_keep:
+            self.parser.error('--attr_keep_attrs names the attributes of the attribute-preservation term: it needs --attr_keep W with W > 0')
+        for name in ('f16_scales', 'f16_calibrate', 'f16_watch', 'id_loss', 'facenet_ckpt', 'attr_keep', 'attr_keep_attrs'):
             if not getattr(opt, name):
                 delattr(opt, name)
 

@@ -270,7 +270,7 @@ def load_networks(device, need_vgg=True):
 
 class TransformGraph(WalkGraph):
     def __init__(self, lr, walk_type, nsliders, loss_type, eps, N_f, trainEmbed, attrList, attrTable, layers, pgan_opts=None, nets=None,
-                 id_weight=0.0, facenet_ckpt=None):
+                 id_weight=0.0, facenet_ckpt=None, attr_keep=0.0, attr_keep_attrs=None):
         if id_weight:
             raise NotImplementedError('id_loss: the identity term is built for the StyleGAN2 graph (graph.TransformGraph); the PGGAN graph has none')
         WalkGraph.__init__(self, lr, nsliders, loss_type, trainEmbed)
@@ -289,6 +289,7 @@ class TransformGraph(WalkGraph):
             self.attrTable = attrTable
         self.attrList = attrList
         self.attrIdx = self.get_attr_idx()
+        self._init_attr_keep(attr_keep, attr_keep_attrs)
         if walk_type == 'linear':
             self.walk = WalkLinearZ_free(self.dim_z, self.step, nsliders, self.attrList).to(self.device)
         else:                                                    # "MLP" (transform_base.py:270-275): every other walk type
@@ -320,6 +321,17 @@ class TransformGraph(WalkGraph):
         preds = preds.unsqueeze(1).to(torch.double)
         return self.get_bce_loss(preds, alpha_gt).mean()
 
+    def get_reg_keep_loss(self, feed_dict):
+        """--attr_keep: (reg, attr_keep * keep, keep).  The edited image's pooled features are computed once: ``get_reg_loss``'s expression on the
+        regressor's own addmm of them, and the kept outputs through l2i_reg_bce_keep_f32 without its BCE part (one launch)."""
+        reg = self.regressor
+        alpha_gt = feed_dict['alpha'].to(torch.double)
+        feat1 = reg.features(feed_dict['logit'])
+        preds = torch.addmm(reg.fc_b, feat1, reg.fc_w.t()).index_select(1, self._attr_columns())
+        preds = preds.unsqueeze(1).to(torch.double)
+        keep_total, _, keep_loss = self.get_keep_loss(feed_dict['org'], feat1)
+        return self.get_bce_loss(preds, alpha_gt).mean(), keep_total, keep_loss
+
     def get_content_loss(self, org_img, shifted_img):
         losses = self.vgg19.content_losses(org_img, shifted_img)
         return [losses[i] for i in range(4)]
@@ -333,11 +345,18 @@ class TransformGraph(WalkGraph):
         if not no_content_loss:
             content_loss_list = self.get_content_loss(feed_dict['org'], feed_dict['logit'])
             content_losses = sum(content_loss_list) / len(content_loss_list)
-        reg_loss = self.get_reg_loss(feed_dict)
+        keep_loss = None
+        if self.attr_keep:
+            reg_loss, keep_total, keep_loss = self.get_reg_keep_loss(feed_dict)
+        else:
+            reg_loss = self.get_reg_loss(feed_dict)
         loss = reg_loss if (no_content_loss or no_gan_loss) else 10 * reg_loss
         if not no_content_loss:
             loss = loss + 0.05 * content_losses
-        self.last_terms = dict(reg=reg_loss.detach(), cont=None if content_losses is None else content_losses.detach(), gan=None)
+        if keep_loss is not None:
+            loss = loss + keep_total
+        self.last_terms = dict(reg=reg_loss.detach(), cont=None if content_losses is None else content_losses.detach(), gan=None,
+                               keep=None if keep_loss is None else keep_loss.detach())
         return loss
 
     def _probe_step(self, z, alpha, no_content_loss=False, **ignored):
@@ -401,7 +420,7 @@ def walk_forward_backward(graph, z, alpha_delta, no_content_loss=False, no_gan_l
     in the walk's ``.grad``.  Returns (loss, x0, x1, alpha_org, alpha_target)."""
     with torch.no_grad():
         out_zs = graph.get_logits({'z': z})
-        alpha_org = graph.get_reg_preds(out_zs)
+        alpha_org = graph.get_reg_preds(out_zs, keep_feats=True)
     alpha_target, alpha_delta_new = graph.get_alphas(alpha_org, alpha_delta)
     z_new = graph.get_z_new_tensor(z, alpha_delta_new)
     transformed_output = graph.get_logits({'z': z_new})

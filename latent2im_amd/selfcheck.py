@@ -7,9 +7,9 @@ import numpy as np
 import torch
 
 
-def build_graph(resolution, attr_names, batch_size, lr=1e-3, walk_seed=7, device=None, transform='face'):
+def build_graph(resolution, attr_names, batch_size, lr=1e-3, walk_seed=7, device=None, transform='face', **graph_kwargs):
     """A faceGraph (CelebA attribute table) or SceneGraph (transient-scene table) on synthetic weights without touching the CLI
-    (used by smoke(), bench.py and the tests)."""
+    (used by smoke(), bench.py and the tests).  ``graph_kwargs``: further constructor keywords (``attr_keep=0.5``, ``nets=...``)."""
     from . import constants, graph, synth
     constants.resolution = resolution
     constants.BATCH_SIZE = batch_size
@@ -22,7 +22,7 @@ def build_graph(resolution, attr_names, batch_size, lr=1e-3, walk_seed=7, device
     state = np.random.get_state()
     cls = {'face': graph.faceGraph, 'scene': graph.SceneGraph}[transform]      # (find_model_using_name prints; bench.py owns stdout)
     g = cls(lr=lr, walk_type='linear', loss='l2', trainEmbed=False, attrList=list(attr_names), attrTable=table,
-            layers=None, stylegan_opts=types.SimpleNamespace(latent='w'))
+            layers=None, stylegan_opts=types.SimpleNamespace(latent='w'), **graph_kwargs)
     np.random.set_state(state)
     if hasattr(g.walk, 'w'):                               # the linear walk; the MLP walks keep torch's own (seeded by the caller) init
         with torch.no_grad():

@@ -193,6 +193,8 @@ def main(multi_attr=False, argv=None):
     if getattr(g, 'id_weight', 0.0):                 # --id_loss: the face network now, so that a missing checkpoint stops the run here and its source is recorded
         g.check_id_loss()
         g.face_net()
+    if getattr(g, 'attr_keep', 0.0) and rk == 0:     # --attr_keep: which regressor outputs the walk is trained to hold still
+        print('attribute-preservation term: weight %g over %d regressor outputs %s' % (g.attr_keep, len(g.keepIdx), list(g.keepIdx)))
     if world > 1:                                    # one source of truth for the trainable state
         dist.broadcast_parameters(g.walk.parameters())
     if getattr(opt, 'f16_calibrate', 0):             # before the first step and the first capture: a recorded graph has the static scales baked in
